@@ -1,17 +1,24 @@
 #!/usr/bin/env python
 """DRN hot-path benchmark on MI355X (driver contract: one JSON line from rank 0).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1]): Charades-STA-shaped synthetic C3D features, T=256 proposals, D=4096,
 batch 32 per GPU, first-stage losses, bf16 storage / fp32 accumulation.  One step = forward + backward of
 drn_amd.model.mainModel + gradient all-reduce (N>1) + clip_grad_norm_(0.5) + Adam (main.py:218-243), inputs
 already resident in HBM.  `value` = clips/s over all ranks (weak scaling: per-GPU batch fixed).
+
+A plain run sets up, warms up, times K steps and prints the result line (`ms_per_step` = one timed step).  --full adds
+everything else the line can carry: per-kernel roofline and the sustained-MFMA ceiling, the eager launch time, FPN + heads
+alone, the exact-f32 and bf16-feature variants, BASELINE configs[2..4], the Trainer loop and the CPU oracle baseline.
+--dump-outputs DIR writes what the last timed step produced (its losses and a fixed sample of the updated parameters) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -24,6 +31,8 @@ from drn_amd.utils.synthetic import VOCAB_SIZE, as_namespace, default_cfg, seede
 
 PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}      # MI355X dense MFMA peaks (MI355X_MICROARCH.md)
 PEAK_HBM_TBS = 8.0
+FORK_TRIES, FORK_PROBE = 2, 6        # ForkedStep.capture's candidate search (side streams tried, timing replays per candidate)
+AB_ROUNDS, AB_REPLAYS = 2, 14        # the warm-up A/B of the linear and the two-branch graph: rounds x replays of each
 
 
 def path_flops(T, D, stage):
@@ -136,6 +145,38 @@ def cpu_baseline(cfg, B, T, D, stage, steps):
                       % (steps, B, T, D, stage)}
 
 
+DUMP_SAMPLE = 1 << 18                # parameters larger than this are dumped as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, losses, model):
+    """--dump-outputs: what the last timed step hands its caller -- every loss (`<key>.npy`) -- and what it left behind, the
+    updated parameters and BN statistics (`param.<name>.npy`, `buffer.<name>.npy`, flattened; above DUMP_SAMPLE elements the ones
+    at a sorted seeded random index set, the same for every run of the same shapes).  float32, ~29 MB at the default workload
+    (asserted <= 64 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().reshape(-1).numpy() for k, v in losses.items()}
+    for kind, named in (("param.", model.named_parameters()), ("buffer.", model.named_buffers())):
+        for name, p in named:
+            flat = p.detach().float().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+                flat = flat[idx.to(flat.device)]
+            arrays[kind + name] = flat.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "outputs to dump: %d bytes" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
+def omp_threads():
+    """The thread count OMP_NUM_THREADS asks for (its first field: "16,8" -> 16), 0 when unset or unreadable."""
+    try:
+        return int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0])
+    except ValueError:
+        return 0
+
+
 def collate_like(batch, names):
     """synthetic_batch's 7 model arguments -> the 8-tuple drn_amd.data.collate_data yields (dataset.py:180-224)."""
     tok, qlen, feats, pse, gt, nprops, nframes = batch
@@ -245,7 +286,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps (100 x 2.2 ms: the ~0.4 ms of barrier + first-replay latency "
-                                                             "around the timed region weighs 0.2 %, not the 1 % it does at 20)")
+                                                             "around the timed region weighs 0.2 %%, not the 1 %% it does at 20)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--T", type=int, default=256)
@@ -255,7 +296,12 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=12, help="timed oracle steps for cpu_baseline (~1 s each on 32 threads); 0 disables")
     ap.add_argument("--no-f32", dest="f32_line", action="store_false",
                     help="skip the extra exact-f32 (1e-4 parity mode) timing of the same workload reported as `f32`")
-    ap.add_argument("--verbose", action="store_true", help="per-kernel MFMA timing table on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (roofline / per-kernel timing, eager step, FPN + heads, f32 and "
+                         "bf16-feature variants, other configs, Trainer loop, CPU baseline); off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's losses and a fixed sample of the updated parameters as DIR/<name>.npy (float32)")
+    ap.add_argument("--verbose", action="store_true", help="progress on stderr; with --full, the per-kernel MFMA timing table")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch every kernel from Python instead of replaying a hipGraph")
     ap.add_argument("--dual-stream", action="store_true",
@@ -265,6 +311,8 @@ def main():
     ap.add_argument("--no-forked", dest="forked", action="store_false",
                     help="N=1: never use the two-branch hipGraph (by default it replaces the linear one when a short A/B at warm-up "
                          "time says it is faster)")
+    ap.add_argument("--force-forked", action="store_true",
+                    help="N=1: replay the two-branch hipGraph whatever the warm-up A/B measures (tests: both launch modes, same outputs)")
     ap.add_argument("--torch-adam", action="store_true", help="torch clip_grad_norm_ + optim.Adam instead of the fused HIP step")
     ap.add_argument("--dump-gemms", default=None, metavar="PATH",
                     help="write the MFMA launches of one step in launch order [(tag, flops)] as JSON (scripts/gemm_table.py joins them "
@@ -277,9 +325,11 @@ def main():
     args = ap.parse_args()
     cmd = launch_plan(args.gpus, sys.argv[1:], os.environ, torch.cuda.device_count() if torch.cuda.is_available() else 0)
     if cmd is not None:
-        # one process per GPU: the plain command launches its own ranks (a driver that mirrors the N = 1 command gets N ranks)
+        # one process per GPU: the plain command launches its own ranks (a driver that mirrors the N = 1 command gets N ranks).
+        # A child process, not exec: the device count above has already brought up the HIP runtime in this one.
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        os.execvpe(cmd[0], cmd, env)
+        rc = subprocess.run(cmd, env=env).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)          # (killed by a signal: the shell's 128 + signal)
 
     def note(msg):                       # progress on stderr with --verbose (where a multi-rank run stopped, if it did)
         if args.verbose:
@@ -339,7 +389,15 @@ def main():
     loss_of = lambda losses: losses["loss_iou"] if stage == 2 else DF.loss_total(losses)             # main.py:222-225
 
     with torch.no_grad():            # the untrained model's loss on the resident batch (checked against the trained one after the run)
+        bn_state = {k: b.clone() for k, b in model.named_buffers()}
         initial_total = float(loss_of(model(*batch)[1]).detach().float().reshape(-1)[0])
+        DF.flush_bn_counters()
+        # (a train-mode forward moves the BN statistics: undone, so that the model the timed steps train has the same history as
+        # the two-branch candidate built below -- --dump-outputs.  By name: the forward may have re-seated a module's buffers as
+        # views of a shared one, model/fcos.py)
+        for k, b in model.named_buffers():
+            b.copy_(bn_state[k])
+        del bn_state
 
     ar_events = None                 # N>1: HIP events around the exchange wait of every timed step (exposed all-reduce time)
     ar_bucket_events = []            # ... and around each bucket's own wait (bucket index, start, end)
@@ -370,6 +428,7 @@ def main():
         torch.cuda.synchronize()
 
     run, mode, degraded, launch_ab = step, "eager", False, None
+    timed_model = model              # the model whose parameters the timed steps update (--dump-outputs)
     if args.graph:
         # all warm-up steps run on the capture stream (see drn_amd/graph.py), then the step is captured once
         from drn_amd.graph import GraphedStep
@@ -384,7 +443,17 @@ def main():
                 # the whole step (query encoder, HIP path forward+backward, fused clip+Adam) replays as ONE hipGraph: the linear
                 # one, or -- when it measures faster in a short A/B of the two captures here, during warm-up -- the same launches
                 # with two branches (drn_amd.graph.ForkedStep: query side beside input preparation / weight gradients; same bits)
-                run = GraphedStep(step, warmup=max(args.warmup, 2)).capture()
+                # (whichever graph is timed, its model has run the same number of steps when the timed loop starts -- the
+                # two-branch candidate's: warm-up + ForkedStep.capture's candidate search + the A/B -- so that what --dump-outputs
+                # writes depends on the arguments, not on which capture measured faster)
+                w = max(args.warmup, 2)
+                lin = run = GraphedStep(step, warmup=w).capture()
+                lin_steps = [w]
+                fork_tuning = FORK_TRIES * (1 + FORK_PROBE) + FORK_TRIES - 1      # ForkedStep.tuning_steps of a full search
+
+                def lin_counted():
+                    lin_steps[0] += 1
+                    return lin()
                 mode = "hipGraph replay of the full step"
                 if args.forked and not args.torch_adam:
                     try:
@@ -406,9 +475,10 @@ def main():
                         reducer_f = ddist.GradReducer(params_f, world_size=1, overlap=True, adjacent=model_f.grad_stack_groups(),
                                                       bucket_bytes=1 << 30, **gkw)
                         forked = ForkedStep(model_f, batch[:5], loss_of, reducer_f, _FA(reducer_f, lr=1e-3, max_norm=0.5), rotate=bool(gkw)).warm(
-                            max(args.warmup, 2)).capture()
+                            w).capture(tries=FORK_TRIES, probe=FORK_PROBE)
+                        fork_tuning = forked.tuning_steps
 
-                        def probe(fn, n=12):
+                        def probe(fn, n=AB_REPLAYS - 2):
                             fn(); fn()
                             torch.cuda.synchronize()
                             tp = time.perf_counter()
@@ -416,11 +486,11 @@ def main():
                                 fn()
                             torch.cuda.synchronize()
                             return (time.perf_counter() - tp) / n * 1e3
-                        ab = [(probe(run), probe(forked)) for _ in range(2)]
+                        ab = [(probe(lin_counted), probe(forked)) for _ in range(AB_ROUNDS)]
                         t_lin, t_fork = min(a for a, _ in ab), min(b for _, b in ab)
                         launch_ab = {"linear_ms": round(t_lin, 3), "forked_ms": round(t_fork, 3)}
-                        if t_fork < 0.995 * t_lin:
-                            run = forked
+                        if t_fork < 0.995 * t_lin or args.force_forked:
+                            run, timed_model = forked, model_f
                             mode = ("hipGraph replay of the full step, two branches, optimizer-first order (query encoder forward beside the "
                                     "Adam kernels of the pending update, its backward beside the weight gradients; same operation sequence as "
                                     "the plain loop)") if forked.rotate else \
@@ -430,6 +500,9 @@ def main():
                             del forked, model_f, reducer_f
                     except Exception as e:
                         print("forked graph not used (%s: %s)" % (type(e).__name__, str(e).split(chr(10))[0]), file=sys.stderr)
+                if run is lin:
+                    for _ in range(w + fork_tuning + AB_ROUNDS * AB_REPLAYS - lin_steps[0]):
+                        lin()
             else:
                 # forward+backward replay as three hipGraphs per rank; RCCL all-reduces + fused optimizer stay outside them
                 from drn_amd.graph import TwoPhaseStep
@@ -481,9 +554,12 @@ def main():
     n_timed = max(len(ar_events), 1) if ar_events else 1
     exposed_by_bucket = [round(exposed_by_bucket.get(i, 0.0) / n_timed, 4) for i in range(len(reducer.buckets))]
     ar_events = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, timed_model)
+        note("outputs written to %s" % args.dump_outputs)
     # the same step launched kernel by kernel from Python (what the hipGraph replay saves): wall clock over a few steps
     eager_ms = None
-    if args.graph and world == 1 and not args.no_kernel_timing:
+    if args.full and args.graph and world == 1 and not args.no_kernel_timing:
         for _ in range(2):
             step()
         torch.cuda.synchronize()
@@ -495,7 +571,7 @@ def main():
     # per-kernel timing of the MFMA GEMMs for the roofline object: HIP events around each launch, on the launch
     # stream, over a few extra eager steps of the same workload (events cannot sit inside a replayed graph)
     timers = None
-    if not args.no_kernel_timing:
+    if (args.full or args.dump_gemms) and not args.no_kernel_timing:
         timers = ops.kernel_timer = []
         for _ in range(max(3, min(args.steps, 5))):
             step()
@@ -531,7 +607,7 @@ def main():
 
     # FPN + heads forward (north_star's named region) as its own hipGraph on the backbone outputs of this workload
     fpn_heads = None
-    if rank == 0 and args.graph and not args.no_kernel_timing:
+    if args.full and rank == 0 and args.graph and not args.no_kernel_timing:
         try:
             with torch.no_grad():
                 g0, gates = model.forward_front(*batch[:4])
@@ -551,7 +627,7 @@ def main():
 
     # the same workload in the exact-f32 mode (the reference's own arithmetic, the <=1e-4 parity mode)
     f32_line = None
-    if rank == 0 and world == 1 and args.f32_line and args.dtype == "bf16" and args.graph and not args.torch_adam:
+    if args.full and rank == 0 and world == 1 and args.f32_line and args.dtype == "bf16" and args.graph and not args.torch_adam:
         try:
             from drn_amd.optim import FusedAdam
             m32 = build(mainModel, cfg, dev, compute_dtype=torch.float32)
@@ -581,7 +657,7 @@ def main():
     # only the K-major copy for the prop_fc weight gradient is produced -- the headline's fp32 hand-over (the reference's dtype) costs
     # the cast_transpose pass on top.  Linear graph on both sides (`launch_ab.linear_ms` is the fp32-input twin).
     bf16_feat = None
-    if rank == 0 and world == 1 and args.dtype == "bf16" and args.graph and not args.torch_adam and not args.no_kernel_timing:
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and args.graph and not args.torch_adam and not args.no_kernel_timing:
         try:
             from drn_amd.optim import FusedAdam
             mb = build(mainModel, cfg, dev, compute_dtype=cdt)
@@ -707,15 +783,15 @@ def main():
         out["f32"] = f32_line
     if bf16_feat is not None:
         out["bf16_features"] = bf16_feat
-    if rank == 0 and world == 1 and args.other_configs and args.graph and not args.torch_adam:
+    if args.full and rank == 0 and world == 1 and args.other_configs and args.graph and not args.torch_adam:
         try:
             out["other_configs"] = other_config_lines(dev)
         except Exception as e:
             print("other_configs timing failed: %s: %s" % (type(e).__name__, e), file=sys.stderr)
-    if rank == 0 and world == 1 and args.trainer_line and args.graph and not args.torch_adam:
+    if args.full and rank == 0 and world == 1 and args.trainer_line and args.graph and not args.torch_adam:
         try:
             del run
-            forked = model_f = reducer_f = params_f = None        # (the two-branch capture, its model and its streams)
+            forked = model_f = reducer_f = params_f = timed_model = None        # (the two-branch capture, its model and its streams)
             import gc
             gc.collect()
             torch.cuda.empty_cache()
@@ -723,9 +799,9 @@ def main():
         except Exception as e:
             print("trainer timing failed: %s: %s" % (type(e).__name__, e), file=sys.stderr)
     if rank == 0:
-        if world == 1 and args.cpu_steps > 0:
-            # stock PyTorch oversubscribes badly on these small convs beyond ~32 threads
-            torch.set_num_threads(min(32, os.cpu_count() or 1))
+        if args.full and world == 1 and args.cpu_steps > 0:
+            # stock PyTorch oversubscribes badly on these small convs beyond ~32 threads (and beyond the cores this job was given)
+            torch.set_num_threads(min(32, omp_threads() or len(os.sched_getaffinity(0)) or 1))
             out["cpu_baseline"] = cpu_baseline(cfg, B, T, D, stage, args.cpu_steps)
         print(json.dumps(out), flush=True)
     note("result printed")

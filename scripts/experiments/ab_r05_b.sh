@@ -6,4 +6,4 @@ for rep in 1 2 3; do
   $B --tune nt_w4h=0 2>/dev/null | get "T256 w4h=0"
   $B --tune nt_w4h=160 2>/dev/null | get "T256 w4h=128"
 done
-python bench.py --cpu-steps 0 --no-f32 --no-trainer --no-other-configs --steps 20 --verbose 2>&1 >/dev/null | grep -E "gemm_nt|gemm_wgrad" | head -30
+python bench.py --full --cpu-steps 0 --no-f32 --no-trainer --no-other-configs --steps 20 --verbose 2>&1 >/dev/null | grep -E "gemm_nt|gemm_wgrad" | head -30

@@ -14,7 +14,7 @@ else
   timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -25 > $OUT/tests.txt
 fi
 tail -25 $OUT/tests.txt
-timeout 900 python bench.py --cpu-steps 0 --no-f32 --dump-gemms $OUT/gemms.json > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --cpu-steps 0 --no-f32 --dump-gemms $OUT/gemms.json > $OUT/bench.json 2> $OUT/bench.err
 head -c 600 $OUT/bench.json; echo; python -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({k: d.get(k) for k in ('eager_ms_per_step', 'trainer')}))" $OUT/bench.json; tail -3 $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $GRAFT_REPO_ROOT/bench.py --cpu-steps 0 --no-kernel-timing --no-f32 --no-trainer --no-other-configs --no-forked --steps 30 > $OUT/bench_under_trace.json 2> /dev/null

@@ -13,7 +13,7 @@ PMCCMD="python $GRAFT_REPO_ROOT/bench.py --cpu-steps 0 --no-kernel-timing --no-f
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o f -- $PMCCMD > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o w -- $PMCCMD > /dev/null 2>&1
 cd $GRAFT_REPO_ROOT
-python bench.py --dump-gemms $OUT/gemms.json > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --dump-gemms $OUT/gemms.json > $OUT/bench_default.json 2> $OUT/bench_default.err
 python scripts/rocprof_summary.py $OUT/trace/t_results.db 35 > $OUT/kernel_stats.txt
 python scripts/rocprof_step.py $OUT/trace/t_results.db > $OUT/step_kernel_sequence.txt
 python scripts/gemm_table.py $OUT/trace/t_results.db $OUT/gemms.json 2500 $OUT/gemm_in_graph.json > $OUT/gemm_table.txt 2> $OUT/gemm_table.err

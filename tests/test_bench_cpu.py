@@ -55,3 +55,47 @@ def test_cli_refuses_two_gpus_on_a_box_without_them():
     assert r.returncode != 0
     assert "{" not in r.stdout
     assert "refusing" in r.stderr
+
+
+def test_dump_outputs_writes_losses_and_a_fixed_parameter_sample(tmp_path):
+    """--dump-outputs: one float32 .npy per loss and per parameter / buffer, large parameters as the same seeded sample every time,
+    the whole dump within 64 MB."""
+    import numpy as np
+    import torch
+    from drn_amd.model import mainModel
+    from drn_amd.utils.synthetic import VOCAB_SIZE, as_namespace, default_cfg, seeded_state_dict
+    m = mainModel(VOCAB_SIZE, as_namespace(default_cfg("C3D", 4096, 1)))
+    m.load_state_dict(seeded_state_dict(m, 0))
+    losses = {"loss_cls": torch.tensor(0.5), "loss_reg": torch.tensor([0.25], dtype=torch.bfloat16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), losses, m)
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b")))
+    assert "loss_cls.npy" in names and "loss_reg.npy" in names and "param.prop_fc.weight.npy" in names
+    assert len([n for n in names if n.startswith("param.")]) == len(list(m.parameters()))
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(str(tmp_path / "a" / "loss_reg.npy"))[0]) == 0.25
+    big = np.load(str(tmp_path / "a" / "param.prop_fc.weight.npy"))
+    assert big.size == bench.DUMP_SAMPLE
+    assert np.isin(big, m.prop_fc.weight.detach().reshape(-1).numpy()).all()
+    small = np.load(str(tmp_path / "a" / "param.prop_fc.bias.npy"))
+    np.testing.assert_array_equal(small, m.prop_fc.bias.detach().numpy())
+
+
+def test_cli_has_full_and_dump_outputs_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_omp_thread_count_reads_the_first_field_and_never_raises(monkeypatch):
+    for value, want in (("16", 16), ("16,8", 16), ("", 0), ("many", 0)):
+        monkeypatch.setenv("OMP_NUM_THREADS", value)
+        assert bench.omp_threads() == want, value
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    assert bench.omp_threads() == 0
