@@ -12,7 +12,7 @@ Harness-side shims, none of which touch reference files:
   3. wrap the focal-loss gamma/alpha in lists so the in-repo CPU formula
      (model/layers/sigmoid_focal_loss.py:40-52) indexes them.
 
-usage: python tests/golden/gen_golden.py
+usage: python tests/golden/gen_golden.py [classes|loc0|evalrs|layers|metrics|dataset|trajectory]
 """
 import os
 import sys
@@ -98,7 +98,46 @@ def matched_gt(m, batch, loc0=False):
     return torch.tensor(gt, dtype=torch.float64)
 
 
-def run_case(name, B, T, D, stage, train=True, match=False, num_class=None, loc0=False):
+def eval_forward(m, batch):
+    """One eval-mode forward in a scratch cwd (model/fcos.py:182 pickles into cwd in eval)."""
+    m.eval()
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            return m(*batch)
+        finally:
+            os.chdir(cwd)
+
+
+def set_running_stats(m, B, T, D, seed=2):
+    """Non-trivial BatchNorm running statistics: one train-mode forward (no_grad) on another batch with every momentum at 1.0,
+    so each running_mean / running_var holds that batch's statistics (the towers' BNs: of the last level they saw)."""
+    bns = [mod for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm1d)]
+    for bn in bns:
+        bn.momentum = 1.0
+    m.train()
+    with torch.no_grad():
+        m(*synthetic_batch(B, T, D, seed=seed))
+    for bn in bns:
+        bn.momentum = 0.1
+    m.fcos.loss_evaluator.total_points = []
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed with a fixed member timestamp: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+def run_case(name, B, T, D, stage, train=True, match=False, num_class=None, loc0=False, rs=False):
+    """rs: eval with real running statistics (set_running_stats), recorded as rs/<key>, plus def/logits0 = level-0 logits
+    with the seeded 0 / 1 statistics."""
     ftype = "C3D" if D == 4096 else "TINY"
     cfg = default_cfg(ftype, D, stage)
     if num_class is not None:                              # model/fcos.py:27,43: cls_logits gets fcos_num_class - 1 channels
@@ -110,6 +149,19 @@ def run_case(name, B, T, D, stage, train=True, match=False, num_class=None, loc0
     out = {"B": B, "T": T, "D": D, "stage": stage, "train": int(train), "gt": batch[4].numpy()}
     if num_class is not None:
         out["num_class"] = num_class
+    if rs:
+        assert not train
+        caught = {}
+        h = m.fcos.head.register_forward_hook(lambda mod, i, o: caught.__setitem__("head", o))
+        with torch.no_grad():
+            eval_forward(m, batch)
+        h.remove()
+        m.fcos.loss_evaluator.total_points = []
+        out["def/logits0"] = caught["head"][0][0].detach().numpy()
+        set_running_stats(m, B, T, D)
+        for k, v in m.state_dict().items():
+            if k.endswith(("running_mean", "running_var", "num_batches_tracked")):
+                out["rs/" + k] = v.numpy().copy()
     taps = {}
     hooks = []
     mods = dict(m.named_modules())
@@ -159,7 +211,10 @@ def run_case(name, B, T, D, stage, train=True, match=False, num_class=None, loc0
         out["score"] = torch.cat([b["scores"] for b in boxes]).detach().numpy()
         out["loc"] = torch.cat([b["locations"] for b in boxes]).detach().numpy()
         out["level"] = np.array([x for b in boxes for lv in b["level"] for x in lv])
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+    if rs:
+        save_npz(os.path.join(HERE, name + ".npz"), out)
+    else:
+        np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print(name, {k: out[k] for k in ("loss_cls", "loss_reg", "loss_iou")},
           "npos_iou" if stage != 1 else "", flush=True)
 
@@ -463,6 +518,13 @@ if __name__ == "__main__":
         run_case("tiny_s3_loc0", 2, 32, 64, 3, match=True, loc0=True)
         run_case("tiny_s2_loc0", 2, 32, 64, 2, match=True, loc0=True)
         run_error_cases()
+        sys.exit(0)
+    if sys.argv[1:] == ["evalrs"]:                         # eval mode with real BatchNorm running statistics (set_running_stats)
+        run_case("tiny_eval_rs", 2, 32, 64, 3, train=False, match=True, rs=True)
+        run_case("tiny_eval_rs_s1", 3, 64, 64, 1, train=False, rs=True)
+        run_case("tiny_k3_eval_rs", 2, 32, 64, 3, train=False, num_class=4, rs=True)
+        run_case("c3d_eval_rs", 2, 64, 4096, 3, train=False, match=True, rs=True)
+        run_case("tiny_eval_rs_b1", 1, 32, 64, 1, train=False, rs=True)       # single-clip inference (errors.json: it runs)
         sys.exit(0)
     if sys.argv[1:] == ["layers"]:
         run_layers()

@@ -10,7 +10,8 @@ from helpers import build_model, case_inputs, load_golden, run_and_compare
 
 CASES = ["tiny_s1", "tiny_s2", "tiny_s3", "tiny_eval", "tiny_eval_s1", "c3d_s1", "c3d_s3",
          "tiny_k3_s1", "tiny_k3_s3", "tiny_k3_eval", "tiny_k2_s3",          # k3: fcos_num_class = 4 (model/fcos.py:27,43), off every shipped config
-         "tiny_s3_loc0", "tiny_s2_loc0"]            # GT matched at location 0: the clamp of model/loss.py:180-181 acts on a tIoU > 0.9 positive
+         "tiny_s3_loc0", "tiny_s2_loc0",            # GT matched at location 0: the clamp of model/loss.py:180-181 acts on a tIoU > 0.9 positive
+         "tiny_eval_rs", "tiny_eval_rs_s1", "tiny_k3_eval_rs", "c3d_eval_rs", "tiny_eval_rs_b1"]   # eval with real running statistics
 
 
 @pytest.mark.parametrize("name", CASES)
