@@ -131,6 +131,17 @@ class LossLevel(ctypes.Structure):
     _fields_ = [("L", c_int32), ("stride", c_float), ("lo", c_float), ("hi", c_float)]
 
 
+c_double = ctypes.c_double
+# argument lists of include/drn_hip.h, in its order, for the entry points that declare them (tests/test_grounding_cpu.py counts them
+# against the header)
+SIGNATURES = {
+    "drn_select_moments": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p],
+    "drn_gate_gather_fwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                            c_int, c_int, c_int, c_void_p],
+}
+
+
 def lib():
     """Load (once) and return the ctypes handle; raises DrnError loudly when absent."""
     global _lib
@@ -145,6 +156,10 @@ def lib():
                    "drn_diag_mfma_ws_bytes"):
             if hasattr(_lib, fn):
                 getattr(_lib, fn).restype = c_int64
+        # (ctypes passes a Python float as nothing at all without a declared signature: the calls that take a double declare theirs)
+        for fn, sig in SIGNATURES.items():
+            if hasattr(_lib, fn):
+                getattr(_lib, fn).argtypes, getattr(_lib, fn).restype = sig, c_int
     return _lib
 
 

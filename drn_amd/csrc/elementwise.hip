@@ -789,6 +789,79 @@ extern "C" int drn_gate_fwd(const void* z, int ld_z, const float* gate, int ldg,
   return drn_launch_status("drn_gate_fwd");
 }
 
+// ---------------------------------------------------------------- query gate with a video indirection (shared videos)
+// Q queries read V <= Q videos: out[q,t,c] = z[vid[q],t,c] * gate[q,c] for c < C (gate_fwd_kernel's arithmetic, statement for
+// statement: vid = identity gives its bits) and out[q,t,C+p] = pos[vid[q],t,p], the position-embedding columns of the video
+// (model/main_model.py:51-59,67 + model/backbone.py:28-32 per (query, video) pair).  Writes Q*L*(C+P) elements; a video's rows are
+// read once per query that uses it (from L2 / Infinity Cache after the first).  An index outside [0, V) is clamped for the loads
+// and its rows are written as zeros.  16-byte vectors, 4 rows per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void gate_gather_fwd_kernel(const T* __restrict__ z, int ld_z, const float* __restrict__ gate, int ldg,
+                                                              const T* __restrict__ pos, int ld_pos, const int* __restrict__ vid, int V,
+                                                              T* __restrict__ out, int ld_out, int M, int L, int C, int P) {
+  constexpr int N = V16<T>::N, U = 4;
+  const int cvec = C / N, nvec = (C + P) / N;
+  const long total = (long)((M + U - 1) / U) * nvec;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int v = (int)(i % nvec);
+    const int m0 = (int)(i / nvec) * U;
+    const bool gated = v < cvec;
+    const int c0 = gated ? v * N : (v - cvec) * N;        // column in z / in pos
+    typename V16<T>::raw_t r[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int m = min(m0 + u, M - 1);
+      const int q = m / L, src = vid[q];
+      ok[u] = src >= 0 && src < V;
+      const long row = (long)min(max(src, 0), V - 1) * L + (m - q * L);
+      r[u] = gated ? V16<T>::ldraw(z + row * ld_z + c0) : V16<T>::ldraw(pos + row * ld_pos + c0);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int m = m0 + u;
+      if (m >= M) break;
+      T* op = out + (long)m * ld_out + v * N;
+      float x[N];
+      V16<T>::cvt(r[u], x);
+      if (!ok[u]) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] = 0.f;
+        V16<T>::store(op, x);
+      } else if (gated) {
+        const float* gp = gate + (long)(m / L) * ldg + c0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] *= gp[k];
+        V16<T>::store(op, x);
+      } else {
+        *(typename V16<T>::raw_t*)op = r[u];
+      }
+    }
+  }
+}
+extern "C" int drn_gate_gather_fwd(const void* z, int ld_z, const float* gate, int ldg, const void* pos, int ld_pos, const int32_t* vid,
+                                   const int32_t* vid_host, int V, void* out, int ld_out, int Q, int L, int C, int P, int dtype,
+                                   void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(z && gate && vid && out && V > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && (P == 0) == (pos == nullptr),
+                "drn_gate_gather_fwd: bad args");
+  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL && (long)V * L <= 0x7fffffffL, "drn_gate_gather_fwd: more than 2^31 rows");
+  if (vid_host)
+    for (int q = 0; q < Q; ++q)
+      DRN_CHECK_ARG(vid_host[q] >= 0 && vid_host[q] < V, "drn_gate_gather_fwd: query %d reads video %d of %d", q, (int)vid_host[q], V);
+  DISPATCH_DT(dtype, "drn_gate_gather_fwd", {
+    constexpr int N = V16<T>::N;
+    DRN_CHECK_ARG(C % N == 0 && P % N == 0 && ld_z % N == 0 && ld_out % N == 0 && (!pos || ld_pos % N == 0) && ldg % 4 == 0 &&
+                      ((((uintptr_t)z) | ((uintptr_t)out) | ((uintptr_t)gate) | ((uintptr_t)pos)) & 15) == 0,
+                  "drn_gate_gather_fwd: C / P / ld must be 16-byte multiples");
+    DRN_CHECK_ARG(ld_z >= C && ld_out >= C + P && (!pos || ld_pos >= P) && ldg >= C, "drn_gate_gather_fwd: a row stride is shorter than its row");
+    const int M = Q * L;
+    gate_gather_fwd_kernel<T><<<ew_blocks((long)cdiv(M, 4) * ((C + P) / N), 256, 8192), 256, 0, (hipStream_t)stream>>>(
+        (const T*)z, ld_z, gate, ldg, (const T*)pos, ld_pos, vid, V, (T*)out, ld_out, M, L, C, P);
+  });
+  return drn_launch_status("drn_gate_gather_fwd");
+}
+
 // ---------------------------------------------------------------- query-gate backward
 // forward was G[s,t,c] = act[s,t,c] * gate[s,c].  Here:
 //   dC[s,t,c] = (add ? add[s,t,c] : 0) + dG[s,t,c] * gate[s,c]        dgate[s,c] = sum_t dG[s,t,c] * act[s,t,c]

@@ -127,25 +127,18 @@ extern "C" int drn_postprocess(const DrnLossLevel* levels, int nlevels, int B, c
 // out[b][q] = position of the first survivor that hits (0-based), or K when none of the first K does.
 // every level table drn_postprocess accepts fits: DRN_MAX_GROUPS levels of at most PP_MAX_L locations
 #define ER_MAX_CAND (DRN_MAX_GROUPS * PP_MAX_L)
-__global__ __launch_bounds__(64) void eval_recall_kernel(const float* __restrict__ det, const float* __restrict__ scores,
-                                                         const int* __restrict__ counts, int nlevels, int rows_per_clip,
-                                                         const void* __restrict__ gt, int gt_f64, const double* __restrict__ ious,
-                                                         int K, int* __restrict__ out, int n_iou) {
-  __shared__ unsigned char alive[ER_MAX_CAND];
-  const int b = blockIdx.x, q = blockIdx.y, lane = threadIdx.x;
-  int n = 0;
-  for (int l = 0; l < nlevels; ++l) n += counts[b * nlevels + l];
-  const float* __restrict__ d = det + (long)b * rows_per_clip * 2;
-  const float* __restrict__ s = scores + (long)b * rows_per_clip;
-  const double iou_thr = ious[q], overlap = ious[q] - 0.05;
-  const double g0 = gt_f64 ? ((const double*)gt)[b * 2] : (double)((const float*)gt)[b * 2];
-  const double g1 = gt_f64 ? ((const double*)gt)[b * 2 + 1] : (double)((const float*)gt)[b * 2 + 1];
-  const bool empty = n == 0;                 // model/inference.py:192-197: one detection (0, 1) with score 1
-  if (empty) n = 1;
+
+// The pick loop both wave-per-clip kernels below run: up to K times, find the best candidate still alive -- highest score, ties to
+// the LATER index -- call on_pick(p, index, score, x1, x2) with wave-uniform arguments, and strike out everything it suppresses at
+// `overlap` (and itself).  `empty`: the clip has no candidates and stands for the single fallback detection (0, 1) with score 1
+// (model/inference.py:192-197); n is then 1 and d / s are not read.  Returns the number of picks made.
+template <typename F>
+__device__ __forceinline__ int nms_pick_loop(unsigned char* alive, const float* __restrict__ d, const float* __restrict__ s, int n,
+                                             const bool empty, const double overlap, const int K, const int lane, F on_pick) {
   for (int j = lane; j < n; j += 64) alive[j] = 1;
   __syncthreads();
-  int first_hit = K;
-  for (int p = 0; p < K; ++p) {
+  int p = 0;
+  for (; p < K; ++p) {
     float bs = -1.f;
     int bj = -1;
     for (int j = lane; j < n; j += 64)
@@ -161,10 +154,7 @@ __global__ __launch_bounds__(64) void eval_recall_kernel(const float* __restrict
     }
     if (bj < 0) break;                        // nothing left
     const double x1 = empty ? 0.0 : (double)d[bj * 2], x2 = empty ? 1.0 : (double)d[bj * 2 + 1];
-    if (first_hit == K) {
-      const double iou = (fmin(g1, x2) - fmax(g0, x1)) / (fmax(g1, x2) - fmin(g0, x1));      // evaluate_utils.py:228-232
-      if (iou >= iou_thr) first_hit = p;
-    }
+    on_pick(p, bj, bs, x1, x2);
     const double len = x2 - x1;
     for (int j = lane; j < n; j += 64)
       if (alive[j]) {
@@ -175,6 +165,31 @@ __global__ __launch_bounds__(64) void eval_recall_kernel(const float* __restrict
       }
     __syncthreads();
   }
+  return p;
+}
+
+__global__ __launch_bounds__(64) void eval_recall_kernel(const float* __restrict__ det, const float* __restrict__ scores,
+                                                         const int* __restrict__ counts, int nlevels, int rows_per_clip,
+                                                         const void* __restrict__ gt, int gt_f64, const double* __restrict__ ious,
+                                                         int K, int* __restrict__ out, int n_iou) {
+  __shared__ unsigned char alive[ER_MAX_CAND];
+  const int b = blockIdx.x, q = blockIdx.y, lane = threadIdx.x;
+  int n = 0;
+  for (int l = 0; l < nlevels; ++l) n += counts[b * nlevels + l];
+  const float* __restrict__ d = det + (long)b * rows_per_clip * 2;
+  const float* __restrict__ s = scores + (long)b * rows_per_clip;
+  const double iou_thr = ious[q], overlap = ious[q] - 0.05;
+  const double g0 = gt_f64 ? ((const double*)gt)[b * 2] : (double)((const float*)gt)[b * 2];
+  const double g1 = gt_f64 ? ((const double*)gt)[b * 2 + 1] : (double)((const float*)gt)[b * 2 + 1];
+  const bool empty = n == 0;                 // model/inference.py:192-197: one detection (0, 1) with score 1
+  if (empty) n = 1;
+  int first_hit = K;
+  nms_pick_loop(alive, d, s, n, empty, overlap, K, lane, [&](int p, int, float, double x1, double x2) {
+    if (first_hit == K) {
+      const double iou = (fmin(g1, x2) - fmax(g0, x1)) / (fmax(g1, x2) - fmin(g0, x1));      // evaluate_utils.py:228-232
+      if (iou >= iou_thr) first_hit = p;
+    }
+  });
   if (lane == 0) out[b * n_iou + q] = first_hit;
 }
 
@@ -188,4 +203,60 @@ extern "C" int drn_eval_recall(const float* det, const float* scores, const int3
   eval_recall_kernel<<<dim3(B, n_iou), 64, 0, (hipStream_t)stream>>>(det, scores, counts, nlevels, rows_per_clip, gt, gt_is_f64, ious,
                                                                      max_topk, first_hit, n_iou);
   return drn_launch_status("drn_eval_recall");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The moments themselves: the first K survivors of that same NMS, best first, one wavefront per clip
+// (utils/evaluate_utils.py:91-107 sort + :186-212 nms_temporal; the fallback moment of model/inference.py:192-197 for a clip without
+// candidates).  The detections are copied, not recomputed; `level` comes from the running sum of the clip's per-level counts.
+__global__ __launch_bounds__(64) void select_moments_kernel(const float* __restrict__ det, const float* __restrict__ scores,
+                                                            const int* __restrict__ counts, int nlevels, int rows_per_clip,
+                                                            double overlap, int K, float* __restrict__ seg, float* __restrict__ score,
+                                                            int* __restrict__ level, int* __restrict__ index, int* __restrict__ n_out) {
+  __shared__ unsigned char alive[ER_MAX_CAND];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int n = 0;
+  for (int l = 0; l < nlevels; ++l) n += counts[b * nlevels + l];
+  n = min(n, rows_per_clip);                 // (counts are the post-processor's; a corrupt table must not reach past the clip's slots)
+  const float* __restrict__ d = det + (long)b * rows_per_clip * 2;
+  const float* __restrict__ s = scores + (long)b * rows_per_clip;
+  const bool empty = n <= 0;
+  if (empty) n = 1;
+  const long o = (long)b * K;
+  const int np = nms_pick_loop(alive, d, s, n, empty, overlap, K, lane, [&](int p, int j, float sj, double, double) {
+    if (lane != 0) return;
+    int lv = -1;
+    if (!empty) {
+      int end = 0;
+      for (lv = 0; lv < nlevels - 1; ++lv) {
+        end += counts[b * nlevels + lv];
+        if (j < end) break;
+      }
+    }
+    seg[(o + p) * 2 + 0] = empty ? 0.f : d[j * 2];
+    seg[(o + p) * 2 + 1] = empty ? 1.f : d[j * 2 + 1];
+    score[o + p] = sj;
+    level[o + p] = lv;
+    index[o + p] = empty ? -1 : j;
+  });
+  for (int p = np + lane; p < K; p += 64) {
+    seg[(o + p) * 2 + 0] = 0.f;
+    seg[(o + p) * 2 + 1] = 0.f;
+    score[o + p] = 0.f;
+    level[o + p] = -1;
+    index[o + p] = -1;
+  }
+  if (lane == 0) n_out[b] = np;
+}
+
+extern "C" int drn_select_moments(const float* det, const float* scores, const int32_t* counts, int B, int nlevels, int rows_per_clip,
+                                  double overlap, int K, float* seg, float* score, int32_t* level, int32_t* index, int32_t* n,
+                                  void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(det && scores && counts && seg && score && level && index && n && B > 0 && nlevels >= 1 && K >= 1,
+                "drn_select_moments: bad args");
+  DRN_CHECK_ARG(rows_per_clip > 0 && rows_per_clip <= ER_MAX_CAND, "drn_select_moments: %d candidate slots per clip (max %d)", rows_per_clip, ER_MAX_CAND);
+  select_moments_kernel<<<B, 64, 0, (hipStream_t)stream>>>(det, scores, counts, nlevels, rows_per_clip, overlap, K, seg, score, level,
+                                                           index, n);
+  return drn_launch_status("drn_select_moments");
 }

@@ -105,6 +105,17 @@ class PostProcessRunner(object):
         return iou_topk_dict["topk"], accs
 
 
+def select_moments(preds, k, overlap):
+    """The first k temporal-NMS survivors of one query's [[start, end, score], ...] predictions, best first: what the evaluator looks
+    at (evaluate_utils.py:91-107 stable sort by descending score, then :186-212 nms_temporal at `overlap`; its value there is
+    iou - 0.05), as indices into `preds`.  The host twin of drn_select_moments (ops.select_moments), for callers that hold host
+    records.  An empty list has no picks (the device path's fallback moment is the post-processor's, inference.py:192-197)."""
+    order = sorted(range(len(preds)), key=lambda i: preds[i][-1], reverse=True)
+    picks = PostProcessRunner.nms_temporal([preds[i][0] for i in order], [preds[i][1] for i in order], [preds[i][-1] for i in order],
+                                           overlap)
+    return [order[i] for i in picks[:max(int(k), 0)]]
+
+
 def recall_from_first_hits(first_hits, ious, topks):
     """accs in run_evaluate's order (for iou: for topk) from the per-query first-hit positions of ops.eval_recall:
     first_hits (n_queries, len(ious)) integer array."""

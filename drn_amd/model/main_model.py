@@ -116,9 +116,11 @@ class mainModel(nn.Module):
         front = set(id(p) for p in self.front_parameters())
         return [p for p in self.parameters() if id(p) not in front]
 
-    def prepare_input(self, props_features, props_start_end):
+    def prepare_input(self, props_features, props_start_end, split_gate=None):
         """The part of the input stage that does not depend on the query (cast / transposed copy of the features, position
-        features, the warmed GEMM copy of the prop_fc weight): drn_amd.graph.DualStreamStep runs it beside the query encoder."""
+        features, the warmed GEMM copy of the prop_fc weight): drn_amd.graph.DualStreamStep runs it beside the query encoder.
+        split_gate: None = the model's `split_gate` attribute (set by the schedules that want it), True = the prop_fc product
+        runs here, un-gated (forward_heads_shared)."""
         if not props_features.is_cuda:
             raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % props_features.device)
         dt = self.compute_dtype
@@ -135,7 +137,8 @@ class mainModel(nn.Module):
             fc = types.SimpleNamespace(weight=F.pad(self.prop_fc.weight, (0, pad, 0, pad)), bias=F.pad(self.prop_fc.bias, (0, pad)))
         else:
             fc = self.prop_fc
-        prep = DF.input_prep(props_features, props_start_end, fc, dt, want_wgrad, split_gate=getattr(self, "split_gate", False),
+        prep = DF.input_prep(props_features, props_start_end, fc, dt, want_wgrad,
+                             split_gate=getattr(self, "split_gate", False) if split_gate is None else split_gate,
                              position_transform=self.position_transform)
         prep.fc = fc
         return prep
@@ -158,8 +161,8 @@ class mainModel(nn.Module):
         g0._drn_tail = tail          # rides on the tensor object to forward_trunk (a caller that replaces g0 simply loses it)
         return g0, gates
 
-    def forward_trunk(self, g0, gates, gt_start_end):
-        """Backbone (gates[1:] only: level 0 is already applied), FPN, heads, losses / post-processor."""
+    def _trunk_heads(self, g0, gates):
+        """Backbone (gates[1:] only: level 0 is already applied), FPN, heads -> (locations, box_cls, box_reg, iou_scores)."""
         backbone_feats = self.backbone_net.forward_from_stage(g0, gates, tail=getattr(g0, "_drn_tail", None))
         feats = self.fpn.forward_nlc(backbone_feats)
         head = self.fcos.head
@@ -173,6 +176,12 @@ class mainModel(nn.Module):
             self.taps["head"] = (box_cls, box_reg, [], iou_scores)
         fc = self.fcos
         locations = [fc.compute_locations_per_level(L, fc.fpn_strides[l], logits.device) for l, (_, L) in enumerate(geo)]
+        return locations, box_cls, box_reg, iou_scores
+
+    def forward_trunk(self, g0, gates, gt_start_end):
+        """Backbone, FPN, heads (_trunk_heads), losses / post-processor."""
+        locations, box_cls, box_reg, iou_scores = self._trunk_heads(g0, gates)
+        fc = self.fcos
         # main_model.py:74 casts the ground truth with .float(): the loss kernel does that on load (fp64 or fp32 in)
         targets = gt_start_end if gt_start_end.dtype in (torch.float32, torch.float64) else gt_start_end.float()
         # the BatchNorm step counters owed by this forward pass are applied by the loss's own launch (DF.take_bn_counters)
@@ -182,6 +191,51 @@ class mainModel(nn.Module):
             res = fc._forward_test(locations, box_cls, box_reg, targets, iou_scores)
         DF.flush_bn_counters()
         return res
+
+    def forward_heads_shared(self, query_tokens, query_length, props_features, props_start_end, video_index=None):
+        """Inference without a ground truth, for Q queries over V <= Q videos: -> (locations, box_cls, box_reg, iou_scores), the
+        per-level head outputs of the Q (query, video) pairs -- no loss, no targets, no BatchNorm counter or buffer touched.
+        props_features (V, T, D), props_start_end (V, T, 2|3); video_index: (Q,) integer tensor, query q reads video
+        video_index[q] (None: Q = V, query q reads video q).  The part of the forward that does not depend on the query -- the cast,
+        prop_fc (63 % of the forward's FLOPs at the benchmarked shape) and the position embedding -- runs once per VIDEO
+        (prepare_input(split_gate=True)); the query gate is applied per (query, video) pair by ops.gate_gather_fwd, which writes
+        conv0's (Q, T, D+P) input; the trunk is the one every forward runs.  Eval mode under torch.no_grad() only."""
+        if self.training:
+            raise DrnError("forward_heads_shared is inference only: call model.eval() first")
+        if torch.is_grad_enabled():
+            raise DrnError("forward_heads_shared is inference only: run it under torch.no_grad()")
+        for t in (props_features, props_start_end, query_tokens):
+            if not t.is_cuda:
+                raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
+        V, T, _ = props_features.shape
+        prep = self.prepare_input(props_features, props_start_end, split_gate=True)
+        gates = self.encode_query(query_tokens, query_length)
+        Q = int(gates[0].shape[0])
+        dev = props_features.device
+        vid_host = None
+        if video_index is None:
+            if Q != V:
+                raise DrnError("forward_heads_shared: %d queries for %d videos need a video_index" % (Q, V))
+            vid = torch.arange(Q, dtype=torch.int32, device=dev)
+        else:
+            if video_index.dim() != 1 or video_index.numel() != Q or video_index.is_floating_point():
+                raise DrnError("forward_heads_shared: video_index must be a (%d,) integer tensor" % Q)
+            if not video_index.is_cuda:                    # a host index is checked before the launch; a device one costs no sync
+                vid_host = video_index.to(torch.int32).contiguous()
+            vid = video_index.to(device=dev, dtype=torch.int32).contiguous()
+        pad = self._front_pad(self.feature_dim)
+        gate0 = F.pad(gates[0], (0, pad)) if pad else gates[0]
+        D = prep.dims[2]                                   # (the zero-padded width inside a bf16 model whose rows need it)
+        P = self.position_transform.weight.shape[0]
+        code = ops.dtype_code(prep.Z)
+        if prep.G0 is not None:                            # input_prep filled the position columns of a (V, T, D+P) buffer
+            pos, ld_pos = prep.G0.view(V * T, D + P)[:, D:], D + P
+        else:
+            pos, ld_pos = torch.empty((V * T, P), dtype=prep.Z.dtype, device=dev), P
+            ops.pos_embed_fwd(prep.pf, self.position_transform.weight.detach(), self.position_transform.bias.detach(), pos, P, V * T, P, code)
+        g0 = torch.empty((Q, T, D + P), dtype=prep.Z.dtype, device=dev)
+        ops.gate_gather_fwd(prep.Z, D, gate0.contiguous(), pos, ld_pos, vid, V, g0, D + P, Q, T, D, P, code, vid_host=vid_host)
+        return self._trunk_heads(g0, gates)
 
     def forward(self, query_tokens, query_length, props_features, props_start_end, gt_start_end, props_num=None,
                 num_frames=None):

@@ -610,6 +610,22 @@ def gate_fwd(z, ld_z, gate, out, ld_out, nseq, L, C, dtype):
     check(lib().drn_gate_fwd(_p(z), ld_z, _p(gate), gate.stride(0), _p(out), ld_out, nseq, L, C, dtype, _stream()), "drn_gate_fwd")
 
 
+def gate_gather_fwd(z, ld_z, gate, pos, ld_pos, vid, V, out, ld_out, Q, L, C, P, dtype, vid_host=None):
+    """out[q, t, :C] = z[vid[q], t, :C] * gate[q] and out[q, t, C:C+P] = pos[vid[q], t, :P] (drn_gate_gather_fwd): Q queries over V
+    shared videos, written into conv0's (Q, L, C+P) input.  vid: (Q,) int32 on the device; vid_host: an optional host copy (int32,
+    contiguous) -- given, an index outside [0, V) raises before the launch; without it the kernel writes zeros for such a query."""
+    _need_gpu(z, gate, pos, vid, out)
+    if vid.dtype != torch.int32 or not vid.is_contiguous() or vid.numel() != Q:
+        raise _lib.DrnError("gate_gather_fwd: vid must be a contiguous int32 tensor of %d entries" % Q)
+    host = None
+    if vid_host is not None:
+        if vid_host.is_cuda or vid_host.dtype != torch.int32 or not vid_host.is_contiguous() or vid_host.numel() != Q:
+            raise _lib.DrnError("gate_gather_fwd: vid_host must be a contiguous int32 host tensor of %d entries" % Q)
+        host = ctypes.c_void_p(vid_host.data_ptr())
+    check(lib().drn_gate_gather_fwd(_p(z), ld_z, _p(gate), gate.stride(0), _p(pos), ld_pos, _p(vid), host, V, _p(out), ld_out, Q, L, C, P,
+                                    dtype, _stream()), "drn_gate_gather_fwd")
+
+
 def gate_bwd(dG, ld_dg, act, ld_act, gate, dC, ld_dc, add, ld_add, dgate, nseq, L, C, dtype, dsum=None):
     """dC = (add or 0) + dG * gate; dgate = sum_t dG * act; dsum (nseq, C) fp32 = sum_t dG * gate."""
     check(lib().drn_gate_bwd(_p(dG), ld_dg, _p(act), ld_act, _p(gate), gate.stride(0), _p(add), ld_add, _p(dC), ld_dc, _p(dgate),
@@ -1035,6 +1051,25 @@ def eval_recall(det, scores, counts, gt, ious, max_topk):
     check(lib().drn_eval_recall(_p(det), _p(scores), _p(counts), B, counts.shape[1], R, _p(gt), int(gt.dtype == torch.float64), _p(ious),
                                 ious.numel(), int(max_topk), _p(out), _stream()), "drn_eval_recall")
     return out
+
+
+def select_moments(det, scores, counts, overlap, k):
+    """The first k temporal-NMS survivors of every clip, best first, from drn_postprocess's buffers (drn_select_moments;
+    utils/evaluate_utils.py:91-107,186-212).  -> seg (B, k, 2), score (B, k), level (B, k) int32, index (B, k) int32, n (B,) int32 on
+    the device; no host synchronisation."""
+    _need_gpu(det, scores, counts)
+    B, R = scores.shape
+    assert det.dtype == torch.float32 and scores.dtype == torch.float32 and counts.dtype == torch.int32
+    assert det.is_contiguous() and scores.is_contiguous() and counts.is_contiguous() and det.shape == (B, R, 2)
+    dev, k = det.device, int(k)
+    seg = torch.empty((B, max(k, 0), 2), dtype=torch.float32, device=dev)
+    score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    level = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    index = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().drn_select_moments(_p(det), _p(scores), _p(counts), B, counts.shape[1], R, float(overlap), k, _p(seg), _p(score),
+                                   _p(level), _p(index), _p(n), _stream()), "drn_select_moments")
+    return seg, score, level, index, n
 
 
 # ---------------------------------------------------------------------------------------------

@@ -479,6 +479,39 @@ class Trainer(object):
         topks, accs = PostProcessRunner(results).run_evaluate(iou_topk_dict=iou_topk, temporal_nms=True)
         return total / max(n, 1), topks, accs, results
 
+    @torch.no_grad()
+    def predict(self, loader, top_k=5, nms_overlap=0.45, share_videos=True, id2word=None):
+        """Ground every query of `loader` (collate_data batches; the ground truth in them is not read): ->
+        {video: [{"query": str, "moments": [[start, end, score], ...]}]}, at most top_k moments per query, best first, after the
+        evaluator's temporal NMS at nms_overlap (drn_amd.grounding.Grounder).  share_videos: the queries of a batch that name the
+        same video share its prop_fc product (group_by_video); False runs every query as a clip of its own.  The model is run in
+        eval mode and put back into the mode it was in; no parameter or buffer changes."""
+        from .grounding import Grounder, group_by_video
+        was_training = self.model.training
+        self.model.eval()
+        grounder = Grounder(self.model, top_k=top_k, nms_overlap=nms_overlap)
+        out = {}
+        try:
+            for batch in loader:
+                names, pse, feats, _, tok, qlen = batch[:6]
+                mv = lambda t: t.to(self.device, non_blocking=True)
+                vid = None
+                if share_videos:
+                    unique, vid = group_by_video(names)
+                    if len(unique) < len(names):
+                        first = torch.tensor([names.index(u) for u in unique], dtype=torch.int64)
+                        feats, pse = feats.index_select(0, first.to(feats.device)), pse.index_select(0, first.to(pse.device))
+                    else:
+                        vid = None
+                moments = grounder.ground(mv(tok), mv(qlen), mv(feats), mv(pse), vid).tolist()
+                tokens, lens = tok.cpu(), qlen.cpu()
+                for i, name in enumerate(names):
+                    query = " ".join(id2word[int(t)] if id2word else str(int(t)) for t in tokens[i, :int(lens[i])])
+                    out.setdefault(name, []).append({"query": query, "moments": moments[i]})
+        finally:
+            self.model.train(was_training)
+        return out
+
     def fit(self, train_loader, test_loader, n_epoch=None, eval_freq=1, snapshot_pref=None, dataset="Charades", id2word=None,
             start_epoch=0, rank=0):
         """main.py:142-190: train, validate every eval_freq epochs, keep the best-R@1 and best-R@5 checkpoints.

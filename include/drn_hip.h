@@ -244,6 +244,15 @@ int drn_pairsum_chain3(const void* d0, int ld0, const void* own1, int ldo1, void
  * the schedule that runs the query encoder beside the prop_fc GEMM (otherwise drn_gemm_nt's epilogue applies the gate). */
 int drn_gate_fwd(const void* z, int ld_z, const float* gate, int ldg, void* out, int ld_out, int nseq, int L, int C, int dtype,
                  void* stream);
+/* drn_gate_fwd with a video indirection, for Q queries that share V <= Q videos (each (query, video) pair is one clip of
+ * model/main_model.py:51-59,67 + model/backbone.py:28-32): out[q*L+t][c] = dtype(float(z[vid[q]*L+t][c]) * gate[q][c]) for c < C and
+ * out[q*L+t][C+p] = pos[vid[q]*L+t][p] for p < P (the video's position-embedding columns; pos NULL with P = 0).  vid: device array
+ * of Q indices in [0, V); the kernel clamps an index outside that range and writes zeros for its rows.  vid_host: an optional host
+ * copy of vid -- when given, an index outside [0, V) is DRN_ERR_ARG before anything is launched.  vid = identity: drn_gate_fwd's
+ * bits. */
+int drn_gate_gather_fwd(const void* z, int ld_z, const float* gate, int ldg, const void* pos, int ld_pos, const int32_t* vid,
+                        const int32_t* vid_host /*host, may be NULL*/, int V, void* out, int ld_out, int Q, int L, int C, int P,
+                        int dtype, void* stream);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */
@@ -481,6 +490,15 @@ int drn_postprocess(const DrnLossLevel* levels /*host*/, int nlevels, int B, con
 int drn_eval_recall(const float* det, const float* scores, const int32_t* counts, int B, int nlevels, int rows_per_clip,
                     const void* gt, int gt_is_f64, const double* ious /*device*/, int n_iou, int max_topk, int32_t* first_hit,
                     void* stream);
+/* The moments of each clip, straight from drn_postprocess's outputs: the first K survivors of that same temporal NMS, best first
+ * (utils/evaluate_utils.py:91-107 stable sort by score, :186-212 nms_temporal at `overlap` -- the evaluator's value is iou - 0.05 --
+ * score ties to the later candidate, a candidate struck out unless inter / (len_i + len_j - inter) <= overlap in double, 0/0 struck
+ * out).  seg [B][K][2] = the detections, copied; score [B][K]; level [B][K] = pyramid level of the candidate (running sum of
+ * counts); index [B][K] = its position in the clip's candidate list; n [B] = valid entries.  Entries past n: 0 / -1.  A clip
+ * without candidates yields the fallback moment of model/inference.py:192-197: (0, 1), score 1, level -1, index -1, n = 1.  One
+ * wavefront per clip, no host synchronisation. */
+int drn_select_moments(const float* det, const float* scores, const int32_t* counts, int B, int nlevels, int rows_per_clip,
+                       double overlap, int K, float* seg, float* score, int32_t* level, int32_t* index, int32_t* n, void* stream);
 
 /* ---- query-encoder glue (drn_amd/csrc/qenc.hip; model/language_module.py:17-63), all fp32 ----------------------
  * Word embedding lookup written time-major (L, B, E) and its dense gradient (row padding_idx stays zero). */
