@@ -26,7 +26,7 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
   DRN_CHECK_ARG(dtype == DRN_F32 || dtype == DRN_BF16, "drn_gemm_nt: bad dtype %d", dtype);
   const int ch = dtype == DRN_BF16 ? 8 : 4;
   // Tile choice: 256x256 (8 waves) when every group is large enough to keep the chip busy with such tiles,
-  // else 128x128.  DRN_NT_TILE=128|256 overrides (tests exercise both).
+  // else 128x128.
   long big_tiles = 0;
   bool fast = true;
   for (int g = 0; g < ngroups; ++g) {
@@ -43,8 +43,6 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
   }
   const int big_min = drn_tuning(DRN_TUNE_EXP0) > 0 ? drn_tuning(DRN_TUNE_EXP0) : 200;     // (exp0: experiment override)
   int tile = big_tiles >= big_min ? 256 : 128;
-  if (const char* e = drn_exp_env("DRN_NT_TILE")) tile = atoi(e) == 256 ? 256 : 128;
-  if (drn_exp_env("DRN_NT_GENERIC")) fast = false;
   GemmParams P;
   memset(&P, 0, sizeof(P));
   P.ngroups = ngroups;
@@ -52,9 +50,8 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
   P.ksplit = ksplit | (ksplit > 1 && counters ? (xchg & DRN_XCHG_NONE ? 0 : xchg & DRN_XCHG_CONFIRM ? DRN_XCHG_CONFIRM : DRN_XCHG_READBACK) : 0);
   P.ws = ws;
   P.counters = counters;
-  P.xcd_swizzle = drn_exp_env("DRN_NO_XCD_SWIZZLE") ? 0 : 3;
+  P.xcd_swizzle = 3;                                                                          // bit 0: XCD-contiguous runs, bit 1: 8-row grouped order
   if (drn_tuning(DRN_TUNE_EXP0 + 3) > 0) P.xcd_swizzle = drn_tuning(DRN_TUNE_EXP0 + 3) - 1;   // (exp3: experiment override, value - 1)
-  if (const char* e = drn_exp_env("DRN_NT_ORDER")) P.xcd_swizzle = atoi(e);      // bit 0: XCD-contiguous runs, bit 1: 8-row grouped order
   if (ksplit > 1) tile = planes256 ? 256 : 128;
   // launches on 128x128 tiles whose problems make enough 256x128 tiles: the 4-wave loop on half-width tiles (gemm_nt_w4h.hip)
   bool w4h = false, w4h_conv = false;
@@ -88,23 +85,14 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     p.tile_start = total;
     total += cdiv(s.M, tile_m) * p.tiles_n;
   }
-  // Pipeline depth for the 128x128 tile: 2 stages leave room for two workgroups per CU (best when the grid
-  // oversubscribes the chip); 4 stages (one workgroup per CU) otherwise.  DRN_NT_STAGES overrides for experiments.
-  int stages = (long)total * ksplit > 256 ? 2 : 4;
-  if (const char* e = drn_exp_env("DRN_NT_STAGES")) stages = atoi(e) == 2 ? 2 : 4;
-  if (tile == 256) stages = 2;
-  // 128x128 tiles: 8 waves per workgroup, 2-slot ring (measured 20-30 % faster than 4 waves at one workgroup per CU, 8 % at
-  // two; DRN_NT_WAVES=4 brings the 4-wave variants back for experiments)
-  bool waves8 = tile == 128;
-  if (const char* e = drn_exp_env("DRN_NT_WAVES")) waves8 = tile == 128 && atoi(e) == 8;
-  if (ksplit > 1) waves8 = true;       // the in-launch split-K exchange exists for the 8-wave 128x128 tile only
-  if (waves8 && !drn_exp_env("DRN_NT_STAGES")) stages = 2;
+  // 128x128 tiles: 8 waves per workgroup, 2-slot ring -- room for two workgroups per CU (measured 20-30 % faster than 4 waves at
+  // one workgroup per CU, 8 % at two); the in-launch split-K exchange exists for this tile only.
   // launches that leave CUs idle anyway (<= 256 workgroups: most of the pyramid GEMMs at T = 256, everything at Charades-STA's
   // T = 32) run one workgroup per CU with a 4-slot ring -- three K-tiles of loads in flight against the cold operands instead of
   // one: step 1.51 -> 1.435 ms at T = 32, 2.448 -> 2.434 at T = 256 (512 as the bound: 2.465)
   int max_ksteps = 0;
   for (int g = 0; g < ngroups; ++g) max_ksteps = max(max_ksteps, cdiv(cdiv(d[g].taps * d[g].Cin, 8 * ch), ksplit));
-  const bool deep8 = waves8 && stages == 2 &&
+  const bool deep8 = tile == 128 &&
                      ((drn_tuning(DRN_TUNE_NT_DEEP) > 0 && (long)total * ksplit <= drn_tuning(DRN_TUNE_NT_DEEP)) ||
                       (drn_tuning(DRN_TUNE_NT_DEEP2) > 0 && (long)total * ksplit <= drn_tuning(DRN_TUNE_NT_DEEP2) &&
                        max_ksteps <= drn_tuning(DRN_TUNE_NT_DEEP_KS)));
@@ -116,9 +104,6 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     NT_ATTR(float, 2, 2, 4, 8, 4); NT_ATTR(bf16_t, 2, 2, 4, 8, 4);
     NT_ATTR(float, 2, 2, 4, 4, 2); NT_ATTR(bf16_t, 2, 2, 4, 4, 2);
     NT_ATTR(float, 4, 2, 4, 4, 2); NT_ATTR(bf16_t, 4, 2, 4, 4, 2);
-#ifdef DRN_EXPERIMENTS
-    NT_ATTR(float, 2, 2, 2, 4, 4); NT_ATTR(bf16_t, 2, 2, 2, 4, 4); NT_ATTR(float, 4, 2, 2, 4, 4); NT_ATTR(bf16_t, 4, 2, 2, 4, 4);
-#endif
 #undef NT_ATTR
     attr_set = true;
   }
@@ -161,17 +146,7 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     if (dtype == DRN_BF16) NT_LAUNCH(bf16_t, 2, 512, 2 * 65536, 2, 4, 8, 4); else NT_LAUNCH(float, 2, 512, 2 * 65536, 2, 4, 8, 4);
   } else if (deep8) {     // few workgroups, cold operands: three tiles of loads in flight instead of one
     if (dtype == DRN_BF16) NT_LAUNCH(bf16_t, 4, 512, 4 * 32768, 2, 4, 4, 2); else NT_LAUNCH(float, 4, 512, 4 * 32768, 2, 4, 4, 2);
-  }
-#ifdef DRN_EXPERIMENTS
-  else if (waves8 && stages == 4) {
-    if (dtype == DRN_BF16) NT_LAUNCH(bf16_t, 4, 512, 4 * 32768, 2, 4, 4, 2); else NT_LAUNCH(float, 4, 512, 4 * 32768, 2, 4, 4, 2);
-  } else if (!waves8 && dtype == DRN_BF16) {
-    if (stages == 2) NT_LAUNCH(bf16_t, 2, 256, 2 * 32768, 2, 2, 4, 4); else NT_LAUNCH(bf16_t, 4, 256, 4 * 32768, 2, 2, 4, 4);
-  } else if (!waves8) {
-    if (stages == 2) NT_LAUNCH(float, 2, 256, 2 * 32768, 2, 2, 4, 4); else NT_LAUNCH(float, 4, 256, 4 * 32768, 2, 2, 4, 4);
-  }
-#endif
-  else {      // 128x128 tile, 8 waves, 2-slot ring
+  } else {      // 128x128 tile, 8 waves, 2-slot ring
     if (dtype == DRN_BF16) NT_LAUNCH(bf16_t, 2, 512, 2 * 32768, 2, 4, 4, 2); else NT_LAUNCH(float, 2, 512, 2 * 32768, 2, 4, 4, 2);
   }
 #undef NT_LAUNCH

@@ -70,16 +70,14 @@ extern "C" int drn_conv_bn_train(const DrnGemmDesc* d, const DrnBnTrainDesc* bn,
   }
   // the same tile choice as drn_gemm_nt (the per-slab statistics are summed in tile order: equal tiles = equal bits)
   const int big_min = drn_tuning(DRN_TUNE_EXP0) > 0 ? drn_tuning(DRN_TUNE_EXP0) : 200;
-  int tile = big_tiles >= big_min ? 256 : 128;
-  if (const char* e = drn_exp_env("DRN_NT_TILE")) tile = atoi(e) == 256 ? 256 : 128;
+  const int tile = big_tiles >= big_min ? 256 : 128;
   BN_UNSUPPORTED(N % tile != 0, "%s: N=%d is not a multiple of the %d-wide tile", who, N, tile);
   GemmParamsBn P;
   memset(&P, 0, sizeof(P));
   P.ngroups = ngroups;
   P.ksplit = 1;
-  P.xcd_swizzle = drn_exp_env("DRN_NO_XCD_SWIZZLE") ? 0 : 3;
+  P.xcd_swizzle = 3;
   if (drn_tuning(DRN_TUNE_EXP0 + 3) > 0) P.xcd_swizzle = drn_tuning(DRN_TUNE_EXP0 + 3) - 1;
-  if (const char* e = drn_exp_env("DRN_NT_ORDER")) P.xcd_swizzle = atoi(e);
   int total = 0;
   bool chain = false;
   unsigned long long* tws = (unsigned long long*)tagged_ws;
@@ -132,7 +130,7 @@ extern "C" int drn_conv_bn_train(const DrnGemmDesc* d, const DrnBnTrainDesc* bn,
   P.bn_relu = relu;
   P.bn_chain = chain ? 1 : 0;
   P.nblocks = total;
-  const bool deep8 = tile == 128 && drn_tuning(DRN_TUNE_NT_DEEP) > 0 && total <= drn_tuning(DRN_TUNE_NT_DEEP) && !drn_exp_env("DRN_NT_STAGES");
+  const bool deep8 = tile == 128 && drn_tuning(DRN_TUNE_NT_DEEP) > 0 && total <= drn_tuning(DRN_TUNE_NT_DEEP);
 
   static bool attr_set = false;
   if (!attr_set) {

@@ -16,7 +16,6 @@
 //   f32 : 4 x v_mfma_f32_16x16x4_f32 per 16-B fragment (exact fp32, parity mode);
 //         the k-permutation this implies is applied identically to A and B.
 #pragma once
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "bn_merge.h"
@@ -86,7 +85,6 @@ struct GemmParamsBn : GemmParams {
   int bn_chain;          // 1: some group has up_group >= 0 (raw outputs are exchanged between workgroups)
 };
 
-constexpr bool getenv_free_scalar_w = false;   // flip to try the scalar wave index on the 8-wave tile as well
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -1062,7 +1060,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BNF && MI * NI == 8 && STAGES == 2) 
   // wave index as a scalar for the 4-wave tiles (LDS-DMA bases / M0 stay in SGPRs: +5-10 % on the pyramid-level GEMMs);
   // the 8-wave 256x256 tile measured 3 % slower with it, so it keeps the per-lane value
   const int tid = threadIdx.x, l = tid & 63;
-  const int w = (WM * WN == 8 && !getenv_free_scalar_w) ? (tid >> 6) : __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int w = WM * WN == 8 ? (tid >> 6) : __builtin_amdgcn_readfirstlane(tid >> 6);
   NT_PHASE(0);
 
   NtHeader P;

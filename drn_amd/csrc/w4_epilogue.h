@@ -71,7 +71,7 @@ struct W4hOut {
 // 4300; ONE patch for the whole tile and one wait 5100 (all 224 workgroups then store at once: ~225 clocks per 1 KB instruction is
 // the chip's write rate, not the wave's).  GATED / DUAL: prop_fc's forward writes the pre-gate value AND the gated one; as two passes
 // over the accumulators (what the old epilogue did too) the step was 10 us slower than with the old layout, as one pass with two
-// patches it is the faster one (scripts/experiments/ab_lib.sh).
+// patches it is the faster one (in-box A/B of two builds of the library).
 template <int NI, int NIT, int NOFF, int CH, bool GATED, bool DUAL>
 __device__ __forceinline__ void w4h_store_chunk(const W4hOut& O, char* wbuf, const int mrow0, const int ncol0, const float (&bias4)[NI][4],
                                                 float (&g)[NI][4]) {

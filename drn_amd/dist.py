@@ -39,9 +39,6 @@ def init_from_env(backend=None):
     return rank, local, world
 
 
-WGRAD_DEFER = os.environ.get("DRN_WGRAD_DEFER", "1") != "0"      # (experiment switch: 0 = every weight gradient reduces in its own launch)
-
-
 def _initialized(group=None):
     return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
 
@@ -220,7 +217,7 @@ class GradReducer(object):
         its dW lives): nothing reads those slices before collect().  Only with steal=True -- otherwise AccumulateGrad adds a
         still un-reduced dW into the bucket the moment backward hands it over -- and not in the eager multi-GPU mode, whose hooks
         hand buckets to RCCL as backward fills them.  zero() drops whatever an earlier backward that raised left recorded."""
-        if not self.params or not self.params[0].is_cuda or (self.world > 1 and self.overlap) or not WGRAD_DEFER or not self.steal:
+        if not self.params or not self.params[0].is_cuda or (self.world > 1 and self.overlap) or not self.steal:
             return
         from . import ops
         want = bool(getattr(self, "ext_sumsq", False)) and self.world == 1

@@ -8,7 +8,6 @@ bfloat16 = storage with fp32 accumulation).  Parameters stay fp32; their GEMM-la
 `stacked_t`) live in the `WeightCopies` store of the model that owns the parameters (`mainModel.weight_copies`; a shared default
 for stand-alone layers) and are refreshed by the optimizer kernels / in one launch after the optimizer step (`repack_all`).
 """
-import os
 import weakref
 
 import torch
@@ -511,10 +510,6 @@ def take_sumsq_notes():
 
 
 NT_WGRAD = True      # prop_fc weight gradient through the NT kernel on transposed operands (bf16): 250 vs 410 us for the TN kernel
-# 1 = warm the prop_fc weight copy right before its GEMM when the general kernel runs it (round 2: 2.562 vs 2.577 ms without).  Off since
-# round 5: with the Adam moments and fp32 masters accessed non-temporally the bf16 copy Adam writes is still in the Infinity Cache when the
-# GEMM starts -- T = 32, three pairs in one box: 1.208 -> 1.201 ms linear, 1.149 -> 1.148 two-branch without the touch launch
-TOUCH_W = os.environ.get("DRN_TOUCH_W", "0") != "0"
 
 # BatchNorm `num_batches_tracked` increments are collected during a forward pass and applied by ONE multi-tensor add
 # (flush_bn_counters) instead of one tiny launch per BN call.
@@ -759,7 +754,7 @@ class _ConvBlockFn(torch.autograd.Function):
                 dG = _grad_nlc(gouts[nl], None, dt)
                 if dG is not None:
                     dgate = torch.empty((B, Cout), dtype=torch.float32, device=dev)
-                    if GATE_BN_FUSE and not ctx.has_up and nl == 1:
+                    if not ctx.has_up and nl == 1:
                         # the gate backward rides in the BatchNorm backward launch (DrnBnBwdDesc::gb_*; ops.bn_bwd_multi runs it as a
                         # launch of its own where that kernel cannot take it)
                         gb = dict(dg=dG, ld_dg=Cout, gate=gate, ldg=gate.stride(0), dgate=dgate, L=Lo, act=outs[l], ld_act=Cout)
@@ -1115,11 +1110,8 @@ def input_prep(feats, props_start_end, prop_fc, dtype, want_wgrad=True, split_ga
     pr.xc = xc
     Wfc = prop_fc.weight
     pr.wfc = Wfc.detach() if code == ops.F32 else packed(Wfc, (0, 2, 1), code)
-    if TOUCH_W and code == ops.BF16 and _fc_kernel_kind(B, T, D, Wfc.shape[0], xc, pr.wfc, code, split_gate) != ops.NT_KIND_W4:
-        ops.touch(pr.wfc)                                  # 2.9 ms old and evicted: ~8 us here saves the GEMM ~29 us
-        # (not when the product runs on gemm_nt_w4_kernel, whose ring keeps 1.5 K-steps of loads in flight: 2.042 ms per step
-        # without the touch against 2.051 with it, three rounds in one process)
-        # (doing the same for the other forward weight copies -- 20 MB in a handful of launches -- measured 10 us SLOWER)
+    # (no ops.touch of the weight copy in front of the GEMM: since the Adam moments and fp32 masters are accessed non-temporally the
+    # bf16 copy Adam writes is still in the Infinity Cache when the GEMM starts -- T = 32: 1.208 -> 1.201 ms without the touch launch)
     # main_model.py:51-55: [start, end, end-start] in fp64, then float(); only level 0 is consumed (backbone.py:31)
     if props_start_end.shape[-1] == 3:                     # already [start, end, end-start]
         pf = props_start_end.float()
@@ -1131,7 +1123,7 @@ def input_prep(feats, props_start_end, prop_fc, dtype, want_wgrad=True, split_ga
     pr.pf = pf.reshape(B * T, 3).contiguous()
     pr.Z = None
     pr.G0 = None
-    if position_transform is not None and POS_EARLY:
+    if position_transform is not None:
         # conv0's input buffer, its position-embedding columns filled HERE: nothing of this depends on the query, so in the
         # two-branch step the launch sits beside the query encoder instead of between the prop_fc GEMM and conv0 (-7 us on that path)
         P = position_transform.weight.shape[0]
@@ -1152,11 +1144,6 @@ def _fc_kernel_kind(B, T, D, N, xc, wfc, code, split_gate):
     # (the output / pre-gate copy are allocated later: any 16-byte aligned address with the real row strides stands in)
     d = ops.gemm_desc(xc, wfc, xc, B * T, N, D, Lout=T, ldc=D + P, C2=None if split_gate else xc, ldc2=D)
     return ops.gemm_nt_plan([d], code)
-
-
-POS_EARLY = os.environ.get("DRN_POS_EARLY", "1") != "0"              # (experiment switch: 0 = the position embedding after the prop_fc GEMM)
-GATE_BN_FUSE = os.environ.get("DRN_GATE_BN_FUSE", "1") != "0"        # (experiment switch: 0 = drn_gate_bwd in front of the BatchNorm backward)
-GATE_BWD_FUSE = os.environ.get("DRN_GATE_BWD_FUSE", "1") != "0"      # (experiment switch: 0 = drn_gate_bwd_t as a launch of its own)
 
 
 class EmbedTail(object):
@@ -1227,7 +1214,7 @@ class _InputStageFn(torch.autograd.Function):
         ctx.param_refs = (Wfc, bfc, Wpos, bpos)
         ctx.tail = tail
         if tail is not None:
-            fuse = GATE_BWD_FUSE and dtype == torch.bfloat16 and xcT is not None and xcT.numel() and T in (32, 64, 128, 256) and D % 256 == 0
+            fuse = dtype == torch.bfloat16 and xcT is not None and xcT.numel() and T in (32, 64, 128, 256) and D % 256 == 0
             tail.gate_ctx = (Z, gate0, B, T, D) if fuse else None
             tail.gate_out = None
         ctx.save_for_backward(xc, pf, gate0, Z, xcT if xcT is not None else xc.new_empty(0))

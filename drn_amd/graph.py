@@ -375,11 +375,6 @@ class ForkedStep(DualStreamStep):
             raise ValueError("ForkedStep(rotate=True) needs GradReducer(groups=[model.query_parameters(), the other parameters])")
         self.rotate = bool(rotate)
         self._primed = False
-        import os
-        if os.environ.get("DRN_FORK_ROTATE") is not None:              # experiment switches (scripts/experiments/ab_r05_c.sh)
-            self.rotate = can and os.environ["DRN_FORK_ROTATE"] == "1"
-        self._env_wf = os.environ.get("DRN_FORK_WGRADS_FIRST")
-        self._env_mf = os.environ.get("DRN_FORK_MAIN_FIRST")
         # (side stream from the DEFAULT-priority pool: high-priority streams bring a second set of hardware queues into being, and
         # with them around everything else in the process that uses two streams ran slower afterwards -- the trainer's H2D
         # look-ahead 12.9 -> 9.0 k clips/s, evaluation 22 -> 15 k, measured in bench.py after a capture on priority -1 streams)
@@ -390,11 +385,7 @@ class ForkedStep(DualStreamStep):
         # 174 us: 2.028 / 2.019 -> 2.012 / 2.013 ms per step (64: 2.055, 96: 2.012-2.024, 192: 2.010-2.027, 256: 2.016-2.020)
         # (re-swept at the end of round 5, non-temporal cast loads and the position embedding beside it: 64: 1.96, 96: 1.92, 128: 1.912,
         # 192: 1.905, 256: 1.907, unthrottled 1.927 ms -- two rounds each in one box)
-        self.prep_throttle = int(os.environ.get("DRN_FORK_PREP_THROTTLE", "192"))
-        if self._env_wf is not None:
-            self.wgrads_first = self._env_wf == "1"
-        if self._env_mf is not None:
-            self.main_first = self._env_mf == "1"
+        self.prep_throttle = 192
         if self._streams[0] is not None:
             self.main = self._streams[0]
         if self._streams[1] is not None:

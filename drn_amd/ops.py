@@ -5,7 +5,6 @@ libdrn_hip.so call on torch's current HIP stream.  Missing library or a non-zero
 return code raises (no fallback).
 """
 import ctypes
-import os
 
 import torch
 
@@ -63,13 +62,12 @@ kernel_timer = None
 # fill the chip (<= 160 tiles of 128x128 on 256 CUs): conv0 forward (128 tiles x 204 K-steps) 157 -> 69 us 4-way.  With warm
 # operands the 12-48-step pyramid GEMMs gain nothing from it (the exchange costs 4-8 us: scripts/bench_splitk.py), but inside
 # the step, where their operands are cold, 2-4 splits of >= 12 K-steps each put twice the loads in flight: -25 us per step.
-SPLITK_MIN_KSTEPS = int(os.environ.get("DRN_SPLITK_MIN_KSTEPS", "24"))
-SPLITK_STEPS_PER_SPLIT = int(os.environ.get("DRN_SPLITK_STEPS", "12"))     # a bf16 split owns at least that many K-steps
+SPLITK_MIN_KSTEPS = 24
+SPLITK_STEPS_PER_SPLIT = 12     # a bf16 split owns at least that many K-steps
 # Workgroups a split launch aims for.  256 = one 8-wave workgroup per CU on the 4-slot ring (three K-tiles of loads in flight
 # against cold operands) rather than 512 = two per CU on 2-slot rings: conv0's forward (128 tiles x 204 K-steps) 4 -> 2 splits, the
-# step 2.222 -> 2.209 ms at T = 256 in one process (384: 2.237, 192 = conv0 unsplit: 2.27), T = 32 unchanged
-# (scripts/experiments/ab_env.sh DRN_KSPLIT_WGS 512 384 256 192).
-KSPLIT_WGS = int(os.environ.get("DRN_KSPLIT_WGS", "256"))
+# step 2.222 -> 2.209 ms at T = 256 in one process (384: 2.237, 192 = conv0 unsplit: 2.27), T = 32 unchanged.
+KSPLIT_WGS = 256
 
 
 def _timed(tag, flops, launch):
@@ -97,8 +95,9 @@ def _ksplit(descs, dtype):
 
 # One long-K bf16 k = 3 convolution with 16-64 tiles of 256x256 (conv0's forward: 32 tiles x 204 K-steps): full-width tiles on the
 # 4-wave kernel, the K loop split so that ~256 workgroups exist, fp32 partial planes + a second launch that adds them
-# (drn_gemm_nt_splitk256) -- half the L2 -> LDS bytes of the 128x128 in-launch split below.  DRN_SPLITK256=0 switches it off.
-SPLITK256 = os.environ.get("DRN_SPLITK256", "0") == "1"
+# (drn_gemm_nt_splitk256) -- half the L2 -> LDS bytes of the 128x128 in-launch split below.  Built and tested, off by default (the in-launch
+# W4H split below takes conv0's forward first); SPLITK256 = True turns it on.
+SPLITK256 = False
 
 
 def _ksplit256(descs, dtype):
@@ -144,8 +143,8 @@ def gemm_nt_plan(descs, dtype):
 # -- scripts/experiments/conv0_alias_bench.py -- the same launch took 56 us).  Split k = 3 launches over >= 2048 input channels now
 # walk K as (channel block, tap) (W4HT_LOOP_ASM, drn_tune "w4h_tapil"): the three taps of a channel block read the same lines one
 # K-step after the other.  conv0's forward 85.8 -> 70.0 us alone and 81.9 -> 75.4 us inside the step (one box each, both paths
-# traced); the step itself moves inside its noise (2.007 -> 2.002 ms).  DRN_KSPLIT_W4H=0 switches it off.
-KSPLIT_W4H = os.environ.get("DRN_KSPLIT_W4H", "1") == "1"
+# traced); the step itself moves inside its noise (2.007 -> 2.002 ms).  KSPLIT_W4H = False switches it off.
+KSPLIT_W4H = True
 
 
 def _ksplit_w4h(descs, dtype):
@@ -174,18 +173,14 @@ def _ksplit_w4h(descs, dtype):
 # own stream beside the replay, RCCL's kernels beside backward, a second graph branch beside the first), so every launch confirms by
 # READ-BACK -- an sc1 load of every stored request, +12 us per step at T = 256, the variant that closed the window on the proven
 # kernel (0 events in 120 k replays against 7) -- which is what the library does when the call's `ksplit` carries no flag.  The mode
-# travels WITH THE CALL (DRN_KSPLIT_CONFIRM_* bits, include/drn_hip.h): no process-wide switch.  DRN_XCHG_CONFIRM=0 / 1 select
-# "nothing" / "returning atomics" for stress tests and A/Bs (scripts/experiments), 2 = the default.
+# travels WITH THE CALL (DRN_KSPLIT_CONFIRM_* bits, include/drn_hip.h): no process-wide switch.  XCHG_CONFIRM = "0" / "1" select
+# "nothing" / "returning atomics" for stress tests and A/Bs (scripts/experiments), "2" = the default.
 KSPLIT_CONFIRM_ATOMIC, KSPLIT_CONFIRM_NONE = 0x20000, 0x80000
-XCHG_CONFIRM = os.environ.get("DRN_XCHG_CONFIRM", "2")
+XCHG_CONFIRM = "2"
 
 
 def _ksplit_arg(ks):
     return ks | (KSPLIT_CONFIRM_NONE if XCHG_CONFIRM == "0" else KSPLIT_CONFIRM_ATOMIC if XCHG_CONFIRM == "1" else 0)
-
-
-def xchg_need(delta):
-    """Kept for callers of rounds 4-5 (declare / withdraw concurrency): the exchanges now confirm unconditionally, nothing to switch."""
 
 
 def gemm_nt(descs, dtype):
@@ -705,9 +700,9 @@ def _bn_train_descs(levels):
 # (tests/test_conv_bn_gpu.py) -- and OFF by default, because it measures slower inside the step (DESIGN.md section 8, round 4:
 # FPN + heads forward 274 vs 257 us).  After a workgroup's K loop the hand-off is publish -> wait -> merge, three memory-side round
 # trips plus 45 MB of L2-bypassing statistics reads per launch (11-13 us), against ~3 us of epilogue + a 6-15 us BatchNorm launch
-# that reads the same statistics out of L2.  DRN_BN_FUSE=1 turns it on (never together with DRN_FORCE_DEVICE, the test mode that
+# that reads the same statistics out of L2.  BN_FUSE = True turns it on (never together with DRN_FORCE_DEVICE, the test mode that
 # puts several ranks on ONE GPU: its in-kernel wait needs the whole grid resident on a device this process owns).
-BN_FUSE = os.environ.get("DRN_BN_FUSE", "0") == "1" and os.environ.get("DRN_FORCE_DEVICE") is None
+BN_FUSE = False
 DRN_ERR_UNSUPPORTED = -3
 
 
@@ -762,8 +757,7 @@ def conv_bn_train_timeouts(reset=True):
     return int(lib().drn_conv_bn_train_timeouts(int(reset)))
 
 
-BN_BWD_ONE = os.environ.get("DRN_BN_BWD_ONE", "1") != "0"      # (experiment switch: 0 = reduce + apply launches, drn_bn_bwd_multi)
-_bn1_maxwg = os.environ.get("DRN_BN1_MAXWG")                  # (experiment switch: workgroup budget of the one-launch kernel)
+BN_BWD_ONE = True      # (False = reduce + apply launches, drn_bn_bwd_multi)
 
 
 def bn_bwd_multi(levels, C, dtype, relu=True):
@@ -794,10 +788,6 @@ def bn_bwd_multi(levels, C, dtype, relu=True):
 
     has_gb = any(v.get("gb") is not None for v in levels)
     arr = fill(has_gb)
-    global _bn1_maxwg
-    if _bn1_maxwg:
-        lib().drn_tune(b"bn1_maxwg", int(_bn1_maxwg))
-        _bn1_maxwg = None
     if BN_BWD_ONE:
         # one launch when the grid fits the chip at once (drn_bn_bwd_one): the tagged-pair workspace is zero at birth and keeps the
         # launch generation afterwards -- one buffer per size AND stream (launches on one stream are ordered; two streams running
@@ -989,11 +979,11 @@ def lstm_step_fwd(xproj, whf, whr, biases, hseq, cseq, gates, out, hprev_t, lens
           "drn_lstm_step_fwd")
 
 
-# 1 = the fp16-state BiLSTM forward as ONE launch (drn_lstm_seq_fwd: hidden states handed over between resident workgroups as
+# True = the fp16-state BiLSTM forward as ONE launch (drn_lstm_seq_fwd: hidden states handed over between resident workgroups as
 # fp16 words whose spare exponent bit carries the launch parity, one wave polling one word per producer; bit-identical).  Third
 # measurement of the idea, third null: 54.1 us for 8 steps against 8 x 7.3 = 58.4, the step 1.981 vs 1.982 ms -- a hand-off through
 # memory costs ~5 us whatever replaces the kernel boundary (every thread polling its own words: 62.5 us).  Kept, tested, off.
-LSTM_SEQ = os.environ.get("DRN_LSTM_SEQ", "0") != "0"
+LSTM_SEQ = False
 
 
 def lstm_seq_fwd(xproj, whf, whr, biases, hseq, cseq, gates, out, hprev_t, lens, B, L, H, qvec=None):

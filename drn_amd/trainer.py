@@ -102,7 +102,7 @@ class _Preloaded(object):
 
 class Trainer(object):
     def __init__(self, model, stage, lr=1e-3, clip_gradient=0.5, world_size=1, fused=True, graph=False, lq_bucket=4,
-                 graph_warmup=2, max_graphs=32, prefetch=None, forked=None):
+                 graph_warmup=2, max_graphs=32, prefetch=True, forked=False):
         """graph=True (fused stages only): `train_step` replays the step as a hipGraph -- the launch path bench.py measures --
         one capture per input geometry (clips, proposals, feature dim, query length rounded up to a multiple of `lq_bucket`:
         the query kernels take the true lengths from the device, so padding changes no value) -- two, used in turn, when
@@ -128,7 +128,7 @@ class Trainer(object):
         self._eager_geos = set()                           # geometries that fell back to eager launches (logged once each)
         self._turn = {}                                    # geometry -> uses so far (its two slots alternate)
         self._copy_stream = None
-        self.prefetch = (os.environ.get("DRN_TRAINER_PREFETCH", "1") != "0") if prefetch is None else bool(prefetch)
+        self.prefetch = bool(prefetch)
         # every step of a graph-mode trainer -- eager ones included -- runs on ONE side stream: autograd's AccumulateGrad nodes
         # remember the stream they were created on, and warm-up, capture and replay must agree on it (drn_amd/graph.py)
         self.stream = torch.cuda.Stream(device=self.device) if self.graph else None
@@ -136,8 +136,6 @@ class Trainer(object):
         # beside input preparation / weight gradients; the same launches and bits as the linear capture).  Worth 3.5 % in bench.py's
         # back-to-back replays, NOTHING inside this loop (2.360 vs 2.369 ms/step at T = 256, scripts/experiments/trainer_forked_probe.py:
         # the per-step input copies and stream hand-offs around the replay sit where the overlap was) -- so it is opt-in
-        if forked is None:
-            forked = os.environ.get("DRN_TRAINER_FORKED", "0") == "1"
         self.forked = bool(forked) and self.graph and world_size == 1 and hasattr(model, "forward_trunk")
         self._side = torch.cuda.Stream(device=self.device) if self.forked else None
         # graph mode: the epoch's loss sum (train_epoch's return value) is accumulated ON THE DEVICE by one add that is part of

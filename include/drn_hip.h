@@ -32,8 +32,7 @@ int drn_abi_version(void);
  * gemm_nt_w4_kernel takes by default; results are bit-identical either way), "nt_w4c" / "nt_w4h" (the same for the k = 3 convolutions on
  * 256x256 tiles and the 256x128-tile kernel), "nt_deep*", "bn1_maxwg", "w4h_tapil", "exp0".."exp4" (launch heuristics, 0 = shipped).
  * Per-launch behaviour (the split-K exchange's confirmation, deferred weight-gradient reduces) is NOT here: it travels in the call's own
- * arguments (DRN_KSPLIT_CONFIRM_*, DrnWgradPending).  The library never reads the environment (the experiment build
- * `make EXPERIMENTS=1` does). */
+ * arguments (DRN_KSPLIT_CONFIRM_*, DrnWgradPending).  The library never reads the environment. */
 int drn_tune(const char* key, int value);
 const char* drn_last_error(void); /* thread-local, valid until the next failing call on this thread */
 
@@ -135,7 +134,7 @@ typedef struct DrnWgradDesc {
 } DrnWgradDesc;
 /* bf16, taps == 3, stride == 1, pad == 1, Lsrc == Lout and >= 4096 rows run the fused-tap kernel (one staged X block
  * feeds all three taps); everything else the per-tap kernel.  Same results to fp32 rounding (the split points differ).
- * Environment (experiments): DRN_TN_FUSED=0 disables, DRN_TN3_MINROWS, DRN_TN3_TARGET, DRN_TN3_STAGES=3|4. */
+ * drn_tune("tn_fused", 0) disables the fused-tap kernel, "tn3_minrows" sets its row threshold (tests). */
 int64_t drn_wgrad_ws_elems(int M_total, int N, int Cin, int taps);
 
 /* Deferred reduce passes.  A weight-gradient launch that splits its rows ends with a reduce launch of its own -- unless the caller hands

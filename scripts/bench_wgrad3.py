@@ -4,6 +4,7 @@ import sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from drn_amd import ops
+from drn_amd._lib import check, lib
 
 dev = "cuda:0"
 dt = torch.bfloat16
@@ -34,7 +35,7 @@ def case(name, levels, N, Cin, layout=1, multi=False, bench=True):
         flops += 2.0 * B * L * N * 3 * Cin
     res = {}
     for fused in ("0", "1"):
-        os.environ["DRN_TN_FUSED"] = fused
+        check(lib().drn_tune(b"tn_fused", int(fused)), "drn_tune")
         if multi:
             dWs = [torch.zeros(N, Cin, 3, device=dev) for _ in levels]
             run = lambda: ops.gemm_wgrad_multi(descs, dWs, N, Cin, taps=3, stride=1, pad=1, w_layout=layout, dtype=code)
@@ -54,7 +55,7 @@ def case(name, levels, N, Cin, layout=1, multi=False, bench=True):
 
 
 B = 32
-os.environ["DRN_TN3_MINROWS"] = "0"
+check(lib().drn_tune(b"tn3_minrows", 0), "drn_tune")
 case("tiny 2x20 N=24 Cin=40", [(2, 20)], 24, 40, bench=False)
 case("ragged 3x33 N=136 Cin=200", [(3, 33)], 136, 200, layout=0, bench=False)
 case("grouped 4x(64,32,16)", [(4, 64), (4, 32), (4, 16)], 128, 128, bench=False)

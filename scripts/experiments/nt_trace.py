@@ -23,19 +23,17 @@ A = torch.randn(M, Cin, device=dev).to(dt)
 C = torch.empty(M, N, device=dev, dtype=dt)
 d = ops.gemm_desc(A, W, C, M, N, Cin, taps=taps, stride=1, pad=(taps - 1) // 2, Lout=L, Lsrc=L)
 arr = (type(d) * 1)(d)
-for stages in (("2",) if big else ("2", "4")):
-    os.environ["DRN_NT_STAGES"] = stages
-    trace = torch.zeros(8 * 64 * 8, dtype=torch.int64, device=dev)
-    for _ in range(3):
-        check(lib().drn_gemm_nt_splitk(arr, 1, ctypes.c_void_p(trace.data_ptr()), ops.BF16, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "trace")
-    torch.cuda.synchronize()
-    t = trace.view(8, 64, 8).cpu()
-    nk = min(64, taps * Cin // 64)
-    print("stages=%s: %d K-steps; wave 0 deltas (ticks) per K-step: wait | barrier | frags0 | mfma0 | frags1 | mfma1 | total" % (stages, nk))
-    for w in range(2):
-        for k in range(4, min(nk, 14)):
-            r = t[w, k]
-            nxt = t[w, k + 1, 0] if k + 1 < nk else r[6]
-            print("  w%d k%2d  %5d | %5d | %5d | %5d | %5d | %5d | %6d" % (w, k, r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3], r[5] - r[4], r[6] - r[5], nxt - r[0]))
-    tot = (t[0, nk - 1, 6] - t[0, 0, 0]).item()
-    print("  loop total %d ticks = %.1f per K-step" % (tot, tot / nk))
+trace = torch.zeros(8 * 64 * 8, dtype=torch.int64, device=dev)
+for _ in range(3):
+    check(lib().drn_gemm_nt_splitk(arr, 1, ctypes.c_void_p(trace.data_ptr()), ops.BF16, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "trace")
+torch.cuda.synchronize()
+t = trace.view(8, 64, 8).cpu()
+nk = min(64, taps * Cin // 64)
+print("%d K-steps; wave 0 deltas (ticks) per K-step: wait | barrier | frags0 | mfma0 | frags1 | mfma1 | total" % nk)
+for w in range(2):
+    for k in range(4, min(nk, 14)):
+        r = t[w, k]
+        nxt = t[w, k + 1, 0] if k + 1 < nk else r[6]
+        print("  w%d k%2d  %5d | %5d | %5d | %5d | %5d | %5d | %6d" % (w, k, r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3], r[5] - r[4], r[6] - r[5], nxt - r[0]))
+tot = (t[0, nk - 1, 6] - t[0, 0, 0]).item()
+print("  loop total %d ticks = %.1f per K-step" % (tot, tot / nk))

@@ -127,7 +127,7 @@ def test_norm_pass_block_classes_are_host_logic():
 
 def test_split_exchange_confirmation_travels_with_the_call(monkeypatch):
     """The K-split exchanges' confirmation mode is an argument of the launch (DRN_KSPLIT_CONFIRM_* bits of `ksplit`, include/drn_hip.h),
-    not process state: no flag = read-back (what ships, everywhere); DRN_XCHG_CONFIRM=1 / 0 select atomics / nothing for stress
+    not process state: no flag = read-back (what ships, everywhere); ops.XCHG_CONFIRM = "1" / "0" select atomics / nothing for stress
     tests.  The product path never calls drn_tune."""
     import re
     from drn_amd import ops
@@ -139,8 +139,8 @@ def test_split_exchange_confirmation_travels_with_the_call(monkeypatch):
     assert ops._ksplit_arg(4) == 4 | 0x80000
     hdr = open(os.path.join(ROOT, "include", "drn_hip.h")).read()
     assert re.search(r"#define DRN_KSPLIT_CONFIRM_ATOMIC\s+0x20000", hdr) and re.search(r"#define DRN_KSPLIT_CONFIRM_NONE\s+0x80000", hdr)
-    # drn_tune is a test / experiment switch: only the BatchNorm-backward workgroup budget override (DRN_BN1_MAXWG, an experiment
-    # environment variable) may reach it from the package
+    # drn_tune is a test / experiment switch: nothing in the package calls it (the rule still tolerates a "bn1_maxwg" override, the
+    # one call the package once had)
     for dirpath, _, files in os.walk(os.path.join(ROOT, "drn_amd")):
         for f in files:
             if f.endswith(".py"):

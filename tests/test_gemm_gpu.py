@@ -957,7 +957,7 @@ def test_w4h_kernel_splitk_in_launch(monkeypatch, shape):
 
 @pytest.mark.parametrize("kind", ["general", "w4h"])
 def test_split_exchange_confirmation_changes_no_bits(monkeypatch, kind):
-    """drn_tune "xchg_confirm" (ops.xchg_need: set while another queue's kernels may run beside the launch): every partial-tile store
+    """ops.XCHG_CONFIRM (the DRN_KSPLIT_CONFIRM_* bits of the call; needed while another queue's kernels may run beside the launch): every partial-tile store
     of the in-launch split-K exchange is followed by a returning OR-with-zero on its address (1) or an sc1 load of it (2) before the
     ticket.  Values untouched:
     the launch with and without it gives the same bits, counters re-armed, for the general 128 x 128 kernel and for gemm_nt_w4h_kernel
