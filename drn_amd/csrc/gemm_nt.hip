@@ -4,9 +4,9 @@
 bool drn_nt_w4_eligible(const DrnGemmDesc* d, int ngroups, int dtype);            // gemm_nt_w4.hip
 int drn_nt_w4_launch(const GemmParams& P, int total, hipStream_t stream);
 bool drn_nt_w4c_eligible(const DrnGemmDesc* d, int ngroups, int dtype);
-int drn_nt_w4c_launch(const GemmParams& P, int total, hipStream_t stream, int ksplit);
+int drn_nt_w4c_launch(const GemmParams& P, int total, hipStream_t stream, int ksplit, bool eval = false);
 bool drn_nt_w4h_eligible(const DrnGemmDesc* d, int ngroups, int dtype, bool* conv_out);  // gemm_nt_w4h.hip
-int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t stream, int ksplit);
+int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t stream, int ksplit, bool eval = false);
 
 // Which kernel a launch runs on, given the tile size launch_nt chose (drn_gemm_nt_plan reports it to callers that schedule
 // around a launch -- functional.input_prep's weight pre-touch -- instead of re-deriving the rule on their side).
@@ -18,7 +18,10 @@ static int nt_kind(const DrnGemmDesc* d, int ngroups, int dtype, int tile, int k
 }
 
 static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t stream, int ksplit_arg = 1, float* ws = nullptr,
-                     int* counters = nullptr, bool planes256 = false, bool plan_only = false) {
+                     int* counters = nullptr, bool planes256 = false, bool plan_only = false, const DrnBnApplyDesc* ev = nullptr,
+                     int ev_relu = 0) {
+  // ev (drn_conv_bn_eval*): the launch ends in eval-mode BatchNorm (+ ReLU) instead of `+ bias`; d[] arrives with the outputs mapped
+  // onto C / C2 / gate (conv_bn_eval_map), so every rule below sees the launch it would see for the plain convolution
   // (the public `ksplit` argument: split count in the low 16 bits + DRN_KSPLIT_CONFIRM_* request bits, include/drn_hip.h)
   const int ksplit = ksplit_arg & 0xffff;
   const int xchg = ksplit_arg & (DRN_XCHG_CONFIRM | DRN_XCHG_NONE);
@@ -80,6 +83,7 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     p.accumulate = s.accumulate;
     p.out_f32 = s.out_f32;
     p.sumsq = s.sumsq;
+    if (ev) { p.ev_ss = ev[g].scale_shift; p.ev_relu = ev_relu ? 1 : 0; }
     p.gb_act = s.gb_act; p.gb_dct = s.gb_dct; p.gb_dgate = s.gb_dgate; p.gb_dsum = s.gb_dsum; p.gb_ld_act = s.gb_ld_act; p.gb_ldt = s.gb_ldt;
     p.tiles_n = cdiv(s.N, tile_n);
     p.tile_start = total;
@@ -105,17 +109,30 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     NT_ATTR(float, 2, 2, 4, 4, 2); NT_ATTR(bf16_t, 2, 2, 4, 4, 2);
     NT_ATTR(float, 4, 2, 4, 4, 2); NT_ATTR(bf16_t, 4, 2, 4, 4, 2);
 #undef NT_ATTR
+#define NT_ATTR(TT, SS, ...) \
+    (void)hipFuncSetAttribute((const void*)conv_gemm_nt_eval_kernel<TT, SS, true, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840); \
+    (void)hipFuncSetAttribute((const void*)conv_gemm_nt_eval_kernel<TT, SS, false, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840)
+    NT_ATTR(float, 2, 2, 4, 8, 4); NT_ATTR(bf16_t, 2, 2, 4, 8, 4);
+    NT_ATTR(float, 2, 2, 4, 4, 2); NT_ATTR(bf16_t, 2, 2, 4, 4, 2);
+    NT_ATTR(float, 4, 2, 4, 4, 2); NT_ATTR(bf16_t, 4, 2, 4, 4, 2);
+#undef NT_ATTR
     attr_set = true;
   }
 #define NT_LAUNCH(TT, SS, THREADS, LDS, ...) do { \
     P.nblocks = total; \
-    if (fast) conv_gemm_nt_kernel<TT, SS, true, __VA_ARGS__><<<dim3(total, ksplit), THREADS, LDS, stream>>>(P); \
+    if (ev && fast) conv_gemm_nt_eval_kernel<TT, SS, true, __VA_ARGS__><<<dim3(total, ksplit), THREADS, LDS, stream>>>(P); \
+    else if (ev) conv_gemm_nt_eval_kernel<TT, SS, false, __VA_ARGS__><<<dim3(total, ksplit), THREADS, LDS, stream>>>(P); \
+    else if (fast) conv_gemm_nt_kernel<TT, SS, true, __VA_ARGS__><<<dim3(total, ksplit), THREADS, LDS, stream>>>(P); \
     else conv_gemm_nt_kernel<TT, SS, false, __VA_ARGS__><<<dim3(total, ksplit), THREADS, LDS, stream>>>(P); } while (0)
   const int kind = w4h ? DRN_NT_KIND_W4H : nt_kind(d, ngroups, dtype, tile, ksplit, planes256);
+  if (ev && kind == DRN_NT_KIND_W4) {
+    drn_set_error("drn_conv_bn_eval: gemm_nt_w4_kernel (large plain products) has no BatchNorm epilogue");
+    return DRN_ERR_UNSUPPORTED;
+  }
   if (plan_only) return kind;
   if (kind == DRN_NT_KIND_W4H) {
     P.nblocks = total;
-    return drn_nt_w4h_launch(P, total, w4h_conv, stream, ksplit);
+    return drn_nt_w4h_launch(P, total, w4h_conv, stream, ksplit, ev != nullptr);
   }
   for (int g = 0; g < ngroups; ++g)
     DRN_CHECK_ARG(!d[g].sumsq || (kind == DRN_NT_KIND_W4 && d[g].out_f32 && !d[g].bias && !d[g].accumulate && ngroups == 1),
@@ -136,7 +153,7 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
   }
   if (kind == DRN_NT_KIND_W4C) {
     P.nblocks = total;
-    return drn_nt_w4c_launch(P, total, stream, ksplit);
+    return drn_nt_w4c_launch(P, total, stream, ksplit, ev != nullptr);
   }
   if (planes256) {
     drn_set_error("drn_gemm_nt_splitk256: the problem is not one gemm_nt_w4c_kernel runs (bf16, k = 3 / stride 1 / pad 1, M and N multiples of 256, Cin of 64)");
@@ -150,7 +167,7 @@ static int launch_nt(const DrnGemmDesc* d, int ngroups, int dtype, hipStream_t s
     if (dtype == DRN_BF16) NT_LAUNCH(bf16_t, 2, 512, 2 * 32768, 2, 4, 4, 2); else NT_LAUNCH(float, 2, 512, 2 * 32768, 2, 4, 4, 2);
   }
 #undef NT_LAUNCH
-  return drn_launch_status("drn_gemm_nt");
+  return drn_launch_status(ev ? "drn_conv_bn_eval" : "drn_gemm_nt");
 }
 
 extern "C" int drn_gemm_nt_plan(const DrnGemmDesc* descs, int ngroups, int dtype) {
@@ -201,6 +218,84 @@ extern "C" int drn_gemm_nt_splitk(const DrnGemmDesc* desc, int ksplit_arg, float
   DRN_CHECK_ARG(ksplit == 1 || (cdiv(desc->M, 128) * cdiv(desc->N, 128) <= DRN_QD_COUNTERS && (((uintptr_t)ws) & 15) == 0),
                 "drn_gemm_nt_splitk: more than %d output tiles or unaligned workspace", DRN_QD_COUNTERS);
   return launch_nt(desc, 1, dtype, (hipStream_t)stream, ksplit_arg, ws, (int*)counters);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Conv1d -> BatchNorm1d (eval) -> [ReLU] in ONE launch (include/drn_hip.h): drn_gemm_nt whose epilogue applies the [2][N] table of
+// drn_bn_eval_scale_shift to the fp32 accumulators -- v = [relu](fmaf(acc, scale, shift)), bn_apply_kernel's arithmetic without the
+// raw tensor in between.  The outputs are mapped onto the epilogue's existing pair: without a gate `out` is C; with one, `out` is
+// the pre-gate copy C2 and `gated` is C.  Kernel choice, tile rule and K order are launch_nt's, as for the plain convolution.
+static int conv_bn_eval_map(const char* who, const DrnGemmDesc* gemm, const DrnBnApplyDesc* bn, int ngroups, int dtype, DrnGemmDesc* out) {
+  DRN_CHECK_ARG(gemm && bn && ngroups >= 1 && ngroups <= DRN_MAX_GROUPS, "%s: bad groups", who);
+  DRN_CHECK_ARG(dtype == DRN_F32 || dtype == DRN_BF16, "%s: bad dtype %d", who, dtype);
+  const int vn = dtype == DRN_BF16 ? 8 : 4;
+#define EV_UNSUPPORTED(cond, ...) do { if (cond) { drn_set_error(__VA_ARGS__); return DRN_ERR_UNSUPPORTED; } } while (0)
+  for (int g = 0; g < ngroups; ++g) {
+    const DrnGemmDesc& s = gemm[g];
+    const DrnBnApplyDesc& b = bn[g];
+    DRN_CHECK_ARG(b.scale_shift && b.out && b.M == s.M && b.L == s.Lout, "%s: group %d: scale_shift / out missing, or M / L differ from the convolution's", who, g);
+    DRN_CHECK_ARG((b.gate != nullptr) == (b.gated != nullptr), "%s: gate and gated must come together", who);
+    EV_UNSUPPORTED(b.up, "%s: group %d: the upsample-add chain (up) needs a finished coarser level", who, g);
+    EV_UNSUPPORTED(s.C2 || s.bias || s.gate || s.stats || s.accumulate || s.out_f32 || s.sumsq || s.gb_act || s.gb_dct || s.gb_dgate || s.gb_dsum,
+                   "%s: group %d: C2 / bias / gate / stats / accumulate / out_f32 / sumsq / gb_* are not served", who, g);
+    EV_UNSUPPORTED(s.mode != 0, "%s: group %d: forward convolutions (mode 0) only", who, g);
+    EV_UNSUPPORTED(s.N != gemm[0].N, "%s: groups with different N", who);
+    EV_UNSUPPORTED(((uintptr_t)b.out & 15) || b.ld_out % vn || (b.gated && (((uintptr_t)b.gated & 15) || b.ld_gated % vn)),
+                   "%s: group %d: outputs must be 16-byte aligned with 16-byte row strides", who, g);
+    DrnGemmDesc& o = out[g];
+    o = s;
+    if (b.gated) {
+      o.C = b.gated; o.ldc = b.ld_gated; o.C2 = b.out; o.ldc2 = b.ld_out; o.gate = b.gate; o.ldg = b.ldg;
+    } else {
+      o.C = b.out; o.ldc = b.ld_out;
+    }
+  }
+#undef EV_UNSUPPORTED
+  return DRN_OK;
+}
+
+extern "C" int drn_conv_bn_eval_plan(const DrnGemmDesc* gemm, const DrnBnApplyDesc* bn, int ngroups, int dtype) {
+  drn_clear_status();
+  DrnGemmDesc m[DRN_MAX_GROUPS];
+  const int rc = conv_bn_eval_map("drn_conv_bn_eval_plan", gemm, bn, ngroups, dtype, m);
+  if (rc != DRN_OK) return rc;
+  return launch_nt(m, ngroups, dtype, nullptr, 1, nullptr, nullptr, false, true, bn, 0);
+}
+
+extern "C" int drn_conv_bn_eval(const DrnGemmDesc* gemm, const DrnBnApplyDesc* bn, int ngroups, int relu, int dtype, void* stream) {
+  drn_clear_status();
+  DrnGemmDesc m[DRN_MAX_GROUPS];
+  const int rc = conv_bn_eval_map("drn_conv_bn_eval", gemm, bn, ngroups, dtype, m);
+  if (rc != DRN_OK) return rc;
+  return launch_nt(m, ngroups, dtype, (hipStream_t)stream, 1, nullptr, nullptr, false, false, bn, relu);
+}
+
+extern "C" int drn_conv_bn_eval_splitk_plan(const DrnGemmDesc* gemm, const DrnBnApplyDesc* bn, int ksplit, int dtype) {
+  drn_clear_status();
+  ksplit &= 0xffff;
+  DRN_CHECK_ARG(ksplit >= 1 && ksplit <= 64, "drn_conv_bn_eval_splitk_plan: bad ksplit");
+  DrnGemmDesc m[DRN_MAX_GROUPS];
+  const int rc = conv_bn_eval_map("drn_conv_bn_eval_splitk_plan", gemm, bn, 1, dtype, m);
+  if (rc != DRN_OK) return rc;
+  static float dummy_ws;           // (plan only, as in drn_gemm_nt_splitk_plan)
+  static int dummy_cnt;
+  return launch_nt(m, 1, dtype, nullptr, ksplit, ksplit > 1 ? &dummy_ws : nullptr, ksplit > 1 ? &dummy_cnt : nullptr, false, true, bn, 0);
+}
+
+extern "C" int drn_conv_bn_eval_splitk(const DrnGemmDesc* gemm, const DrnBnApplyDesc* bn, int ksplit_arg, float* ws, int32_t* counters, int dtype,
+                                       void* stream) {
+  drn_clear_status();
+  const int relu = (ksplit_arg & DRN_KSPLIT_EVAL_RELU) != 0;
+  ksplit_arg &= ~DRN_KSPLIT_EVAL_RELU;
+  const int ksplit = ksplit_arg & 0xffff;
+  DRN_CHECK_ARG(!(ksplit_arg & ~(0xffff | DRN_XCHG_CONFIRM | DRN_XCHG_NONE)), "drn_conv_bn_eval_splitk: unknown bits in ksplit");
+  DRN_CHECK_ARG(gemm && ksplit >= 1 && ksplit <= 64 && (ksplit == 1 || (ws && counters)), "drn_conv_bn_eval_splitk: bad ksplit/workspace/counters");
+  DRN_CHECK_ARG(ksplit == 1 || (cdiv(gemm->M, 128) * cdiv(gemm->N, 128) <= DRN_QD_COUNTERS && (((uintptr_t)ws) & 15) == 0),
+                "drn_conv_bn_eval_splitk: more than %d output tiles or unaligned workspace", DRN_QD_COUNTERS);
+  DrnGemmDesc m[DRN_MAX_GROUPS];
+  const int rc = conv_bn_eval_map("drn_conv_bn_eval_splitk", gemm, bn, 1, dtype, m);
+  if (rc != DRN_OK) return rc;
+  return launch_nt(m, 1, dtype, (hipStream_t)stream, ksplit_arg, ws, (int*)counters, false, false, bn, relu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -28,14 +28,20 @@ struct GemmProb {
   const void* B;
   void* C;
   void* C2;
-  const float* bias;
+  union {
+    const float* bias;
+    const float* ev_ss;   // the EVAL instantiations (drn_conv_bn_eval): [2][N] scale, shift of an eval-mode BatchNorm instead of a bias
+  };
   const float* gate;
   float* stats;
   int M, N, K;
   int Cin, taps, stride, pad, mode;
   int Lout, Lsrc;
   int lda, ldb, ldc, ldg, ldc2;
-  int accumulate;
+  union {
+    int accumulate;
+    int ev_relu;          // the EVAL instantiations (which never accumulate): 1 = ReLU after the affine map
+  };
   int out_f32;      // C is fp32 [M][ldc] whatever T is (weight gradients computed as an NT product of transposed operands)
   int tiles_n, tile_start;
   float* sumsq;     // gemm_nt_w4_kernel, out_f32: [workgroups] sum of the squares of each workgroup's outputs (DrnGemmDesc::sumsq)
@@ -458,7 +464,9 @@ __device__ __forceinline__ void nt_epi_chunk_vec(const GemmProb& pr, const f32x4
 
 // Epilogue shared by the NT kernels.  acc[mi][ni][r]: m = wr*MI*16 + mi*16 + (l>>4)*4 + r, n = wc*NI*16 + ni*16 + (l&15).
 // Enter after a workgroup barrier that follows the last LDS read of the main loop (it reuses `smem`).
-template <typename T, int WM, int WN, int MI, int NI>
+// EVAL (drn_conv_bn_eval): the value is not acc + bias but [relu](fmaf(acc, scale, shift)) -- eval-mode BatchNorm (+ ReLU) of the conv
+// whose accumulator this is, bn_apply_kernel's arithmetic on the unrounded accumulator; pr.C2 / pr.C then carry `out` / `gated`.
+template <typename T, int WM, int WN, int MI, int NI, bool EVAL = false>
 __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& pr, f32x4 (&acc)[MI][NI], char* smem,
                                             const int m0, const int n0, const int tm) {
   constexpr int NW = WM * WN, TM = WM * MI * 16, TN = WN * NI * 16;
@@ -466,7 +474,9 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
   const int wr = w / WN, wc = w % WN;
   const int M = pr.M, N = pr.N;
   (void)TM; (void)NW;
-  if (pr.out_f32) {
+  const int accumulate = EVAL ? 0 : pr.accumulate;
+  const bool ev_relu = EVAL && pr.ev_relu;
+  if (!EVAL && pr.out_f32) {
     // fp32 destination (a weight gradient): each wave transposes its slab (NI*16 columns) through a private LDS patch, 32 rows
     // at a time, and writes 16-byte row segments.  Only bias / accumulate apply here.
     float* __restrict__ Cf = (float*)pr.C;
@@ -518,7 +528,7 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
   const bool vec_ok = (pr.ldc % VEC == 0) && (((uintptr_t)Cg & 15) == 0) &&
                       (!C2g || ((pr.ldc2 % VEC == 0) && (((uintptr_t)C2g & 15) == 0)));
   const bool stats_first = !vec_ok;
-  if (stats_first && pr.stats) {
+  if (!EVAL && stats_first && pr.stats) {
     bn_stats((float*)smem);
     __syncthreads();
   }
@@ -531,12 +541,18 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
     constexpr int LPR = WCOLS * (int)sizeof(T) / 16;         // lanes per staged row in the 16-byte read-back
     constexpr int RPI = 64 / LPR;                            // rows per read-back instruction
     char* wbuf = smem + w * (32 * PITCH);
-    float bias_v[NI];
+    float bias_v[NI], scale_v[NI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
       const int n = n0 + wc * (NI * 16) + ni * 16 + (l & 15);
-      bias_v[ni] = (pr.bias && n < N) ? pr.bias[n] : 0.f;
+      if constexpr (EVAL) {
+        scale_v[ni] = n < N ? pr.ev_ss[n] : 0.f;
+        bias_v[ni] = n < N ? pr.ev_ss[N + n] : 0.f;
+      } else {
+        bias_v[ni] = (pr.bias && n < N) ? pr.bias[n] : 0.f;
+      }
     }
+    (void)scale_v;
     const int npass = C2g ? 2 : 1;
 #pragma unroll
     for (int ch = 0; ch < MI / 2; ++ch) {
@@ -550,7 +566,7 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
         // there were four ds_write_b16.  Same conversions, same values, same 16-byte global stores.
         const int ncol0 = n0 + wc * WCOLS;
         const int sq0 = mrow0 / pr.Lout;
-        const bool fast_w = mrow0 + 32 <= M && ncol0 + WCOLS <= N && !pr.accumulate &&
+        const bool fast_w = mrow0 + 32 <= M && ncol0 + WCOLS <= N && !accumulate &&
                             (!pr.gate || (mrow0 + 31) / pr.Lout == sq0);
         if (__builtin_amdgcn_readfirstlane((int)fast_w)) {
           float gv[NI];
@@ -569,7 +585,12 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                  v[r] = acc[ch * 2 + mi2][ni][r] + bias_v[ni];
+                  if constexpr (EVAL) {
+                    v[r] = fmaf(acc[ch * 2 + mi2][ni][r], scale_v[ni], bias_v[ni]);
+                    if (ev_relu) v[r] = fmaxf(v[r], 0.f);
+                  } else {
+                    v[r] = acc[ch * 2 + mi2][ni][r] + bias_v[ni];
+                  }
                   if (gated) v[r] *= gv[ni];
                 }
                 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -611,7 +632,13 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
             const float* grow = (gated && m < M) ? pr.gate + (long)(m / pr.Lout) * pr.ldg : nullptr;
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) {
-              float v = acc[ch * 2 + mi2][ni][r] + bias_v[ni];
+              float v;
+              if constexpr (EVAL) {
+                v = fmaf(acc[ch * 2 + mi2][ni][r], scale_v[ni], bias_v[ni]);
+                if (ev_relu) v = fmaxf(v, 0.f);
+              } else {
+                v = acc[ch * 2 + mi2][ni][r] + bias_v[ni];
+              }
               if (grow) {
                 const int n = n0 + wc * (NI * 16) + ni * 16 + (l & 15);
                 v *= n < N ? grow[n] : 0.f;
@@ -627,7 +654,7 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
           if (m < M && n < N) {
             const uint4 raw = *(const uint4*)(wbuf + rl * PITCH + cv * 16);
             T* g = dst + ((long)m * ldd + n);
-            const bool acc_c = pr.accumulate && dst == Cg;
+            const bool acc_c = accumulate && dst == Cg;
             if (n + VEC <= N && !acc_c) {
               *(uint4*)g = raw;
             } else {
@@ -644,7 +671,7 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
     // BatchNorm statistics AFTER the stores have been issued: the tile's write burst (the whole chip stores at once: 3-6 us at the
     // HBM write rate) drains while the three-barrier statistics pass runs, instead of starting behind it.  The statistics use the
     // LDS beyond the per-wave store patches.
-    if (pr.stats && !stats_first) bn_stats((float*)(smem + NW * (32 * PITCH)));
+    if (!EVAL && pr.stats && !stats_first) bn_stats((float*)(smem + NW * (32 * PITCH)));
     return;
   }
 #pragma unroll
@@ -659,11 +686,16 @@ __device__ __forceinline__ void nt_epilogue(const NtHeader& P, const GemmProb& p
         const int n = n0 + wc * (NI * 16) + ni * 16 + (l & 15);
         if (n >= N) continue;
         float v = acc[mi][ni][r];
-        if (pr.bias) v += pr.bias[n];
+        if constexpr (EVAL) {
+          v = fmaf(v, pr.ev_ss[n], pr.ev_ss[N + n]);
+          if (ev_relu) v = fmaxf(v, 0.f);
+        } else {
+          if (pr.bias) v += pr.bias[n];
+        }
         const long off = (long)m * pr.ldc + n;
         if (C2g) DT<T>::st(C2g + ((long)m * pr.ldc2 + n), v);
         if (grow) v *= grow[n];
-        if (pr.accumulate) v += DT<T>::ld(Cg + off);
+        if (accumulate) v += DT<T>::ld(Cg + off);
         DT<T>::st(Cg + off, v);
       }
     }
@@ -1046,9 +1078,10 @@ __device__ __forceinline__ void nt_epilogue_bn(const GemmParamsBn& K, int* gen_w
 //              (per-wave timeline: 2300 cycles per K-step for 512 cycles of MFMA); 8 waves halve that and overlap it
 //   <2,4,8,4>: 256x256, 8 waves (2 per SIMD), 64 KB/stage, 2 stages               -- large GEMMs: half the operand
 //              traffic and half the global_load_lds / ds_read per MFMA
-template <typename T, int STAGES, bool FAST, int WM, int WN, int MI, int NI, bool BNF = false, bool CHAIN = false>
-__global__ __launch_bounds__(64 * WM * WN, (BNF && MI * NI == 8 && STAGES == 2) ? 4 : (WM * WN == 8 ? 2 : (STAGES <= 2 ? 2 : 1))) void conv_gemm_nt_kernel(
-    const std::conditional_t<BNF, GemmParamsBn, GemmParams> P_arg) {
+// The kernels proper are at the end of this file: conv_gemm_nt_kernel, and conv_gemm_nt_eval_kernel -- the same body with EVAL, the
+// eval-mode BatchNorm (+ ReLU) epilogue of drn_conv_bn_eval (see nt_epilogue).
+template <typename T, int STAGES, bool FAST, int WM, int WN, int MI, int NI, bool BNF, bool CHAIN, bool EVAL>
+__device__ __forceinline__ void conv_gemm_nt_body(const std::conditional_t<BNF, GemmParamsBn, GemmParams>& P_arg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int CH = 16 / (int)sizeof(T);  // elements per 16-byte chunk
   constexpr int BK = 8 * CH;               // elements per K-step (128 bytes)
@@ -1353,6 +1386,16 @@ __global__ __launch_bounds__(64 * WM * WN, (BNF && MI * NI == 8 && STAGES == 2) 
       __syncthreads();
     }
   }
-  nt_epilogue<T, WM, WN, MI, NI>(P, pr, acc, smem, m0, n0, tm);
+  nt_epilogue<T, WM, WN, MI, NI, EVAL>(P, pr, acc, smem, m0, n0, tm);
   NT_PHASE(4);
+}
+
+template <typename T, int STAGES, bool FAST, int WM, int WN, int MI, int NI, bool BNF = false, bool CHAIN = false>
+__global__ __launch_bounds__(64 * WM * WN, (BNF && MI * NI == 8 && STAGES == 2) ? 4 : (WM * WN == 8 ? 2 : (STAGES <= 2 ? 2 : 1))) void conv_gemm_nt_kernel(
+    const std::conditional_t<BNF, GemmParamsBn, GemmParams> P_arg) {
+  conv_gemm_nt_body<T, STAGES, FAST, WM, WN, MI, NI, BNF, CHAIN, false>(P_arg);
+}
+template <typename T, int STAGES, bool FAST, int WM, int WN, int MI, int NI>
+__global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 2 : (STAGES <= 2 ? 2 : 1)) void conv_gemm_nt_eval_kernel(const GemmParams P_arg) {
+  conv_gemm_nt_body<T, STAGES, FAST, WM, WN, MI, NI, false, false, true>(P_arg);
 }

@@ -34,7 +34,8 @@ extern "C" int drn_debug_epi_cyc(long long* out, int n) { return (int)hipMemcpyF
 #define W4H_HALO 0x100000      // flag in GemmParams::ksplit: the K loop walks (channel block, tap) and stages a channel block ONCE for its three
                                // taps (W4HX_LOOP_ASM, gen_w4_loop.py: rows -1 .. 256 of the tile as four 66-row blocks, a third of the A traffic)
 constexpr int W4H_LDS = 3 * (32768 + 16384), W4HX_A_RING = 2 * 36864, W4HX_LDS = W4HX_A_RING + 5 * 16384;
-template <bool CONV>
+// EVAL: the eval-mode BatchNorm (+ ReLU) epilogue of drn_conv_bn_eval (w4_epilogue.h); loops and exchange are the same statements.
+template <bool CONV, bool EVAL = false>
 __global__ __launch_bounds__(256, 1) void gemm_nt_w4h_kernel(const GemmParams P_arg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, l = tid & 63;
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4h_kernel(const GemmParams P_
   }
 
   NT_PHASE(3);
-  w4h_epilogue<4>(pr, smem + w * (2 * 32 * (4 * 32 + 16)), m0 + wr * 128, n0 + wc * 64, tm * 2 + wr);
+  w4h_epilogue<4, 4, 0, EVAL>(pr, smem + w * (2 * 32 * (4 * 32 + 16)), m0 + wr * 128, n0 + wc * 64, tm * 2 + wr);
 #ifdef DRN_NT_PHASES
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the stamp that follows = the stores have left the wave)
 #endif
@@ -225,12 +226,14 @@ bool drn_nt_w4h_eligible(const DrnGemmDesc* d, int ngroups, int dtype, bool* con
   return true;
 }
 
-int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t stream, int ksplit) {
+int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t stream, int ksplit, bool eval) {
   static bool attr_set = false;
   constexpr int LDS = W4H_LDS;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)gemm_nt_w4h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     (void)hipFuncSetAttribute((const void*)gemm_nt_w4h_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, W4HX_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_w4h_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_w4h_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, W4HX_LDS);
     attr_set = true;
   }
   if (conv && drn_tuning(DRN_TUNE_W4H_HALO) > 0) {
@@ -243,7 +246,8 @@ int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t str
     if (ok) {
       GemmParams Q = P;
       Q.ksplit = P.ksplit | W4H_HALO;
-      gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, W4HX_LDS, stream>>>(Q);
+      if (eval) gemm_nt_w4h_kernel<true, true><<<dim3(total, ksplit), 256, W4HX_LDS, stream>>>(Q);
+      else gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, W4HX_LDS, stream>>>(Q);
       return drn_launch_status("drn_gemm_nt");
     }
   }
@@ -254,11 +258,15 @@ int drn_nt_w4h_launch(const GemmParams& P, int total, bool conv, hipStream_t str
     if ((ksplit - 1) * per < ksteps) {
       GemmParams Q = P;
       Q.ksplit = P.ksplit | W4H_TAPIL;        // (P.ksplit = ksplit + the DRN_XCHG_CONFIRM flag)
-      gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, LDS, stream>>>(Q);
+      if (eval) gemm_nt_w4h_kernel<true, true><<<dim3(total, ksplit), 256, LDS, stream>>>(Q);
+      else gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, LDS, stream>>>(Q);
       return drn_launch_status("drn_gemm_nt");
     }
   }
-  if (conv) gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, LDS, stream>>>(P);
+  if (eval) {
+    if (conv) gemm_nt_w4h_kernel<true, true><<<dim3(total, ksplit), 256, LDS, stream>>>(P);
+    else gemm_nt_w4h_kernel<false, true><<<dim3(total, ksplit), 256, LDS, stream>>>(P);
+  } else if (conv) gemm_nt_w4h_kernel<true><<<dim3(total, ksplit), 256, LDS, stream>>>(P);
   else gemm_nt_w4h_kernel<false><<<dim3(total, ksplit), 256, LDS, stream>>>(P);
   return drn_launch_status("drn_gemm_nt");
 }

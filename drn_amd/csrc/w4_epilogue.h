@@ -42,17 +42,32 @@ __device__ __forceinline__ unsigned w4h_pack_bf16(const float a, const float b) 
 }
 // accumulator tiles (MI, ni), ni = NI0 .. NI - 1, of grid row MI into the lane's place in the patch row(s).  DUAL: the value before the gate
 // goes to the first patch (the pre-gate copy C2), the gated value to the second, from ONE read of the accumulators.
-template <int NI, int NIT, int NOFF, int MI, int NI0, bool GATED, bool DUAL>
-__device__ __forceinline__ void w4h_row_tiles(const float (&g)[NI][4], char* wrow, char* wrow2, const float (&bias4)[NI][4]) {
+// EVAL (drn_conv_bn_eval): not x + bias but [relu](fmaf(x, scale, shift)), bias4 holding the shifts -- eval-mode BatchNorm (+ ReLU) of
+// the accumulator, bn_apply_kernel's arithmetic; a compile-time variant: W4hEval is empty, and the other instantiations keep their code.
+template <int NI, bool EVAL> struct W4hEval {};
+template <int NI> struct W4hEval<NI, true> {
+  float scale4[NI][4];
+  bool relu;
+};
+template <int NI, int NIT, int NOFF, int MI, int NI0, bool GATED, bool DUAL, bool EVAL>
+__device__ __forceinline__ void w4h_row_tiles(const float (&g)[NI][4], char* wrow, char* wrow2, const float (&bias4)[NI][4],
+                                              const W4hEval<NI, EVAL>& ev) {
   if constexpr (NI0 < NI) {
     constexpr int R = (MI * NIT + NOFF + NI0) * 4;
     const float x0 = w4h_acc_read<R>(), x1 = w4h_acc_read<R + 1>(), x2 = w4h_acc_read<R + 2>(), x3 = w4h_acc_read<R + 3>();
-    float v0 = x0 + bias4[NI0][0], v1 = x1 + bias4[NI0][1], v2 = x2 + bias4[NI0][2], v3 = x3 + bias4[NI0][3];
+    float v0, v1, v2, v3;
+    if constexpr (EVAL) {
+      v0 = fmaf(x0, ev.scale4[NI0][0], bias4[NI0][0]); v1 = fmaf(x1, ev.scale4[NI0][1], bias4[NI0][1]);
+      v2 = fmaf(x2, ev.scale4[NI0][2], bias4[NI0][2]); v3 = fmaf(x3, ev.scale4[NI0][3], bias4[NI0][3]);
+      if (ev.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+    } else {
+      v0 = x0 + bias4[NI0][0]; v1 = x1 + bias4[NI0][1]; v2 = x2 + bias4[NI0][2]; v3 = x3 + bias4[NI0][3];
+    }
     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
     if constexpr (DUAL) *(u32x2_t*)(wrow + NI0 * 32) = (u32x2_t){w4h_pack_bf16(v0, v1), w4h_pack_bf16(v2, v3)};
     if constexpr (GATED) { v0 *= g[NI0][0]; v1 *= g[NI0][1]; v2 *= g[NI0][2]; v3 *= g[NI0][3]; }
     *(u32x2_t*)((DUAL ? wrow2 : wrow) + NI0 * 32) = (u32x2_t){w4h_pack_bf16(v0, v1), w4h_pack_bf16(v2, v3)};
-    w4h_row_tiles<NI, NIT, NOFF, MI, NI0 + 1, GATED, DUAL>(g, wrow, wrow2, bias4);
+    w4h_row_tiles<NI, NIT, NOFF, MI, NI0 + 1, GATED, DUAL, EVAL>(g, wrow, wrow2, bias4, ev);
   }
 }
 struct W4hOut {
@@ -72,9 +87,9 @@ struct W4hOut {
 // the chip's write rate, not the wave's).  GATED / DUAL: prop_fc's forward writes the pre-gate value AND the gated one; as two passes
 // over the accumulators (what the old epilogue did too) the step was 10 us slower than with the old layout, as one pass with two
 // patches it is the faster one (in-box A/B of two builds of the library).
-template <int NI, int NIT, int NOFF, int CH, bool GATED, bool DUAL>
+template <int NI, int NIT, int NOFF, int CH, bool GATED, bool DUAL, bool EVAL = false>
 __device__ __forceinline__ void w4h_store_chunk(const W4hOut& O, char* wbuf, const int mrow0, const int ncol0, const float (&bias4)[NI][4],
-                                                float (&g)[NI][4]) {
+                                                float (&g)[NI][4], const W4hEval<NI, EVAL>& ev = W4hEval<NI, EVAL>()) {
   constexpr int PITCH = NI * 32 + 16, LPR = NI * 2, RPI = 64 / LPR, PATCH = 32 * PITCH;
   const int l = w4h_lane(), rho = l & 15, q = l >> 4;
   char* wrow = wbuf + rho * PITCH + q * 8;
@@ -83,7 +98,7 @@ __device__ __forceinline__ void w4h_store_chunk(const W4hOut& O, char* wbuf, con
       const float* gp = O.gate + (long)((mrow0 + CH * 32 + MI2 * 16 + rho) / O.Lout) * O.ldg + ncol0 + 4 * q; \
       _Pragma("unroll") for (int ni = 0; ni < NI; ++ni) _Pragma("unroll") for (int r = 0; r < 4; ++r) g[ni][r] = gp[ni * 16 + r]; \
     } \
-    w4h_row_tiles<NI, NIT, NOFF, 2 * CH + MI2, 0, GATED, DUAL>(g, wrow + MI2 * 16 * PITCH, wrow + PATCH + MI2 * 16 * PITCH, bias4); } while (0)
+    w4h_row_tiles<NI, NIT, NOFF, 2 * CH + MI2, 0, GATED, DUAL, EVAL>(g, wrow + MI2 * 16 * PITCH, wrow + PATCH + MI2 * 16 * PITCH, bias4, ev); } while (0)
   W4H_ROW(0); W4H_ROW(1);
 #undef W4H_ROW
   wave_lds_sync();
@@ -99,8 +114,9 @@ __device__ __forceinline__ void w4h_store_chunk(const W4hOut& O, char* wbuf, con
   }
   wave_lds_sync();
 }
-template <int NI, int NIT, int NOFF, bool GATED, bool DUAL>
-__device__ __forceinline__ void w4h_store_tile(const W4hOut& O, char* wbuf, const int mrow0, const int ncol0, const float (&bias4)[NI][4]) {
+template <int NI, int NIT, int NOFF, bool GATED, bool DUAL, bool EVAL = false>
+__device__ __forceinline__ void w4h_store_tile(const W4hOut& O, char* wbuf, const int mrow0, const int ncol0, const float (&bias4)[NI][4],
+                                               const W4hEval<NI, EVAL>& ev = W4hEval<NI, EVAL>()) {
   float g[NI][4];
   if (GATED && O.gate_uniform) {
     const int l = w4h_lane();
@@ -110,10 +126,10 @@ __device__ __forceinline__ void w4h_store_tile(const W4hOut& O, char* wbuf, cons
 #pragma unroll
       for (int r = 0; r < 4; ++r) g[ni][r] = gp[ni * 16 + r];
   }
-  w4h_store_chunk<NI, NIT, NOFF, 0, GATED, DUAL>(O, wbuf, mrow0, ncol0, bias4, g);
-  w4h_store_chunk<NI, NIT, NOFF, 1, GATED, DUAL>(O, wbuf, mrow0, ncol0, bias4, g);
-  w4h_store_chunk<NI, NIT, NOFF, 2, GATED, DUAL>(O, wbuf, mrow0, ncol0, bias4, g);
-  w4h_store_chunk<NI, NIT, NOFF, 3, GATED, DUAL>(O, wbuf, mrow0, ncol0, bias4, g);
+  w4h_store_chunk<NI, NIT, NOFF, 0, GATED, DUAL, EVAL>(O, wbuf, mrow0, ncol0, bias4, g, ev);
+  w4h_store_chunk<NI, NIT, NOFF, 1, GATED, DUAL, EVAL>(O, wbuf, mrow0, ncol0, bias4, g, ev);
+  w4h_store_chunk<NI, NIT, NOFF, 2, GATED, DUAL, EVAL>(O, wbuf, mrow0, ncol0, bias4, g, ev);
+  w4h_store_chunk<NI, NIT, NOFF, 3, GATED, DUAL, EVAL>(O, wbuf, mrow0, ncol0, bias4, g, ev);
 }
 // first pass of the statistics: sum over mi of the raw accumulators per column slot.  (Passes of their own, each reading the AGPRs
 // again: folded into the store pass the compiler postponed the additions and parked the values -- in AGPRs it believes free, i.e. in
@@ -141,7 +157,7 @@ __device__ __forceinline__ void w4h_sq_tiles(const float (&mean)[NI][4], float (
 // row, ni < NI.  gemm_nt_w4h_kernel: NI = NIT = 4; gemm_nt_w4c_kernel<true> (8 tiles per row) runs it twice with NI = 4, NOFF = 0 / 4 --
 // as ONE 8-tile-wide pass the register allocator ran out and parked values in AGPRs (tests/test_kernel_resources_cpu.py).
 // mrow0 / ncol0 = first row / column of the sub-tile; slab = the wave's 128-row slab.
-template <int NI, int NIT = NI, int NOFF = 0>
+template <int NI, int NIT = NI, int NOFF = 0, bool EVAL = false>
 __device__ __forceinline__ void w4h_epilogue(const GemmProb& pr, char* wbuf, const int mrow0, const int ncol0, const int slab) {
   const int l = w4h_lane();
   const int ncolq = ncol0 + 4 * (l >> 4);
@@ -149,6 +165,21 @@ __device__ __forceinline__ void w4h_epilogue(const GemmProb& pr, char* wbuf, con
   asm volatile("" : "+s"(Lout));      // (opaque: the reciprocal the staging code derived from Lout before the loop must not be kept alive for the gate rows)
   W4hOut O{(bf16_t*)pr.C, (bf16_t*)pr.C2, pr.gate, (long)pr.ldc, (long)pr.ldc2, (long)pr.ldg, Lout, mrow0 / Lout == (mrow0 + 127) / Lout};
   float bias4[NI][4];
+  if constexpr (EVAL) {
+    // out = the value before the gate = O.C2 when there is a gate (O.C: gated), else O.C -- the launcher's mapping (gemm_nt.hip)
+    W4hEval<NI, true> ev;
+    ev.relu = pr.ev_relu != 0;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        ev.scale4[ni][r] = pr.ev_ss[ncolq + ni * 16 + r];
+        bias4[ni][r] = pr.ev_ss[pr.N + ncolq + ni * 16 + r];
+      }
+    if (O.gate) w4h_store_tile<NI, NIT, NOFF, true, true, true>(O, wbuf, mrow0, ncol0, bias4, ev);
+    else w4h_store_tile<NI, NIT, NOFF, false, false, true>(O, wbuf, mrow0, ncol0, bias4, ev);
+    return;
+  }
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni)
 #pragma unroll

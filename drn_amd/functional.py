@@ -8,6 +8,7 @@ bfloat16 = storage with fp32 accumulation).  Parameters stay fp32; their GEMM-la
 `stacked_t`) live in the `WeightCopies` store of the model that owns the parameters (`mainModel.weight_copies`; a shared default
 for stand-alone layers) and are refreshed by the optimizer kernels / in one launch after the optimizer step (`repack_all`).
 """
+import contextlib
 import weakref
 
 import torch
@@ -611,6 +612,21 @@ def _tap_relu(weight, level, out, up=None):
     relu_tap.append((weight, level, mask))
 
 
+# Eval-mode conv -> BatchNorm -> ReLU blocks in ONE launch each (ops.conv_bn_eval: the affine map runs in the GEMM's epilogue, the raw
+# tensor is never written).  Off unless inside fused_eval(); a stage the library cannot serve that way runs the separate launches.
+FUSED_EVAL = False
+
+
+@contextlib.contextmanager
+def fused_eval(on=True):
+    global FUSED_EVAL
+    prev, FUSED_EVAL = FUSED_EVAL, bool(on)
+    try:
+        yield
+    finally:
+        FUSED_EVAL = prev
+
+
 class ConvMeta(object):
     """Static (non-tensor) description of one conv+BN(+ReLU) block call."""
 
@@ -659,7 +675,8 @@ class _ConvBlockFn(torch.autograd.Function):
                 stats.append(st)
                 descs[l].stats = ops._p(st)
             ops.gemm_nt(descs, code)
-        if not fused:
+        ev = FUSED_EVAL and not meta.training and up is None      # (conv and BatchNorm in one launch, tried below)
+        if not fused and not ev:
             gemm_with_stats()
         track = False
         if meta.training:
@@ -710,7 +727,9 @@ class _ConvBlockFn(torch.autograd.Function):
                 for l in range(nl):
                     levels[l]["stats"] = stats[l]
                 ops.bn_train_apply(levels, Cout, code, relu=meta.relu)
-        else:
+        elif not (ev and ops.conv_bn_eval(descs, levels, code, meta.relu)):
+            if ev:
+                gemm_with_stats()
             ops.bn_apply_multi(levels, Cout, code, relu=meta.relu)        # all pyramid levels in one launch
         if relu_tap is not None and meta.relu:
             for l in range(nl):
@@ -950,6 +969,8 @@ class _MultiConvFn(torch.autograd.Function):
         # levels it adds from their raw outputs and statistics inside that launch (drn_conv_bn_train, up_group)
         one_launch = fused and same_c and ops.conv_bn_train(descs, lvs, code, up_group=[l + 1 if (chain_up and l + 1 < n) else -1
                                                                                              for l in range(n)])
+        if not one_launch and FUSED_EVAL and not training and not chain_up and same_c:
+            one_launch = ops.conv_bn_eval(descs, lvs, code, True)
         if not one_launch:
             for l in range(n):                                 # the convs as their own launch leave per-slab statistics behind
                 st = torch.empty(((geo[l][3] + 127) // 128, 2, geo[l][5]), dtype=torch.float32, device=dev) if training else None

@@ -752,6 +752,80 @@ def conv_bn_train(descs, levels, dtype, relu=True, up_group=None):
     return True
 
 
+# conv -> BN(eval) -> ReLU in ONE launch (drn_conv_bn_eval): eval BatchNorm is a per-channel affine map, so it runs in the GEMM's
+# epilogue and the raw tensor is never written.  Opt-in (functional.fused_eval); conv_bn_eval_launches counts the launches that ran.
+KSPLIT_EVAL_RELU = 0x1000000
+conv_bn_eval_launches = 0
+
+
+def _bn_apply_descs(levels):
+    arr = (_lib.BnApplyDesc * len(levels))()
+    for d, v in zip(arr, levels):
+        gate = v.get("gate")
+        d.raw, d.scale_shift, d.out = _p(v.get("raw")), _p(v["ss"]), _p(v["out"])
+        d.up, d.gate, d.gated = _p(v.get("up")), _p(gate), _p(v.get("gated") if gate is not None else None)
+        d.ld_raw, d.ld_out, d.ld_up = v.get("ld_raw", 0), v["ld_out"], v.get("ld_up", 0)
+        d.ldg, d.ld_gated = (gate.stride(0) if gate is not None else 0), v.get("ld_gated", 0)
+        d.M, d.L = v["M"], v["L"]
+    return arr
+
+
+def _conv_bn_eval_call(descs, levels, dtype, relu, plan):
+    """-> the library's return code: the launch (or, plan=True, the kernel kind it would run on) with the split gemm_nt would choose for
+    the same problems, so that a stage keeps its kernel and its K order; DRN_ERR_UNSUPPORTED where that split has no fused form."""
+    global conv_bn_eval_launches
+    arr = (GemmDesc * len(descs))(*descs)
+    barr = _bn_apply_descs(levels)
+    ks = _ksplit_w4h(descs, dtype)
+    if ks == 1:
+        if _ksplit256(descs, dtype) > 1:
+            return DRN_ERR_UNSUPPORTED
+        ks = _ksplit(descs, dtype)
+        if ks > 1 and len(descs) > 1:          # the grouped K-split has no fused form
+            return DRN_ERR_UNSUPPORTED
+    d0 = descs[0]
+    if plan:
+        return lib().drn_conv_bn_eval_splitk_plan(arr, barr, ks, dtype) if ks > 1 else lib().drn_conv_bn_eval_plan(arr, barr, len(descs), dtype)
+    flops = sum(2.0 * d.M * d.N * d.taps * d.Cin for d in descs)
+    tag = "gemm_nt[%s] g=%d M=%d N=%d K=%d mode=0 +bn(eval)%s" % ("bf16" if dtype == BF16 else "f32", len(descs), sum(d.M for d in descs), d0.N,
+                                                                 d0.taps * d0.Cin, " splitK=%d" % ks if ks > 1 else "")
+    rc = []
+    if ks > 1:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        tiles = ((d0.M + 127) // 128) * ((d0.N + 127) // 128)
+        ws = torch.empty(ks * max(tiles * 128 * 128, d0.M * d0.N), dtype=torch.float32, device=dev)
+        arg = _ksplit_arg(ks) | (KSPLIT_EVAL_RELU if relu else 0)
+        _timed(tag, flops, lambda: rc.append(lib().drn_conv_bn_eval_splitk(arr, barr, arg, _p(ws), _p(_counters(dev)), dtype, _stream())))
+    else:
+        _timed(tag, flops, lambda: rc.append(lib().drn_conv_bn_eval(arr, barr, len(descs), int(relu), dtype, _stream())))
+    if rc[0] == DRN_ERR_UNSUPPORTED and kernel_timer is not None:
+        kernel_timer.pop()
+    if rc[0] == 0:
+        conv_bn_eval_launches += 1
+    return rc[0]
+
+
+def conv_bn_eval(descs, levels, dtype, relu=True):
+    """descs: gemm_desc per group (no bias / gate / C2 / stats; C is not written and may be None); levels: the bn_apply_multi dicts of
+    the same groups (`raw` unused, no `up`).  -> True when launched; False when the library cannot serve this launch
+    (DRN_ERR_UNSUPPORTED): the caller runs gemm_nt + bn_apply_multi."""
+    rc = _conv_bn_eval_call(descs, levels, dtype, relu, False)
+    if rc == DRN_ERR_UNSUPPORTED:
+        return False
+    check(rc, "drn_conv_bn_eval")
+    return True
+
+
+def conv_bn_eval_plan(descs, levels, dtype):
+    """The kernel conv_bn_eval would run these problems on (NT_KIND_*), or None where it would return False."""
+    rc = _conv_bn_eval_call(descs, levels, dtype, False, True)
+    if rc == DRN_ERR_UNSUPPORTED:
+        return None
+    if rc < 0:
+        check(rc, "drn_conv_bn_eval_plan")
+    return rc
+
+
 def conv_bn_train_timeouts(reset=True):
     """Workgroups of fused conv->BN launches that gave up waiting for their tile column (0 in a healthy run).  Synchronises."""
     return int(lib().drn_conv_bn_train_timeouts(int(reset)))

@@ -478,16 +478,17 @@ class Trainer(object):
         return total / max(n, 1), topks, accs, results
 
     @torch.no_grad()
-    def predict(self, loader, top_k=5, nms_overlap=0.45, share_videos=True, id2word=None):
+    def predict(self, loader, top_k=5, nms_overlap=0.45, share_videos=True, id2word=None, fused=False, graph=False):
         """Ground every query of `loader` (collate_data batches; the ground truth in them is not read): ->
         {video: [{"query": str, "moments": [[start, end, score], ...]}]}, at most top_k moments per query, best first, after the
         evaluator's temporal NMS at nms_overlap (drn_amd.grounding.Grounder).  share_videos: the queries of a batch that name the
         same video share its prop_fc product (group_by_video); False runs every query as a clip of its own.  The model is run in
-        eval mode and put back into the mode it was in; no parameter or buffer changes."""
+        eval mode and put back into the mode it was in; no parameter or buffer changes.  fused / graph: Grounder's options (one-launch
+        eval conv blocks; hipGraph replay per batch signature)."""
         from .grounding import Grounder, group_by_video
         was_training = self.model.training
         self.model.eval()
-        grounder = Grounder(self.model, top_k=top_k, nms_overlap=nms_overlap)
+        grounder = Grounder(self.model, top_k=top_k, nms_overlap=nms_overlap, fused=fused, graph=graph)
         out = {}
         try:
             for batch in loader:

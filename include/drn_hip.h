@@ -307,6 +307,30 @@ typedef struct DrnBnApplyDesc {
   int32_t ld_raw, ld_out, ld_up, ldg, ld_gated, M, L;
 } DrnBnApplyDesc;
 int drn_bn_apply_multi(const DrnBnApplyDesc* descs /*host*/, int n, int C, int relu, int dtype, void* stream);
+/* Conv1d -> BatchNorm1d (eval) -> [ReLU] in ONE launch: drn_gemm_nt + drn_bn_apply_multi without the raw tensor.  Eval BatchNorm is a
+ * per-channel affine map, so it runs in the GEMM epilogue: no statistics, no exchange, no second pass over the output.
+ * Per group g, with acc[m][n] the fp32 accumulator of problem gemm[g] (mode 0; any taps / stride / pad drn_gemm_nt serves) and
+ * (sc, sh) = bn[g].scale_shift[n], scale_shift[N + n] -- the table drn_bn_eval_scale_shift writes, conv bias folded into sh:
+ *   v = fmaf(acc, sc, sh);  v = fmaxf(v, 0) when relu;
+ *   out[m*ld_out + n] = dtype(v);
+ *   with bn[g].gate: gated[m*ld_gated + n] = dtype(v * gate[(m / L)*ldg + n])  -- from the unrounded v, as drn_bn_apply_multi does.
+ * In fp32 the results are bit-identical to drn_gemm_nt followed by drn_bn_apply_multi (the raw fp32 tensor IS the accumulator); in
+ * bf16 they skip the rounding of the raw tensor.  gemm[g].C is not written and may be NULL; bn[g].raw is ignored; bn[g].M / L must
+ * equal gemm[g].M / Lout.
+ * DRN_ERR_UNSUPPORTED -- nothing launched, drn_last_error() says why, run the separate launches: bn[g].up set (the FPN top-down chain
+ * needs a finished coarser level); any of gemm[g].C2 / bias / gate / stats / accumulate / out_f32 / sumsq / gb_*; mode 1; groups with
+ * different N; outputs that are not 16-byte aligned with 16-byte row strides; a launch drn_gemm_nt_plan puts on DRN_NT_KIND_W4
+ * (gemm_nt_w4_kernel has no such epilogue).
+ * Kernel selection is drn_gemm_nt's / drn_gemm_nt_splitk's own (same tile rule, same drn_tune keys, same K order): a convolution runs
+ * on the kernel kind it runs on without the fusion; the _plan entry points report that kind (or an error code) without launching.
+ * _splitk serves ONE problem (conv0); ws / counters as for drn_gemm_nt_splitk; OR DRN_KSPLIT_EVAL_RELU into ksplit for the ReLU.  The
+ * grouped K-split has no fused form. */
+#define DRN_KSPLIT_EVAL_RELU 0x1000000
+int drn_conv_bn_eval(const DrnGemmDesc* gemm /*host*/, const DrnBnApplyDesc* bn /*host*/, int ngroups, int relu, int dtype, void* stream);
+int drn_conv_bn_eval_plan(const DrnGemmDesc* gemm /*host*/, const DrnBnApplyDesc* bn /*host*/, int ngroups, int dtype);
+int drn_conv_bn_eval_splitk(const DrnGemmDesc* gemm /*host*/, const DrnBnApplyDesc* bn /*host*/, int ksplit, float* ws, int32_t* counters,
+                            int dtype, void* stream);
+int drn_conv_bn_eval_splitk_plan(const DrnGemmDesc* gemm /*host*/, const DrnBnApplyDesc* bn /*host*/, int ksplit, int dtype);
 /* Train-mode forward in ONE launch (C % 64 == 0): statistics merge + running-statistics update + apply.  Each workgroup of the
  * apply pass merges the slab statistics of its own 64 channels; scale_shift / save / the running statistics are written once
  * per channel, groups in order (groups may share a BatchNorm module: model/fcos.py:93-102).  Replaces drn_bn_finalize(_multi)

@@ -5,7 +5,7 @@ loss + drn_eval_recall), in one process on one MI355X.
 
 Shape: T = 256 proposals, D = 4096, bf16, Q = 32 queries per batch over V = Q / share videos, share = Q/V in {1, 2, 4}.  Both paths
 read device-resident batches (no host -> device copy inside the window) and end in one device synchronise per timed window.  The
-four variants are run interleaved, `--rounds` rounds of `--iters` batches each after `--warmup` untimed batches per variant; the
+all variants (the eager ones, and `fused` / `graph` / `fused+graph` of each sharing factor) are run interleaved, `--rounds` rounds of `--iters` batches each after `--warmup` untimed batches per variant; the
 figure reported is the median over rounds, with the min / max next to it.  evaluate() is timed on V = Q clips whatever the share
 (it has no way to share a video), so its three figures are repeats of one measurement and show the spread.
 
@@ -50,6 +50,9 @@ def main():
     model = model.to(dev).eval()
     trainer = TR.Trainer(model, 3, lr=1e-4)
     grounder = Grounder(model, top_k=5, nms_overlap=0.45)
+    engines = {"fused": Grounder(model, top_k=5, nms_overlap=0.45, fused=True),
+               "graph": Grounder(model, top_k=5, nms_overlap=0.45, graph=True, max_graphs=8),
+               "fused+graph": Grounder(model, top_k=5, nms_overlap=0.45, fused=True, graph=True, max_graphs=8)}
     tok, qlen, feats, pse, gt, nprops, nframes = synthetic_batch(Q, T, D, seed=11)
     tok, qlen, feats, pse, gt = (t.to(dev) for t in (tok, qlen, feats, pse, gt))
     names = ["v%d" % i for i in range(Q)]
@@ -63,6 +66,9 @@ def main():
         f, p = feats[:V].contiguous(), pse[:V].contiguous()
         index = None if share == 1 else vid
         variants["ground_share%d" % share] = (lambda f=f, p=p, index=index: grounder.ground(tok, qlen, f, p, index))
+        # the opt-in paths, same inputs: one-launch eval conv blocks, hipGraph replay, both (the base is the eager variant above)
+        for tag, g in engines.items():
+            variants["ground_%s_share%d" % (tag, share)] = (lambda g=g, f=f, p=p, index=index: g.ground(tok, qlen, f, p, index))
     variants["evaluate"] = lambda: trainer.evaluate([eval_batch], with_results=False)
 
     def window(fn, n):
