@@ -131,6 +131,13 @@ class LossLevel(ctypes.Structure):
     _fields_ = [("L", c_int32), ("stride", c_float), ("lo", c_float), ("hi", c_float)]
 
 
+class PoolPropsDesc(ctypes.Structure):
+    """DrnPoolProps (include/drn_hip.h): one gather of proposal features from a device-resident feature store."""
+    _fields_ = [("feats", c_void_p), ("seg_off", c_void_p), ("prop_off", c_void_p), ("win", c_void_p), ("pse", c_void_p),
+                ("vids", c_void_p), ("vids_host", c_void_p), ("counts_host", c_void_p), ("out", c_void_p), ("out_pse", c_void_p),
+                ("Nv", c_int32), ("B", c_int32), ("T", c_int32), ("D", c_int32), ("dtype", c_int32), ("max_rows", c_int32)]
+
+
 c_double = ctypes.c_double
 # argument lists of include/drn_hip.h, in its order, for the entry points that declare them (tests/test_grounding_cpu.py counts them
 # against the header)
@@ -139,6 +146,7 @@ SIGNATURES = {
                            c_void_p, c_void_p],
     "drn_gate_gather_fwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                             c_int, c_int, c_int, c_void_p],
+    "drn_pool_props": [c_void_p, c_void_p],
 }
 
 
@@ -153,7 +161,7 @@ def lib():
         _lib.drn_last_error.restype = ctypes.c_char_p
         for fn in ("drn_wgrad_ws_elems", "drn_skinny_group_ws_elems", "drn_opt_nblocks", "drn_gemm_nt_splitk_ws_elems", "drn_gemm_nt_splitk256_ws_elems", "drn_heads_ws_elems",
                    "drn_conv_tail_bwd_ws_elems", "drn_conv_bn_train_ws_bytes", "drn_wgrad_pending_bytes", "drn_bn_bwd_one_ws_bytes", "drn_lstm_seq_fwd_ws_bytes",
-                   "drn_diag_mfma_ws_bytes"):
+                   "drn_diag_mfma_ws_bytes", "drn_pool_props_lds_rows"):
             if hasattr(_lib, fn):
                 getattr(_lib, fn).restype = c_int64
         # (ctypes passes a Python float as nothing at all without a declared signature: the calls that take a double declare theirs)

@@ -33,6 +33,33 @@ def default_tokenizer():
         return lambda s: pat.findall(s)
 
 
+def proposal_windows(proposals, num_frames, n_segments, window, overlap):
+    """The window arithmetic of CharadesSTA.__getitem__ (dataset.py:119-154) without the features: for each (start, end) frame pair
+    the stored segments whose element-wise max is the proposal's feature, and the proposal's normalised bounds.
+    -> lo, hi (P,) int32, inclusive and local to the video; pse (P, 2) float64 = (start, end) / num_frames.
+    The index list of __getitem__ -- first = floor(start / interval) * interval, one index when the proposal is no longer than a
+    window, else every interval up to the end frame, each clamped to the last stored segment -- is a contiguous run after the
+    clamp, so (lo, hi) describes it exactly: range(lo, hi + 1) (tests/test_store_cpu.py checks that by brute force)."""
+    interval = int(window * (1 - overlap))
+    if interval <= 0:
+        raise ValueError("proposal_windows: window %r with overlap %r leaves no interval between windows" % (window, overlap))
+    if n_segments < 1 or num_frames < 1:
+        raise ValueError("proposal_windows: a video needs at least one stored segment and one frame")
+    last = n_segments - 1
+    P = len(proposals)
+    lo, hi, pse = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32), np.zeros((P, 2), dtype=np.float64)
+    for i, (start, end) in enumerate(proposals):
+        if start < 0:
+            raise ValueError("proposal_windows: proposal %d starts before the video (%r)" % (i, start))
+        pse[i, 0], pse[i, 1] = start / num_frames, end / num_frames
+        first = (int(start) // interval) * interval
+        a = b = first // interval
+        if end - start > window:
+            b = a + (int(end) - first - 1) // interval                      # the last element of range(first, end, interval)
+        lo[i], hi[i] = min(last, a), min(last, b)
+    return lo, hi, pse
+
+
 class CharadesSTA(Dataset):
     def __init__(self, dataset_configs, split="train", root=".", tokenizer=None):
         cfg = dataset_configs if isinstance(dataset_configs, dict) else vars(dataset_configs)
@@ -74,6 +101,15 @@ class CharadesSTA(Dataset):
 
     def __len__(self):
         return len(self.samples)
+
+    def meta(self, index):
+        """Everything of sample `index` that is not a feature: (vid, tokens, gt, num_frames), as __getitem__ returns them, without
+        opening the feature file (drn_amd.store.StoreLoader builds its batches from these)."""
+        smp = self.samples[index]
+        vid = smp["vid"]
+        duration = float(self.duration_info[vid])
+        gt = (smp["gt_start_time"] / duration, smp["gt_end_time"] / duration)
+        return vid, torch.from_numpy(np.array(smp["tokens"])), gt, self.props[vid][0]
 
     def __getitem__(self, index):
         smp = self.samples[index]

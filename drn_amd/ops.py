@@ -621,6 +621,41 @@ def gate_gather_fwd(z, ld_z, gate, pos, ld_pos, vid, V, out, ld_out, Q, L, C, P,
                                     dtype, _stream()), "drn_gate_gather_fwd")
 
 
+def pool_props_lds_rows(B, D, dtype):
+    """Rows of one video the LDS path of drn_pool_props holds for B clips of D elements (0: the element-wise path)."""
+    return int(lib().drn_pool_props_lds_rows(int(B), int(D), int(dtype)))
+
+
+def pool_props(feats, seg_off, prop_off, win, pse, vids, T, out, out_pse, vids_host=None, counts_host=None, max_rows=0, tag=None):
+    """out[b, t] = max over rows seg_off[v] + lo .. seg_off[v] + hi of feats, out_pse[b, t] = pse[prop_off[v] + t] for v = vids[b],
+    [lo, hi] = win[prop_off[v] + t], t < the video's proposal count; zeros past it (drn_pool_props: one launch, every element of
+    out (B, T, D) and out_pse (B, T, 2) written once).  vids: (B,) int32 on the device.  vids_host / counts_host: optional host copies
+    (int32, contiguous) of the indices and of the clips' proposal counts -- given, an index outside [0, Nv) or a count above T
+    raises before the launch; without vids_host the kernel writes zeros for such a clip.  tag: name under ops.kernel_timer."""
+    _need_gpu(feats, seg_off, prop_off, win, pse, vids, out, out_pse)
+    B, Nv = int(vids.numel()), int(seg_off.numel()) - 1
+    D = int(feats.shape[-1])
+    for name, t, dt in (("seg_off", seg_off, torch.int64), ("prop_off", prop_off, torch.int32), ("win", win, torch.int32),
+                        ("pse", pse, torch.float64), ("vids", vids, torch.int32), ("out_pse", out_pse, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise _lib.DrnError("pool_props: %s must be a contiguous %s tensor" % (name, dt))
+    if out.dtype != feats.dtype or not out.is_contiguous() or not feats.is_contiguous() or tuple(out.shape) != (B, T, D) \
+            or tuple(out_pse.shape) != (B, T, 2) or prop_off.numel() != Nv + 1 or win.shape[0] != pse.shape[0]:
+        raise _lib.DrnError("pool_props: out must be a contiguous (%d, %d, %d) %s tensor and out_pse (%d, %d, 2)"
+                            % (B, T, D, feats.dtype, B, T))
+    host = []
+    for name, t in (("vids_host", vids_host), ("counts_host", counts_host)):
+        if t is not None and (t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B):
+            raise _lib.DrnError("pool_props: %s must be a contiguous int32 host tensor of %d entries" % (name, B))
+        host.append(ctypes.c_void_p(t.data_ptr()) if t is not None and B else None)
+    d = _lib.PoolPropsDesc(feats=_p(feats), seg_off=_p(seg_off), prop_off=_p(prop_off), win=_p(win), pse=_p(pse), vids=_p(vids),
+                           vids_host=host[0], counts_host=host[1], out=_p(out), out_pse=_p(out_pse), Nv=Nv, B=B, T=int(T), D=D,
+                           dtype=dtype_code(feats), max_rows=int(max_rows))
+    if B == 0 or T == 0:
+        return                                                                  # (nothing to write; data_ptr() of an empty tensor is null)
+    _timed(tag or "pool_props", 0, lambda: check(lib().drn_pool_props(ctypes.byref(d), _stream()), "drn_pool_props"))
+
+
 def gate_bwd(dG, ld_dg, act, ld_act, gate, dC, ld_dc, add, ld_add, dgate, nseq, L, C, dtype, dsum=None):
     """dC = (add or 0) + dG * gate; dgate = sum_t dG * act; dsum (nseq, C) fp32 = sum_t dG * gate."""
     check(lib().drn_gate_bwd(_p(dG), ld_dg, _p(act), ld_act, _p(gate), gate.stride(0), _p(add), ld_add, _p(dC), ld_dc, _p(dgate),

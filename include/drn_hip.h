@@ -680,6 +680,36 @@ int drn_adam_tiled(const float* g, float* m, float* v, const DrnAdamTiledItem* i
                    const int32_t* blk_tile_dev, int nblocks, const float* total_sumsq, const int* step_counter, float lr, float beta1,
                    float beta2, float eps, float max_norm, float grad_scale, void* stream);
 
+/* Proposal features from a device-resident feature store (drn_amd.store; replaces the reference's per-sample host loop,
+ * dataset.py:118-154 + the collate padding 180-224, on the device): for clip b with video v = vids[b], n = prop_off[v+1] - prop_off[v]
+ * and proposal t < n with [lo, hi] = win[prop_off[v] + t],
+ *   out[b][t][:]  = element-wise max over rows seg_off[v] + lo .. seg_off[v] + hi of feats     out_pse[b][t] = pse[prop_off[v] + t]
+ * and rows t >= n are zero in both.  Every element of out (B, T, D) and out_pse (B, T, 2) is written exactly once (no clearing by the
+ * caller); the running maximum starts from the first row of the run (features are signed) and is an exact order comparison of the stored
+ * bits (-0 < +0); the store holds finite values only.  A vids[b] outside [0, Nv) (or a video of no rows) reads nothing and has its rows
+ * written as zeros; lo / hi are clamped to the video's rows and n to T, so a bad table cannot read outside feats.
+ * One workgroup owns one clip x one column block: it stages the video's rows of that block in LDS once (videos of at most
+ * drn_pool_props_lds_rows() rows; longer ones are read through L2), its lanes own 16-byte column chunks.  Rows whose byte length
+ * is not a multiple of 16 (or unaligned bases) take an element-wise path.  Host checks, DRN_ERR_ARG before anything is launched:
+ * null pointers, negative counts, a vids_host entry outside [0, Nv), T < a counts_host entry, dtype; pse / out_pse 16-byte aligned. */
+typedef struct DrnPoolProps {
+  const void* feats;         /* (R, D) row-major, `dtype` */
+  const int64_t* seg_off;    /* (Nv + 1) first row of each video */
+  const int32_t* prop_off;   /* (Nv + 1) first proposal of each video in win / pse */
+  const int32_t* win;        /* (Ptot, 2) [lo, hi], inclusive, local to the video */
+  const double* pse;         /* (Ptot, 2) */
+  const int32_t* vids;       /* (B) device */
+  const int32_t* vids_host;  /* (B) host copy of vids, or NULL */
+  const int32_t* counts_host;/* (B) host: proposals of each clip, or NULL */
+  void* out;                 /* (B, T, D) `dtype` */
+  double* out_pse;           /* (B, T, 2) */
+  int32_t Nv, B, T, D, dtype;
+  int32_t max_rows;          /* rows of the longest video when the caller knows them (sizes the LDS request), else 0 */
+} DrnPoolProps;
+int drn_pool_props(const DrnPoolProps* d /*host*/, void* stream);
+/* rows of one video the LDS path of drn_pool_props holds for B clips of D elements (0: that geometry takes the element-wise path) */
+int64_t drn_pool_props_lds_rows(int B, int D, int dtype);
+
 /* MEASUREMENT infrastructure (bench.py; nothing on the product path calls it): what this chip sustains on bf16 MFMA with operands that
  * toggle like data.  MI355X clocks to its power budget: a register-only v_mfma_f32_32x32x16_bf16 loop at the issue floor (32 cycles per
  * MFMA and SIMD, 256 workgroups x 4 waves, no LDS or memory traffic) runs at ~2.3 GHz on zeros and ~1.7-1.8 GHz on random bf16 operands.

@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="launch every kernel of a step from Python instead of replaying it as a hipGraph (stages 1 and 3)")
+    ap.add_argument("--device-store", action="store_true",
+                    help="keep every video's window features on the GPU (drn_amd.store.FeatureStore, in the model dtype) and build each "
+                         "batch's proposal features there in one launch instead of in DataLoader workers")
     args = ap.parse_args()
 
     rank, local, world = ddist.init_from_env()
@@ -56,15 +59,26 @@ def main():
     test_set = CharadesSTA(cfg, "test", args.root)
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, world, rank, shuffle=True) if world > 1 else None
     bs = args.batch_size or cfg.get("batch_size", 32)
-    # the workers hand the features over in the compute dtype (bf16: half the bytes over PCIe, same bits after the step's cast)
-    collate = functools.partial(collate_data, feature_dtype=torch.bfloat16 if args.dtype == "bf16" else None)
-    train_loader = DataLoader(train_set, batch_size=bs, shuffle=sampler is None, sampler=sampler, collate_fn=collate,
-                              num_workers=args.workers, pin_memory=True, drop_last=world > 1)
-    # evaluation is sharded too: every rank scores its share of the test queries (Recall@k with temporal NMS on the device)
-    # and the ranks merge their counts (drn_amd.trainer.Trainer.evaluate) -- replaces main.py:275-366 on one process
-    test_loader = DataLoader(test_set, batch_size=cfg.get("test_batch_size", 16), shuffle=False, collate_fn=collate,
-                             sampler=ShardSampler(test_set, world, rank) if world > 1 else None,
-                             num_workers=args.workers, pin_memory=True)
+    if args.device_store:
+        # one store per rank serves both splits (they share the props table); only tokens, lengths, ground truth and video indices
+        # leave the host per step
+        from drn_amd.store import FeatureStore, StoreLoader
+        store = FeatureStore.from_dataset(train_set, dev, torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+        if rank == 0:
+            print("device store: %d videos, %.1f MB" % (len(store), store.nbytes / 1e6))
+        train_loader = StoreLoader(train_set, store, bs, shuffle=sampler is None, sampler=sampler, drop_last=world > 1)
+        test_loader = StoreLoader(test_set, store, cfg.get("test_batch_size", 16),
+                                  sampler=ShardSampler(test_set, world, rank) if world > 1 else None)
+    else:
+        # the workers hand the features over in the compute dtype (bf16: half the bytes over PCIe, same bits after the step's cast)
+        collate = functools.partial(collate_data, feature_dtype=torch.bfloat16 if args.dtype == "bf16" else None)
+        train_loader = DataLoader(train_set, batch_size=bs, shuffle=sampler is None, sampler=sampler, collate_fn=collate,
+                                  num_workers=args.workers, pin_memory=True, drop_last=world > 1)
+        # evaluation is sharded too: every rank scores its share of the test queries (Recall@k with temporal NMS on the device)
+        # and the ranks merge their counts (drn_amd.trainer.Trainer.evaluate) -- replaces main.py:275-366 on one process
+        test_loader = DataLoader(test_set, batch_size=cfg.get("test_batch_size", 16), shuffle=False, collate_fn=collate,
+                                 sampler=ShardSampler(test_set, world, rank) if world > 1 else None,
+                                 num_workers=args.workers, pin_memory=True)
 
     model = mainModel(len(word2id), argparse.Namespace(**cfg),
                       compute_dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
