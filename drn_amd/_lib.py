@@ -19,6 +19,7 @@ c_int, c_void_p, c_float, c_int64, c_int32 = ctypes.c_int, ctypes.c_void_p, ctyp
 MAX_GROUPS = 4
 QD_MAX, QD_COUNTERS = 16, 2048
 LOSS_MAX_BUMPS = 32
+MERGE_MAX_CAND = 2048     # DRN_MERGE_MAX_CAND: K + Vc * kv candidates one drn_merge_moments wavefront stages in LDS
 
 
 class DrnError(RuntimeError):
@@ -147,6 +148,8 @@ SIGNATURES = {
     "drn_gate_gather_fwd": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                             c_int, c_int, c_int, c_void_p],
     "drn_pool_props": [c_void_p, c_void_p],
+    "drn_merge_moments": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

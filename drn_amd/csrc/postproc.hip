@@ -260,3 +260,124 @@ extern "C" int drn_select_moments(const float* det, const float* scores, const i
                                                            index, n);
   return drn_launch_status("drn_select_moments");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The best K moments of a sentence across videos, streamed chunk by chunk (Grounder.search): one wavefront per sentence merges one
+// chunk's select_moments outputs into the sentence's running state, in place.  The K state entries and the chunk's Vc * kv entries
+// are staged in LDS -- everything the state holds is read before anything is written -- then, as in nms_pick_loop, up to K times
+// the best candidate still alive is found with a wave reduction and struck out.  The order is total: score descending (the stored
+// floats), video position ascending, rank ascending (and the staging slot, for a video listed twice), so the result does not
+// depend on how the videos were cut into chunks.  No candidates: padded chunk slots (vids outside [0, Nv)), the fallback moment
+// (index < 0, score 1: it would top every ranking), entries past n[p], scores that are not finite.
+#define MM_MAX_CAND DRN_MERGE_MAX_CAND
+
+// does candidate (s1, v1, r1, i1) come before (s2, v2, r2, i2)?  i < 0: no candidate
+__device__ __forceinline__ bool mm_before(float s1, int v1, int r1, int i1, float s2, int v2, int r2, int i2) {
+  if (i1 < 0) return false;
+  if (i2 < 0) return true;
+  if (s1 != s2) return s1 > s2;
+  if (v1 != v2) return v1 < v2;
+  if (r1 != r2) return r1 < r2;
+  return i1 < i2;
+}
+
+__global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restrict__ seg, const float* __restrict__ score,
+                                                           const int* __restrict__ level, const int* __restrict__ index,
+                                                           const int* __restrict__ n_in, int Vc, int kv, const int* __restrict__ vids,
+                                                           int Nv, int K, int first, const int* __restrict__ first_dev,
+                                                           float* st_seg, float* st_score, int* st_video, int* st_level, int* st_rank,
+                                                           int* st_n) {
+  __shared__ float c_score[MM_MAX_CAND], c_seg[MM_MAX_CAND * 2];
+  __shared__ int c_video[MM_MAX_CAND], c_level[MM_MAX_CAND], c_rank[MM_MAX_CAND];
+  __shared__ unsigned char alive[MM_MAX_CAND];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const long o = (long)s * K;
+  const bool fresh = first_dev ? first_dev[0] != 0 : first != 0;
+  const int ns = fresh ? 0 : min(max(st_n[s], 0), K);
+  const int N = K + Vc * kv;                  // (<= MM_MAX_CAND: checked by the host)
+  for (int i = lane; i < N; i += 64) {
+    bool ok;
+    long src = 0;
+    int v = -1, r = 0;
+    if (i < K) {
+      ok = i < ns;
+      src = o + i;
+      if (ok) { v = st_video[src]; r = st_rank[src]; }
+    } else {
+      const int e = i - K, slot = e / kv;
+      r = e - slot * kv;
+      const long p = (long)s * Vc + slot;
+      v = vids[slot];
+      src = p * kv + r;
+      ok = v >= 0 && v < Nv && r < n_in[p] && index[src] >= 0;
+    }
+    float sc = 0.f;
+    if (ok) {
+      sc = i < K ? st_score[src] : score[src];
+      ok = isfinite(sc);
+    }
+    if (ok) {
+      c_score[i] = sc;
+      c_video[i] = v;
+      c_rank[i] = r;
+      c_seg[i * 2 + 0] = i < K ? st_seg[src * 2 + 0] : seg[src * 2 + 0];
+      c_seg[i * 2 + 1] = i < K ? st_seg[src * 2 + 1] : seg[src * 2 + 1];
+      c_level[i] = i < K ? st_level[src] : level[src];
+    }
+    alive[i] = ok;
+  }
+  __syncthreads();
+  int np = 0;
+  for (; np < K; ++np) {
+    float bs = 0.f;
+    int bv = 0, br = 0, bi = -1;
+    for (int i = lane; i < N; i += 64)
+      if (alive[i] && mm_before(c_score[i], c_video[i], c_rank[i], i, bs, bv, br, bi)) {
+        bs = c_score[i]; bv = c_video[i]; br = c_rank[i]; bi = i;
+      }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) {
+      const float os = __shfl_xor(bs, w, 64);
+      const int ov = __shfl_xor(bv, w, 64), orr = __shfl_xor(br, w, 64), oi = __shfl_xor(bi, w, 64);
+      if (mm_before(os, ov, orr, oi, bs, bv, br, bi)) { bs = os; bv = ov; br = orr; bi = oi; }
+    }
+    if (bi < 0) break;                        // nothing left
+    if (lane == 0) {
+      st_seg[(o + np) * 2 + 0] = c_seg[bi * 2 + 0];
+      st_seg[(o + np) * 2 + 1] = c_seg[bi * 2 + 1];
+      st_score[o + np] = bs;
+      st_video[o + np] = bv;
+      st_level[o + np] = c_level[bi];
+      st_rank[o + np] = br;
+      alive[bi] = 0;
+    }
+    __syncthreads();
+  }
+  for (int p = np + lane; p < K; p += 64) {
+    st_seg[(o + p) * 2 + 0] = 0.f;
+    st_seg[(o + p) * 2 + 1] = 0.f;
+    st_score[o + p] = 0.f;
+    st_video[o + p] = -1;
+    st_level[o + p] = -1;
+    st_rank[o + p] = -1;
+  }
+  if (lane == 0) st_n[s] = np;
+}
+
+extern "C" int drn_merge_moments(const float* seg, const float* score, const int32_t* level, const int32_t* index, const int32_t* n,
+                                 int S, int Vc, int kv, const int32_t* vids, int Nv, int K, int first, const int32_t* first_dev,
+                                 float* st_seg, float* st_score, int32_t* st_video, int32_t* st_level, int32_t* st_rank, int32_t* st_n,
+                                 void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(seg && score && level && index && n && vids && st_seg && st_score && st_video && st_level && st_rank && st_n,
+                "drn_merge_moments: null pointer");
+  DRN_CHECK_ARG(S > 0 && Vc > 0 && Nv >= 0, "drn_merge_moments: bad args (S = %d sentences, Vc = %d chunk slots, Nv = %d videos)", S, Vc, Nv);
+  DRN_CHECK_ARG(K >= 1, "drn_merge_moments: K = %d, at least 1 moment per sentence", K);
+  DRN_CHECK_ARG(kv >= 1, "drn_merge_moments: kv = %d, at least 1 slot per pair", kv);
+  DRN_CHECK_ARG((long)K + (long)Vc * kv <= MM_MAX_CAND, "drn_merge_moments: K + Vc * kv = %ld candidates per sentence (max %d)",
+                (long)K + (long)Vc * kv, MM_MAX_CAND);
+  DRN_CHECK_ARG((long)S * Vc * kv <= 0x7fffffffL, "drn_merge_moments: more than 2^31 chunk entries");
+  merge_moments_kernel<<<S, 64, 0, (hipStream_t)stream>>>(seg, score, level, index, n, Vc, kv, vids, Nv, K, first, first_dev, st_seg,
+                                                          st_score, st_video, st_level, st_rank, st_n);
+  return drn_launch_status("drn_merge_moments");
+}

@@ -3,7 +3,13 @@
 Grounder.ground = mainModel.forward_heads_shared (the query-independent part of the forward -- prop_fc above all -- once per VIDEO,
 however many sentences ask about it) -> the device post-processor (drn_postprocess) -> the evaluator's temporal NMS on the device
 (drn_select_moments: utils/evaluate_utils.py:91-107,186-212), which hands back the surviving moments themselves, best first.
-Nothing crosses to the host until the caller asks (Moments.tolist)."""
+Nothing crosses to the host until the caller asks (Moments.tolist).
+
+Grounder.search answers "in which video, and where": S sentences against every video of a resident FeatureStore.  The sentences are
+encoded ONCE; the store is walked in chunks of equal shape (store.gather with a device index buffer -> forward_heads_shared with the
+encoded gates, pair p = (sentence p // Vc, chunk slot p % Vc) -> post-processor -> drn_select_moments), and drn_merge_moments keeps
+each sentence's best moments across the chunks on the device (Hits)."""
+import numpy as np
 import torch
 
 from . import ops
@@ -23,10 +29,35 @@ class Moments(object):
     def __len__(self):
         return int(self.n.shape[0])
 
+    def fields(self):
+        return self.seg, self.score, self.level, self.index, self.n
+
     def tolist(self):
         """Per query [[start, end, score], ...], the first n[q] entries: one host copy per field."""
         n, seg, score = self.n.tolist(), self.seg.tolist(), self.score.tolist()
         return [[[seg[q][i][0], seg[q][i][1], score[q][i]] for i in range(n[q])] for q in range(len(n))]
+
+
+class Hits(object):
+    """The best moments of S sentences across the videos of a store, on the device, best first: seg (S, k, 2) [start, end] as fractions
+    of the video, score (S, k), video (S, k) int32 position in the store, level (S, k) int32 pyramid level, rank (S, k) int32 position
+    of the moment among its (sentence, video) pair's NMS survivors, n (S,) int32 valid entries per sentence (entries past n are
+    0 / -1).  Order: score descending, then video position ascending, then rank ascending.  A video in which the model found no
+    candidate contributes nothing (the fallback moment of Moments is no hit), so n may be 0."""
+    __slots__ = ("seg", "score", "video", "level", "rank", "n")
+
+    def __init__(self, seg, score, video, level, rank, n):
+        self.seg, self.score, self.video, self.level, self.rank, self.n = seg, score, video, level, rank, n
+
+    def __len__(self):
+        return int(self.n.shape[0])
+
+    def tolist(self, names=None):
+        """Per sentence [[video, start, end, score], ...], the first n[s] entries: one host copy per field.  video: the store position,
+        or names[position] (names: e.g. store.names)."""
+        n, seg, score, video = self.n.tolist(), self.seg.tolist(), self.score.tolist(), self.video.tolist()
+        name = (lambda v: v) if names is None else (lambda v: names[v])
+        return [[[name(video[s][i]), seg[s][i][0], seg[s][i][1], score[s][i]] for i in range(n[s])] for s in range(len(n))]
 
 
 def group_by_video(names):
@@ -59,7 +90,13 @@ class Grounder(object):
     signatures are kept, none is evicted, a further one runs eagerly.  The graph holds raw pointers to the re-laid weight copies
     (functional.packed), which are re-made when a parameter's version moves: every graph carries the address and _version of each
     parameter and the WeightCopies epoch, and a call under another stamp captures again.  Running
-    statistics changed IN PLACE keep their address and are re-read by the scale/shift launches of every replay.  `captures` counts the captures made."""
+    statistics changed IN PLACE keep their address and are re-read by the scale/shift launches of every replay.  `captures` counts the captures made.
+    search() shares all of this: its per-chunk body is one more signature among the max_graphs."""
+
+    # Pairs (sentence, video) per chunk that search() allows itself by default.  A CHOICE, not a measurement: conv0's input g0 holds
+    # T * (D + 256) elements per pair -- 2.1 MiB at T = 256, D = 4096 in bf16 -- so 512 pairs are 1.1 GiB of g0, and the trunk's
+    # activations a small multiple of that: a few GiB of a 288 GiB device, beside a store that is meant to fill most of it.
+    SEARCH_PAIR_BUDGET = 512
 
     def __init__(self, model, top_k=5, nms_overlap=0.45, fused=False, graph=False, max_graphs=4):
         if int(top_k) < 1:
@@ -100,8 +137,7 @@ class Grounder(object):
         if self.model.training or any(t is not None and i != 4 and not t.is_cuda for i, t in enumerate(args)):
             return self._ground(*args)                          # (refused there, as without the graph)
         sig = self.signature(*args)
-        ent = self._graphs.get(sig)
-        if ent is None and len(self._graphs) >= self.max_graphs:
+        if sig not in self._graphs and len(self._graphs) >= self.max_graphs:
             return self._ground(*args)
         if video_index is not None:
             if video_index.dim() != 1 or video_index.is_floating_point():
@@ -110,45 +146,58 @@ class Grounder(object):
                 V = int(props_features.shape[0])
                 if int(video_index.min()) < 0 or int(video_index.max()) >= V:
                     raise DrnError("Grounder: video_index outside [0, %d)" % V)
-        stamp = self._stamp()
-        if ent is not None and ent.stamp != stamp:
-            del self._graphs[sig]
-            ent = None
-        if ent is None:
-            ent = self._capture(args, sig)
-            ent.stamp = self._stamp()
-            self._graphs[sig] = ent
-        else:
+        dev = props_features.device
+        ent, fresh = self._entry(sig, lambda *a: self._ground(*a).fields(), dev, lambda: [
+            None if t is None else (t.to(device=dev, dtype=torch.int32) if i == 4 else t).clone().contiguous() for i, t in enumerate(args)])
+        if not fresh:
             for dst, src in zip(ent.inputs, args):
                 if dst is not None and src is not dst and src.data_ptr() != dst.data_ptr():
                     dst.copy_(src, non_blocking=src.is_cuda)
             ent.graph.replay()
         return Moments(*[t.clone() for t in ent.out])
 
-    def _capture(self, args, sig):
-        """Static buffers <- this call's inputs, one warm run on the capture stream (lazy module loads, weight copies, workspaces), then
-        the capture: everything on ONE stream, so the graph is one linear chain."""
+    def _entry(self, sig, run, dev, make_inputs):
+        """The captured graph of `sig` under today's stamp -> (entry, captured just now): one whose stamp has moved is dropped and
+        captured again.  (None, False) when the signature is new and max_graphs are held: the caller runs eagerly."""
+        ent = self._graphs.get(sig)
+        if ent is None and len(self._graphs) >= self.max_graphs:
+            return None, False
+        if ent is not None and ent.stamp != self._stamp():
+            del self._graphs[sig]
+            ent = None
+        if ent is not None:
+            return ent, False
+        ent = self._capture(run, make_inputs(), dev)
+        ent.stamp = self._stamp()
+        self._graphs[sig] = ent
+        return ent, True
+
+    def _capture(self, run, inputs, dev):
+        """run(*inputs) -> tuple of tensors, on the static buffers `inputs`: one warm run on the capture stream (lazy module loads,
+        weight copies, workspaces), then the capture: everything on ONE stream, so the graph is one linear chain; one replay, so that
+        the static outputs hold this call's result."""
         from .graph import capture_graph
         ent = _GroundGraph()
-        dev = args[2].device
-        ent.inputs = [None if t is None else (t.to(device=dev, dtype=torch.int32) if i == 4 else t).clone().contiguous()
-                      for i, t in enumerate(args)]
+        ent.inputs = inputs
         ent.stream = torch.cuda.Stream(device=dev)
         ent.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(ent.stream):
-            self._ground(*ent.inputs)
+            run(*ent.inputs)
         torch.cuda.current_stream().wait_stream(ent.stream)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with capture_graph(g, ent.stream):
-            mom = self._ground(*ent.inputs)
+            ent.out = tuple(run(*ent.inputs))
         ent.graph = g
-        ent.out = (mom.seg, mom.score, mom.level, mom.index, mom.n)
         self.captures += 1
         g.replay()
         return ent
 
     def _ground(self, query_tokens, query_length, props_features, props_start_end, video_index=None):
+        return Moments(*self._select(self.top_k, query_tokens, query_length, props_features, props_start_end, video_index))
+
+    def _select(self, k, *forward_args, **forward_kw):
+        """forward_heads_shared(...) -> device post-processor -> ops.select_moments(k): the five Moments fields."""
         from . import functional as DF
         model = self.model
         selector = model.fcos.box_selector_test
@@ -159,11 +208,101 @@ class Grounder(object):
         selector.device_only = True
         try:
             with DF.fused_eval(self.fused):
-                locations, box_cls, box_reg, iou_scores = model.forward_heads_shared(query_tokens, query_length, props_features,
-                                                                                     props_start_end, video_index)
+                locations, box_cls, box_reg, iou_scores = model.forward_heads_shared(*forward_args, **forward_kw)
             dd = selector(locations, box_cls, box_reg, iou_scores)
         finally:
             selector.device_only = was
         if isinstance(dd, list):
             raise DrnError("Grounder: the post-processor has no flat device path for this model (min_size != 0?)")
-        return Moments(*ops.select_moments(dd.det, dd.scores, dd.counts, self.nms_overlap, self.top_k))
+        return ops.select_moments(dd.det, dd.scores, dd.counts, self.nms_overlap, k)
+
+    # -- search across the videos of a store -----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def search(self, query_tokens, query_length, store, top_k=None, per_video=1, videos=None, chunk=None, T=None):
+        """The best top_k (default: the Grounder's) moments of each of the S sentences across the videos of `store` (a FeatureStore on
+        the GPU in the model's compute dtype) -> Hits.  per_video: at most that many moments of one video compete (the first per_video
+        survivors of the pair's temporal NMS at nms_overlap).  videos: names or store positions to search, default the whole store.
+        T: the padded proposal count, default the largest count among the searched videos (padded proposal positions are treated as
+        ground() treats them).  chunk: videos per step.  Its default is the largest value that keeps a step within
+        SEARCH_PAIR_BUDGET (sentence, video) pairs and top_k + chunk * per_video within drn_merge_moments' LDS cap -- the pair budget
+        is a choice made from the memory of conv0's input at D = 4096, not a measurement.
+        The sentences are encoded once.  Every chunk has the same shape (the last one is padded with position -1, whose pairs the
+        ranking skips) and runs store.gather -> forward_heads_shared(gates=, query_index=, video_index=) -> post-processor ->
+        select_moments -> merge_moments; the chunks' positions are uploaded in one copy before the first.  There is no host
+        synchronisation, here or in the loop: only Hits.tolist waits.  A video without a candidate contributes nothing.
+        graph=True: that per-chunk body is captured once per (store, S, chunk, T, per_video, top_k) as one linear hipGraph and replayed
+        per chunk -- the chunk's positions and the first-chunk word are copied into its static buffers outside the graph -- under
+        ground()'s stamp, max_graphs and `captures` rules; Hits' fields are copies of the static state."""
+        from ._lib import MERGE_MAX_CAND
+        model = self.model
+        K = self.top_k if top_k is None else int(top_k)
+        kv = int(per_video)
+        if model.training:
+            raise DrnError("Grounder.search is inference only: call model.eval() first")
+        for t in (query_tokens, query_length):
+            if not t.is_cuda:
+                raise DrnError("Grounder.search runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
+        if not store.feats.is_cuda:
+            raise DrnError("Grounder.search needs a store on the GPU (this one lives on %s); there is no CPU fallback" % store.device)
+        if store.dtype != model.compute_dtype:
+            raise DrnError("Grounder.search: the store holds %s, the model computes in %s" % (store.dtype, model.compute_dtype))
+        if kv < 1 or K < 1:
+            raise DrnError("Grounder.search: per_video and top_k must be at least 1 (got %d, %d)" % (kv, K))
+        ids = np.arange(len(store), dtype=np.int32) if videos is None else store.ids_of(videos).numpy()
+        if ids.size == 0:
+            raise DrnError("Grounder.search: no videos to search")
+        if int(ids.min()) < 0 or int(ids.max()) >= len(store):
+            raise DrnError("Grounder.search: video positions outside [0, %d)" % len(store))
+        S = int(query_tokens.shape[0])
+        if S < 1:
+            raise DrnError("Grounder.search: no sentences")
+        cap = (MERGE_MAX_CAND - K) // kv
+        if cap < 1:
+            raise DrnError("Grounder.search: top_k + per_video = %d exceeds the %d candidates one ranking step holds" % (K + kv, MERGE_MAX_CAND))
+        if chunk is None:
+            chunk = min(cap, max(1, self.SEARCH_PAIR_BUDGET // S), int(ids.size))
+        Vc = int(chunk)
+        if Vc < 1 or Vc > cap:
+            raise DrnError("Grounder.search: chunk must be in [1, %d] for top_k = %d, per_video = %d" % (cap, K, kv))
+        T = int(store.nprops[ids].max()) if T is None else int(T)
+        dev = store.feats.device
+        nchunks = -(-int(ids.size) // Vc)
+        # ONE upload for the whole walk: the chunks' store positions, padded with -1, then the first-chunk words 1, 0, 0, ...
+        plan = np.full(nchunks * Vc + nchunks, -1, dtype=np.int32)
+        plan[:ids.size] = ids
+        plan[nchunks * Vc:] = 0
+        plan[nchunks * Vc] = 1
+        plan = torch.from_numpy(plan).pin_memory().to(dev, non_blocking=True)
+        vids, first = plan[:nchunks * Vc].view(nchunks, Vc), plan[nchunks * Vc:].view(nchunks, 1)
+        gates = [g.contiguous() for g in model.encode_query(query_tokens, query_length)]
+        pair = torch.arange(S * Vc, dtype=torch.int32, device=dev)
+        pair_q, pair_v = torch.div(pair, Vc, rounding_mode="floor"), torch.remainder(pair, Vc)
+
+        def body(vid, flag, pq, pv, seg, score, video, level, rank, n, *g):
+            feats, pse, _ = store.gather(vid, T=T)
+            mom = self._select(kv, None, None, feats, pse, video_index=pv, query_index=pq, gates=list(g))
+            return ops.merge_moments(mom, vid, len(store), (seg, score, video, level, rank, n), flag)
+
+        ent = None
+        if self.graph:
+            sig = ("search", store, S, Vc, T, kv, K)             # (the key keeps the store, whose addresses the graph holds, alive)
+            ent, _ = self._entry(sig, body, dev, lambda: [vids[0].clone(), first[0].clone(), pair_q, pair_v]
+                                 + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates])
+        if ent is None:
+            state = ops.merge_state(S, K, dev)
+            for c in range(nchunks):
+                body(vids[c], first[c], pair_q, pair_v, *(state + tuple(gates)))
+            return Hits(*state)
+        for dst, src in zip(ent.inputs[10:], gates):
+            dst.copy_(src)
+        for c in range(nchunks):
+            ent.inputs[0].copy_(vids[c])
+            ent.inputs[1].copy_(first[c])
+            ent.graph.replay()
+        return Hits(*[t.clone() for t in ent.out])
+
+
+def search(model, query_tokens, query_length, store, top_k=5, nms_overlap=0.45, fused=False, **kw):
+    """Grounder(model, top_k, nms_overlap, fused).search(query_tokens, query_length, store, **kw) for a one-off question; keep a
+    Grounder to search by graph replay."""
+    return Grounder(model, top_k=top_k, nms_overlap=nms_overlap, fused=fused).search(query_tokens, query_length, store, **kw)

@@ -116,6 +116,28 @@ def select_moments(preds, k, overlap):
     return [order[i] for i in picks[:max(int(k), 0)]]
 
 
+def merge_moments(per_pair_lists, video_ids, k, state=None):
+    """The best k moments of ONE sentence across videos, best first: the host twin of drn_merge_moments (ops.merge_moments, the
+    ranking of Grounder.search), for callers that hold host records.
+    per_pair_lists[i]: the moments of the (sentence, video video_ids[i]) pair, best first (Moments.tolist()'s rows or select_moments'
+    picks): [start, end, score] or [start, end, score, index] records; a moment's rank is its position in that list.
+    Dropped: pairs whose video id is None or negative (padding), records that are None (padding), records with index < 0 (the
+    fallback moment of a pair without candidates: (0, 1) with score 1 is no hit, and it would top every ranking) and records whose
+    score is not finite.  Order: score descending, then video id ascending, then rank ascending -- total, so merging the videos in
+    chunks (state = the result of the chunks before) gives the list that merging them at once gives.
+    -> [[video, start, end, score, rank], ...], at most k."""
+    cand = [list(r) for r in (state or [])]
+    for vid, moments in zip(video_ids, per_pair_lists):
+        if vid is None or vid < 0:
+            continue
+        for rank, r in enumerate(moments):
+            if r is None or (len(r) > 3 and r[3] < 0) or not np.isfinite(r[2]):
+                continue
+            cand.append([vid, r[0], r[1], r[2], rank])
+    cand.sort(key=lambda c: (-c[3], c[0], c[4]))
+    return cand[:max(int(k), 0)]
+
+
 def recall_from_first_hits(first_hits, ious, topks):
     """accs in run_evaluate's order (for iou: for topk) from the per-query first-hit positions of ops.eval_recall:
     first_hits (n_queries, len(ious)) integer array."""

@@ -192,26 +192,44 @@ class mainModel(nn.Module):
         DF.flush_bn_counters()
         return res
 
-    def forward_heads_shared(self, query_tokens, query_length, props_features, props_start_end, video_index=None):
+    def forward_heads_shared(self, query_tokens, query_length, props_features, props_start_end, video_index=None, query_index=None,
+                             gates=None):
         """Inference without a ground truth, for Q queries over V <= Q videos: -> (locations, box_cls, box_reg, iou_scores), the
         per-level head outputs of the Q (query, video) pairs -- no loss, no targets, no BatchNorm counter or buffer touched.
         props_features (V, T, D), props_start_end (V, T, 2|3); video_index: (Q,) integer tensor, query q reads video
         video_index[q] (None: Q = V, query q reads video q).  The part of the forward that does not depend on the query -- the cast,
         prop_fc (63 % of the forward's FLOPs at the benchmarked shape) and the position embedding -- runs once per VIDEO
         (prepare_input(split_gate=True)); the query gate is applied per (query, video) pair by ops.gate_gather_fwd, which writes
-        conv0's (Q, T, D+P) input; the trunk is the one every forward runs.  Eval mode under torch.no_grad() only."""
+        conv0's (Q, T, D+P) input; the trunk is the one every forward runs.  Eval mode under torch.no_grad() only.
+        gates: already encoded gate tensors (encode_query's three (S, C_l) fp32 tensors), as forward_front takes them: the query
+        encoder does not run and query_tokens / query_length are not read (they may be None).
+        query_index: (Q,) integer tensor, pair q uses gate row query_index[q] of the S encoded sentences at every level (None: Q = S,
+        pair q uses row q), so that S sentences over V videos are encoded once, not once per pair.  The rows are gathered with
+        index_select.  A host index outside [0, S) raises before any launch; a device index is not read back (the caller answers
+        for its range)."""
         if self.training:
             raise DrnError("forward_heads_shared is inference only: call model.eval() first")
         if torch.is_grad_enabled():
             raise DrnError("forward_heads_shared is inference only: run it under torch.no_grad()")
-        for t in (props_features, props_start_end, query_tokens):
+        for t in (props_features, props_start_end) + ((query_tokens,) if gates is None else tuple(gates)):
             if not t.is_cuda:
                 raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
         V, T, _ = props_features.shape
-        prep = self.prepare_input(props_features, props_start_end, split_gate=True)
-        gates = self.encode_query(query_tokens, query_length)
-        Q = int(gates[0].shape[0])
         dev = props_features.device
+        qidx = None
+        if query_index is not None:
+            if query_index.dim() != 1 or query_index.is_floating_point():
+                raise DrnError("forward_heads_shared: query_index must be a 1-d integer tensor")
+            S = int(gates[0].shape[0]) if gates is not None else int(query_tokens.shape[0])
+            if not query_index.is_cuda and query_index.numel() and (int(query_index.min()) < 0 or int(query_index.max()) >= S):
+                raise DrnError("forward_heads_shared: query_index outside [0, %d)" % S)
+            qidx = query_index.to(device=dev, dtype=torch.int64)
+        prep = self.prepare_input(props_features, props_start_end, split_gate=True)
+        if gates is None:
+            gates = self.encode_query(query_tokens, query_length)
+        if qidx is not None:
+            gates = [g.index_select(0, qidx) for g in gates]
+        Q = int(gates[0].shape[0])
         vid_host = None
         if video_index is None:
             if Q != V:

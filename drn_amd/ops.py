@@ -1171,6 +1171,47 @@ def select_moments(det, scores, counts, overlap, k):
     return seg, score, level, index, n
 
 
+def merge_state(S, k, device):
+    """The running best-k state of S sentences for merge_moments: (seg (S, k, 2), score (S, k), video (S, k) int32, level (S, k) int32,
+    rank (S, k) int32, n (S,) int32), uninitialised -- the first merge (first=True) never reads it."""
+    S, k = int(S), max(int(k), 0)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
+    return (torch.empty((S, k, 2), dtype=torch.float32, device=device), torch.empty((S, k), dtype=torch.float32, device=device),
+            i32(S, k), i32(S, k), i32(S, k), i32(S))
+
+
+def merge_moments(moments, vids, num_videos, state, first):
+    """One chunk of a search across videos (drn_merge_moments): `moments` = select_moments' (seg, score, level, index, n) for
+    P = S * Vc (sentence, chunk slot) pairs, pair p = (p // Vc, p % Vc); vids (Vc,) int32 on the device = the slots' store positions
+    (outside [0, num_videos): a padded slot, skipped); state = merge_state(S, k, ...), updated IN PLACE to each sentence's best k of
+    (its state entries + the chunk's entries that are no fallback moment and have a finite score), ordered by score descending, video
+    position ascending, rank ascending.  first: True / False, or a (1,) int32 DEVICE tensor read by the launch (non-zero: the state
+    coming in is ignored) -- what a captured graph needs to serve every chunk.  No host synchronisation."""
+    seg, score, level, index, n = moments
+    st_seg, st_score, st_video, st_level, st_rank, st_n = state
+    _need_gpu(seg, score, level, index, n, vids, *state)
+    P, kv = (int(x) for x in score.shape)
+    S, k = (int(x) for x in st_score.shape)
+    Vc = int(vids.numel())
+    flag = first if torch.is_tensor(first) else None
+    if flag is not None:
+        _need_gpu(flag)
+    for name, t, dt, shape in (("seg", seg, torch.float32, (P, kv, 2)), ("score", score, torch.float32, (P, kv)),
+                               ("level", level, torch.int32, (P, kv)), ("index", index, torch.int32, (P, kv)), ("n", n, torch.int32, (P,)),
+                               ("vids", vids, torch.int32, (Vc,)), ("state seg", st_seg, torch.float32, (S, k, 2)),
+                               ("state score", st_score, torch.float32, (S, k)), ("state video", st_video, torch.int32, (S, k)),
+                               ("state level", st_level, torch.int32, (S, k)), ("state rank", st_rank, torch.int32, (S, k)),
+                               ("state n", st_n, torch.int32, (S,)), ("first", flag, torch.int32, (1,))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.DrnError("merge_moments: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    if S * Vc != P:
+        raise _lib.DrnError("merge_moments: %d pairs are not %d sentences x %d chunk slots" % (P, S, Vc))
+    check(lib().drn_merge_moments(_p(seg), _p(score), _p(level), _p(index), _p(n), S, Vc, kv, _p(vids), int(num_videos), k,
+                                  0 if flag is not None else int(bool(first)), _p(flag), _p(st_seg), _p(st_score), _p(st_video),
+                                  _p(st_level), _p(st_rank), _p(st_n), _stream()), "drn_merge_moments")
+    return state
+
+
 # ---------------------------------------------------------------------------------------------
 # query-encoder glue (drn_amd/csrc/qenc.hip)
 # ---------------------------------------------------------------------------------------------

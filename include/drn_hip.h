@@ -522,6 +522,21 @@ int drn_eval_recall(const float* det, const float* scores, const int32_t* counts
  * wavefront per clip, no host synchronisation. */
 int drn_select_moments(const float* det, const float* scores, const int32_t* counts, int B, int nlevels, int rows_per_clip,
                        double overlap, int K, float* seg, float* score, int32_t* level, int32_t* index, int32_t* n, void* stream);
+/* The best K moments of S sentences ACROSS videos, streamed chunk by chunk: one call merges one chunk's drn_select_moments outputs --
+ * P = S * Vc pairs of kv slots each, pair p = (sentence p / Vc, chunk slot p % Vc), vids [Vc] = the slots' positions in a store of Nv
+ * videos -- into the running state of each sentence, in place: st_seg [S][K][2], st_score [S][K], st_video [S][K] (store position),
+ * st_level [S][K], st_rank [S][K] (the moment's position among its pair's survivors), st_n [S]; slots past st_n are written 0 / -1.
+ * Candidates of sentence s: its st_n[s] state entries and the entries r < n[p] of its pairs, EXCEPT pairs whose vids[slot] is outside
+ * [0, Nv) (the padded tail of the last chunk), fallback entries (index < 0: a video without a candidate is no hit) and entries whose
+ * score is not finite.  Order, total, so that the result does not depend on how the videos were cut into chunks: score descending
+ * (the stored floats compared, nothing recomputed), then video position ascending, then rank ascending.
+ * The incoming state is ignored (never read) when `first` is non-zero; first_dev, when not NULL, is a DEVICE word read instead of
+ * `first`, so that a captured graph serves the first chunk and the later ones.  One wavefront per sentence stages the K + Vc * kv
+ * candidates in LDS: K + Vc * kv <= DRN_MERGE_MAX_CAND, refused otherwise.  No host synchronisation. */
+#define DRN_MERGE_MAX_CAND 2048
+int drn_merge_moments(const float* seg, const float* score, const int32_t* level, const int32_t* index, const int32_t* n, int S, int Vc,
+                      int kv, const int32_t* vids, int Nv, int K, int first, const int32_t* first_dev, float* st_seg, float* st_score,
+                      int32_t* st_video, int32_t* st_level, int32_t* st_rank, int32_t* st_n, void* stream);
 
 /* ---- query-encoder glue (drn_amd/csrc/qenc.hip; model/language_module.py:17-63), all fp32 ----------------------
  * Word embedding lookup written time-major (L, B, E) and its dense gradient (row padding_idx stays zero). */
