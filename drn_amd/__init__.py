@@ -5,3 +5,4 @@ hand-written HIP kernels behind the C-ABI in include/drn_hip.h (libdrn_hip.so).
 __version__ = "0.1.0"
 from .grounding import Grounder, Hits, Moments, group_by_video, search  # noqa: E402,F401
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
+from .index import SearchIndex  # noqa: E402,F401

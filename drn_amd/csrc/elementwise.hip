@@ -862,6 +862,101 @@ extern "C" int drn_gate_gather_fwd(const void* z, int ld_z, const float* gate, i
   return drn_launch_status("drn_gate_gather_fwd");
 }
 
+// ---------------------------------------------------------------- query gate over a packed, projected index (drn_amd.SearchIndex)
+// rows (n_rows, C+P): per proposal [prop_fc output | position embedding], video v owning rows prop_off[v] .. prop_off[v+1]; pad_row:
+// what the same launches gave for a padded proposal.  Pair p = (sentence pq[p], chunk slot pv[p]), video v = vids[pv[p]]:
+//   src = (0 <= v < Nv && t < prop_off[v+1] - prop_off[v]) ? prop_off[v] + t : pad_row
+//   out[p,t,c] = rows[src,c] * gate[pq[p],c] for c < C (gate_gather_fwd_kernel's arithmetic, statement for statement) and
+//   out[p,t,C+j] = rows[src,C+j], copied as loaded.
+// Writes Q*T*(C+P) elements and reads a video's rows once per sentence (from L2 / Infinity Cache after the first): a store-bandwidth
+// kernel.  One WAVE owns U rows of one pair x 64 column vectors (1 KiB of a row); consecutive waves take neighbouring column chunks of
+// the same rows.  Pair, video, proposal range and source rows are wave-uniform: pq / pv / vids / prop_off are looked up once
+// per U rows (scalar loads), and a lane loads its gate vector once for its U rows.  pq and a slot are clamped for the loads (a slot
+// outside [0, Vc) reads the pad row), src is kept inside the table.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void gate_gather_packed_kernel(const T* __restrict__ rows, int ld_rows, int n_rows, int pad_row,
+                                                                 const int* __restrict__ prop_off, int Nv, const float* __restrict__ gate,
+                                                                 int ldg, int S, const int* __restrict__ pq, const int* __restrict__ pv,
+                                                                 const int* __restrict__ vids, int Vc, T* __restrict__ out, int ld_out,
+                                                                 int Q, int L, int C, int P) {
+  constexpr int N = V16<T>::N;
+  const int cvec = C / N, nvec = (C + P) / N;
+  const int ncc = (nvec + 63) / 64, ngr = (L + U - 1) / U;
+  const long total = (long)Q * ngr * ncc;
+  const int lane = threadIdx.x & 63;
+  const long wave0 = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (long w = wave0; w < total; w += (long)gridDim.x * 4) {
+    const int cc = (int)(w % ncc);
+    const long rg = w / ncc;
+    const int p = (int)(rg / ngr), t0 = (int)(rg % ngr) * U;
+    const int q = min(max(pq[p], 0), S - 1), slot = pv[p];
+    const int vd = (slot >= 0 && slot < Vc) ? vids[slot] : -1;
+    int base = 0, cnt = 0;
+    if (vd >= 0 && vd < Nv) {
+      base = prop_off[vd];
+      cnt = prop_off[vd + 1] - base;
+    }
+    const int v = cc * 64 + lane;
+    if (v >= nvec) continue;
+    const bool gated = v < cvec;
+    const int c0 = v * N;
+    typename V16<T>::raw_t r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int t = min(t0 + u, L - 1);
+      const int src = min(max(t < cnt ? base + t : pad_row, 0), n_rows - 1);
+      r[u] = V16<T>::ldraw(rows + (long)src * ld_rows + c0);
+    }
+    float g[N];
+    if (gated) {
+      const float* gp = gate + (long)q * ldg + c0;
+#pragma unroll
+      for (int k = 0; k < N; ++k) g[k] = gp[k];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int t = t0 + u;
+      if (t >= L) break;
+      T* op = out + ((long)p * L + t) * ld_out + c0;
+      if (gated) {
+        float x[N];
+        V16<T>::cvt(r[u], x);
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] *= g[k];
+        V16<T>::store(op, x);
+      } else {
+        *(typename V16<T>::raw_t*)op = r[u];
+      }
+    }
+  }
+}
+extern "C" int drn_gate_gather_packed(const void* rows, int ld_rows, int n_rows, int pad_row, const int32_t* prop_off, int Nv,
+                                      const float* gate, int ldg, int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv,
+                                      const int32_t* vids, int Vc, void* out, int ld_out, int Q, int L, int C, int P, int dtype,
+                                      void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(rows && prop_off && gate && pq && pv && vids && out, "drn_gate_gather_packed: null pointer");
+  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0,
+                "drn_gate_gather_packed: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d)", n_rows, pad_row, Nv,
+                S, Vc, Q, L, C, P);
+  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL, "drn_gate_gather_packed: more than 2^31 rows");
+  if (pq_host)
+    for (int p = 0; p < Q; ++p)
+      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "drn_gate_gather_packed: pair %d reads sentence %d of %d", p, (int)pq_host[p], S);
+  DISPATCH_DT(dtype, "drn_gate_gather_packed", {
+    constexpr int N = V16<T>::N;
+    DRN_CHECK_ARG(C % N == 0 && P % N == 0 && ld_rows % N == 0 && ld_out % N == 0 && ldg % 4 == 0 &&
+                      ((((uintptr_t)rows) | ((uintptr_t)out) | ((uintptr_t)gate)) & 15) == 0,
+                  "drn_gate_gather_packed: C / P / ld must be 16-byte multiples");
+    DRN_CHECK_ARG(ld_rows >= C + P && ld_out >= C + P && ldg >= C, "drn_gate_gather_packed: a row stride is shorter than its row");
+    constexpr int U = 8;
+    const long waves = (long)Q * cdiv(L, U) * cdiv((C + P) / N, 64);
+    gate_gather_packed_kernel<T, U><<<ew_blocks(waves * 64, 256, 8192), 256, 0, (hipStream_t)stream>>>(
+        (const T*)rows, ld_rows, n_rows, pad_row, prop_off, Nv, gate, ldg, S, pq, pv, vids, Vc, (T*)out, ld_out, Q, L, C, P);
+  });
+  return drn_launch_status("drn_gate_gather_packed");
+}
+
 // ---------------------------------------------------------------- query-gate backward
 // forward was G[s,t,c] = act[s,t,c] * gate[s,c].  Here:
 //   dC[s,t,c] = (add ? add[s,t,c] : 0) + dG[s,t,c] * gate[s,c]        dgate[s,c] = sum_t dG[s,t,c] * act[s,t,c]

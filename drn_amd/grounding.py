@@ -197,9 +197,11 @@ class Grounder(object):
         return Moments(*self._select(self.top_k, query_tokens, query_length, props_features, props_start_end, video_index))
 
     def _select(self, k, *forward_args, **forward_kw):
-        """forward_heads_shared(...) -> device post-processor -> ops.select_moments(k): the five Moments fields."""
+        """forward_heads_shared(...) -> device post-processor -> ops.select_moments(k): the five Moments fields.  entry=: the name of
+        another model method of the same return value (forward_heads_packed)."""
         from . import functional as DF
         model = self.model
+        forward = getattr(model, forward_kw.pop("entry", "forward_heads_shared"))
         selector = model.fcos.box_selector_test
         if model.fcos.head.cls_logits.weight.shape[0] != 1:
             raise DrnError("Grounder: the device post-processor serves one foreground channel (fcos_num_class = 2); this model has %d"
@@ -208,7 +210,7 @@ class Grounder(object):
         selector.device_only = True
         try:
             with DF.fused_eval(self.fused):
-                locations, box_cls, box_reg, iou_scores = model.forward_heads_shared(*forward_args, **forward_kw)
+                locations, box_cls, box_reg, iou_scores = forward(*forward_args, **forward_kw)
             dd = selector(locations, box_cls, box_reg, iou_scores)
         finally:
             selector.device_only = was
@@ -232,9 +234,16 @@ class Grounder(object):
         synchronisation, here or in the loop: only Hits.tolist waits.  A video without a candidate contributes nothing.
         graph=True: that per-chunk body is captured once per (store, S, chunk, T, per_video, top_k) as one linear hipGraph and replayed
         per chunk -- the chunk's positions and the first-chunk word are copied into its static buffers outside the graph -- under
-        ground()'s stamp, max_graphs and `captures` rules; Hits' fields are copies of the static state."""
+        ground()'s stamp, max_graphs and `captures` rules; Hits' fields are copies of the static state.
+        store may be a drn_amd.SearchIndex built from the store for this model: every keyword means what it means above and the Hits
+        are the same bit for bit, but a chunk's front is ONE launch (drn_gate_gather_packed reads the projected rows) instead of
+        store.gather, the cast, the prop_fc GEMM, the position embedding and the gate pass.  A stale index (index.is_current(model) is
+        False) raises before any launch."""
         from ._lib import MERGE_MAX_CAND
+        from .index import SearchIndex
         model = self.model
+        indexed = isinstance(store, SearchIndex)
+        resident = store.rows if indexed else store.feats
         K = self.top_k if top_k is None else int(top_k)
         kv = int(per_video)
         if model.training:
@@ -242,12 +251,14 @@ class Grounder(object):
         for t in (query_tokens, query_length):
             if not t.is_cuda:
                 raise DrnError("Grounder.search runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
-        if not store.feats.is_cuda:
+        if not resident.is_cuda:
             raise DrnError("Grounder.search needs a store on the GPU (this one lives on %s); there is no CPU fallback" % store.device)
         if store.dtype != model.compute_dtype:
             raise DrnError("Grounder.search: the store holds %s, the model computes in %s" % (store.dtype, model.compute_dtype))
         if kv < 1 or K < 1:
             raise DrnError("Grounder.search: per_video and top_k must be at least 1 (got %d, %d)" % (kv, K))
+        if indexed:
+            store.check(model, "Grounder.search")
         ids = np.arange(len(store), dtype=np.int32) if videos is None else store.ids_of(videos).numpy()
         if ids.size == 0:
             raise DrnError("Grounder.search: no videos to search")
@@ -265,7 +276,7 @@ class Grounder(object):
         if Vc < 1 or Vc > cap:
             raise DrnError("Grounder.search: chunk must be in [1, %d] for top_k = %d, per_video = %d" % (cap, K, kv))
         T = int(store.nprops[ids].max()) if T is None else int(T)
-        dev = store.feats.device
+        dev = resident.device
         nchunks = -(-int(ids.size) // Vc)
         # ONE upload for the whole walk: the chunks' store positions, padded with -1, then the first-chunk words 1, 0, 0, ...
         plan = np.full(nchunks * Vc + nchunks, -1, dtype=np.int32)
@@ -279,8 +290,11 @@ class Grounder(object):
         pair_q, pair_v = torch.div(pair, Vc, rounding_mode="floor"), torch.remainder(pair, Vc)
 
         def body(vid, flag, pq, pv, seg, score, video, level, rank, n, *g):
-            feats, pse, _ = store.gather(vid, T=T)
-            mom = self._select(kv, None, None, feats, pse, video_index=pv, query_index=pq, gates=list(g))
+            if indexed:
+                mom = self._select(kv, store, vid, pq, pv, list(g), T, entry="forward_heads_packed")
+            else:
+                feats, pse, _ = store.gather(vid, T=T)
+                mom = self._select(kv, None, None, feats, pse, video_index=pv, query_index=pq, gates=list(g))
             return ops.merge_moments(mom, vid, len(store), (seg, score, video, level, rank, n), flag)
 
         ent = None

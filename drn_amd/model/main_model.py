@@ -255,6 +255,29 @@ class mainModel(nn.Module):
         ops.gate_gather_fwd(prep.Z, D, gate0.contiguous(), pos, ld_pos, vid, V, g0, D + P, Q, T, D, P, code, vid_host=vid_host)
         return self._trunk_heads(g0, gates)
 
+    def forward_heads_packed(self, index, vids, pair_q, pair_v, gates, T):
+        """forward_heads_shared for Q (sentence, video) pairs whose query-independent front is already in a drn_amd.SearchIndex:
+        pair p is sentence pair_q[p] of the S encoded `gates` over the video at store position vids[pair_v[p]], its first T proposals
+        (the pad row past them, and for a slot or position out of range).  vids (Vc,), pair_q / pair_v (Q,): contiguous int32 on the
+        device, read by the launch itself.  ONE launch (ops.gate_gather_packed) writes conv0's (Q, T, Dp+P) input -- no pooling, no
+        cast, no prop_fc, no position embedding, no level-0 index_select -- and the trunk is the one every forward runs, with the
+        level-1.. gates gathered by pair_q.  A stale index raises before any launch.  Eval mode under torch.no_grad() only."""
+        if self.training:
+            raise DrnError("forward_heads_packed is inference only: call model.eval() first")
+        if torch.is_grad_enabled():
+            raise DrnError("forward_heads_packed is inference only: run it under torch.no_grad()")
+        index.check(self, "forward_heads_packed")
+        for t in (index.rows, vids, pair_q, pair_v) + tuple(gates):
+            if not t.is_cuda:
+                raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
+        pad = index.Dp - index.D
+        gate0 = F.pad(gates[0], (0, pad)) if pad else gates[0]
+        g0 = torch.empty((int(pair_q.numel()), int(T), index.Dp + index.P), dtype=index.dtype, device=index.rows.device)
+        ops.gate_gather_packed(index.rows, index.pad_row, index.prop_off, gate0.contiguous(), pair_q, pair_v, vids, g0, int(T), index.Dp,
+                               index.P, ops.dtype_code(index.rows))
+        qidx = pair_q.long()
+        return self._trunk_heads(g0, [None] + [g.index_select(0, qidx) for g in gates[1:]])
+
     def forward(self, query_tokens, query_length, props_features, props_start_end, gt_start_end, props_num=None,
                 num_frames=None):
         g0, gates = self.forward_front(query_tokens, query_length, props_features, props_start_end)

@@ -621,6 +621,33 @@ def gate_gather_fwd(z, ld_z, gate, pos, ld_pos, vid, V, out, ld_out, Q, L, C, P,
                                     dtype, _stream()), "drn_gate_gather_fwd")
 
 
+def gate_gather_packed(rows, pad_row, prop_off, gate, pq, pv, vids, out, L, C, P, dtype, pq_host=None):
+    """out[p, t, :C] = rows[src, :C] * gate[pq[p]] and out[p, t, C:C+P] = rows[src, C:C+P] with v = vids[pv[p]] and
+    src = prop_off[v] + t while t is below video v's proposal count, else pad_row (drn_gate_gather_packed): conv0's whole (Q, L, C+P)
+    input in one launch from a packed index (drn_amd.SearchIndex: rows (n_rows, >= C+P), prop_off (Nv + 1,) int32 on the device).
+    pq, pv: (Q,) int32 on the device, vids: (Vc,) int32 store positions on the device; a slot or a position out of range reads the
+    pad row.  pq_host: an optional host copy of pq (int32, contiguous) -- given, an entry outside [0, S) raises before the launch;
+    without it pq is the caller's to keep in range.  P may be 0."""
+    _need_gpu(rows, prop_off, gate, pq, pv, vids, out)
+    Q = int(pq.numel())
+    for name, t, n in (("pq", pq, Q), ("pv", pv, Q), ("vids", vids, int(vids.numel())), ("prop_off", prop_off, int(prop_off.numel()))):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n or n < 1:
+            raise _lib.DrnError("gate_gather_packed: %s must be a contiguous 1-d int32 tensor (pq and pv of the same length)" % name)
+    if rows.dim() != 2 or rows.stride(1) != 1 or gate.dim() != 2 or gate.stride(1) != 1 or gate.dtype != torch.float32:
+        raise _lib.DrnError("gate_gather_packed: rows must be (n_rows, C + P) and gate (S, C) float32, both with unit column stride")
+    if out.dim() != 3 or tuple(out.shape[:2]) != (Q, L) or not out.is_contiguous() or out.dtype != rows.dtype:
+        raise _lib.DrnError("gate_gather_packed: out must be a contiguous (%d, %d, >= C + P) tensor of the rows' dtype" % (Q, L))
+    host = None
+    if pq_host is not None:
+        if pq_host.is_cuda or pq_host.dtype != torch.int32 or not pq_host.is_contiguous() or pq_host.numel() != Q:
+            raise _lib.DrnError("gate_gather_packed: pq_host must be a contiguous int32 host tensor of %d entries" % Q)
+        host = ctypes.c_void_p(pq_host.data_ptr())
+    _timed("gate_gather_packed", 0, lambda: check(lib().drn_gate_gather_packed(
+        _p(rows), rows.stride(0), int(rows.shape[0]), int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(gate), gate.stride(0),
+        int(gate.shape[0]), _p(pq), host, _p(pv), _p(vids), int(vids.numel()), _p(out), int(out.shape[2]), Q, L, C, P, dtype, _stream()),
+        "drn_gate_gather_packed"))
+
+
 def pool_props_lds_rows(B, D, dtype):
     """Rows of one video the LDS path of drn_pool_props holds for B clips of D elements (0: the element-wise path)."""
     return int(lib().drn_pool_props_lds_rows(int(B), int(D), int(dtype)))

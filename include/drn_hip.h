@@ -252,6 +252,19 @@ int drn_gate_fwd(const void* z, int ld_z, const float* gate, int ldg, void* out,
 int drn_gate_gather_fwd(const void* z, int ld_z, const float* gate, int ldg, const void* pos, int ld_pos, const int32_t* vid,
                         const int32_t* vid_host /*host, may be NULL*/, int V, void* out, int ld_out, int Q, int L, int C, int P,
                         int dtype, void* stream);
+/* The same gate + position columns read from a PACKED, projected index (drn_amd.SearchIndex) instead of a chunk's (V, L, .) buffers:
+ * rows (n_rows, C + P) holds per proposal [prop_fc output | position embedding], video v owning rows prop_off[v] .. prop_off[v+1]
+ * (prop_off: Nv + 1 device int32), and pad_row is the row of a padded proposal.  Pair p < Q is (sentence pq[p], chunk slot pv[p]),
+ * its video v = vids[pv[p]] (vids: Vc device int32 store positions):
+ *   src = (0 <= v < Nv && t < prop_off[v+1] - prop_off[v]) ? prop_off[v] + t : pad_row          for t < L
+ *   out[p*L+t][c] = dtype(float(rows[src][c]) * gate[pq[p]][c]) for c < C      out[p*L+t][C+j] = rows[src][C+j] for j < P
+ * One launch writes conv0's whole (Q, L, C+P) input; pq, pv and vids are read on the device at every launch (a captured graph serves
+ * every chunk).  A slot outside [0, Vc) or a video outside [0, Nv) reads the pad row; pq is clamped to [0, S) for the loads and is
+ * the caller's to keep in range.  pq_host: an optional host copy of pq -- when given, an entry outside [0, S) is DRN_ERR_ARG before
+ * anything is launched.  P may be 0. */
+int drn_gate_gather_packed(const void* rows, int ld_rows, int n_rows, int pad_row, const int32_t* prop_off, int Nv, const float* gate,
+                           int ldg, int S, const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv,
+                           const int32_t* vids, int Vc, void* out, int ld_out, int Q, int L, int C, int P, int dtype, void* stream);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */

@@ -1,0 +1,160 @@
+#!/usr/bin/env python
+"""Measures Grounder.search on a resident FeatureStore and on a SearchIndex built from it, on the MI355X -> profiles/search_bench.json:
+
+  search   ms per search of S in {1, 8} sentences against 64 videos (120 rows x 4096, bf16; bench_store.py's store), T = 256 and
+           T = 32, four ways in one process, interleaved, median over rounds: the store path and the index path, each eager and by
+           graph replay.  Host clock around windows of searches that end in a device synchronise; the default chunk (all 64 videos in
+           one step).  The two paths' Hits are compared field for field at every shape;
+  build    ms per SearchIndex.build of that store (synchronised), and nbytes of the store and of the index;
+  kernel   drn_gate_gather_packed alone at the search's largest step (512 pairs) and at 64 pairs: launch-inclusive microseconds per
+           call over ~0.3 s windows and the bytes it WRITES (Q T (C + P) elements) over that time.
+
+    python scripts/bench_search.py [--out profiles/search_bench.json] [--rounds 5]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+D, NV = 4096, 64
+STATE = ("seg", "score", "video", "level", "rank", "n")
+
+
+def make_model():
+    from drn_amd.model import mainModel
+    from drn_amd.utils.synthetic import VOCAB_SIZE, as_namespace, default_cfg, seeded_state_dict
+    m = mainModel(VOCAB_SIZE, as_namespace(default_cfg("C3D", D, 3)), compute_dtype=torch.bfloat16)
+    m.load_state_dict(seeded_state_dict(m, 0))
+    m = m.to("cuda:0").eval()
+    with torch.no_grad():                                  # a classifier that passes most locations: every pair has candidates
+        m.fcos.head.cls_logits.bias.fill_(0.5)
+    return m
+
+
+def sentences(S, seed):
+    from drn_amd.utils.synthetic import synthetic_batch
+    tok, qlen = synthetic_batch(S, 32, 64, seed=seed)[:2]
+    return tok.to("cuda:0"), qlen.to("cuda:0")
+
+
+def window(fn, n):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / n
+
+
+def bench_search(model, store, index, T, S, rounds, window_s=0.3):
+    from drn_amd import Grounder
+    tok, qlen = sentences(S, 7)
+    eager, graphed = Grounder(model, top_k=10), Grounder(model, top_k=10, graph=True)
+    variants = {"store_eager": lambda: eager.search(tok, qlen, store, per_video=2),
+                "index_eager": lambda: eager.search(tok, qlen, index, per_video=2),
+                "store_graph": lambda: graphed.search(tok, qlen, store, per_video=2),
+                "index_graph": lambda: graphed.search(tok, qlen, index, per_video=2)}
+    hits = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    same = {k: all(torch.equal(getattr(hits[k], f), getattr(hits["store_eager"], f)) for f in STATE) for k in variants}
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():                     # interleaved: a drift of the clock or the host hits all variants alike
+            times[k].append(window(fn, reps[k]))
+    res = {"T": T, "S": S, "videos": len(store), "pairs_per_step": S * len(store), "top_k": 10, "per_video": 2, "rounds": rounds,
+           "hits_equal_store_eager": same, "hits_min_n": int(hits["store_eager"].n.min()), "graph_captures": graphed.captures, "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    return res
+
+
+def bench_build(model, store, rounds):
+    from drn_amd import SearchIndex
+    index = SearchIndex.build(model, store)
+    ts = [window(lambda: SearchIndex.build(model, store), 1) for _ in range(max(rounds, 3))]
+    return index, {"ms_per_build_median": statistics.median(ts), "ms_per_build_rounds": ts, "videos": len(store),
+                   "proposals": int(store.nprops.sum()), "store_nbytes": store.nbytes, "index_nbytes": index.nbytes,
+                   "row_width": index.Dp + index.P}
+
+
+def bench_kernel(index, T, Q, rounds, window_s=0.3):
+    """Launch-inclusive: back-to-back launches issued from Python on one stream, device events around each window.  Two output
+    buffers in turn.  What is counted is what the kernel WRITES; it also reads every source row once per pair (mostly from L2 /
+    Infinity Cache: 64 videos' rows are 143 MB at T = 256, 18 MB at T = 32)."""
+    from drn_amd import ops
+    dev = index.rows.device
+    S = Q // NV
+    gate = torch.randn(S, index.Dp, device=dev)
+    pair = torch.arange(Q, dtype=torch.int32, device=dev)
+    pq, pv = torch.div(pair, NV, rounding_mode="floor"), torch.remainder(pair, NV)
+    vids = torch.arange(NV, dtype=torch.int32, device=dev)
+    outs = [torch.empty((Q, T, index.Dp + index.P), dtype=index.dtype, device=dev) for _ in range(2)]
+
+    def run(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            ops.gate_gather_packed(index.rows, index.pad_row, index.prop_off, gate, pq, pv, vids, outs[i & 1], T, index.Dp, index.P, ops.BF16)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    run(10)
+    reps = max(20, int(window_s / (run(20) * 1e-6)))
+    ts = [run(reps) for _ in range(rounds)]
+    written = outs[0].numel() * outs[0].element_size()
+    us = statistics.median(ts)
+    return {"Q": Q, "T": T, "C": index.Dp, "P": index.P, "dtype": "bf16", "launches_per_window": reps, "bytes_written": written,
+            "us_median": us, "us_rounds": ts, "written_bytes_per_s": written / (us * 1e-6),
+            "note": "launch-inclusive; written bytes over that time.  At Q = 64, T = 32 the output (18 MB) fits the Infinity Cache: "
+                    "that figure is not an HBM rate"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search_bench.json"))
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    from bench_store import build_store
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, store and index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s",
+                      "clock": "host clock around searches ending in a device synchronise; device events for the kernel windows"},
+           "build": [], "search": [], "kernel": []}
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        index, b = bench_build(model, store, args.rounds)
+        res["build"].append(dict(b, T=T))
+        print(json.dumps({"build": res["build"][-1]}), flush=True)
+        for S in (1, 8):
+            res["search"].append(bench_search(model, store, index, T, S, args.rounds))
+            print(json.dumps({"search": res["search"][-1]}), flush=True)
+            json.dump(res, open(args.out, "w"), indent=1)
+        for Q in (512, 64):
+            res["kernel"].append(bench_kernel(index, T, Q, args.rounds))
+            print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+        json.dump(res, open(args.out, "w"), indent=1)
+        del store, index
+        torch.cuda.empty_cache()
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
