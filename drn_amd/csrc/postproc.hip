@@ -281,20 +281,30 @@ __device__ __forceinline__ bool mm_before(float s1, int v1, int r1, int i1, floa
   return i1 < i2;
 }
 
-__global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restrict__ seg, const float* __restrict__ score,
-                                                           const int* __restrict__ level, const int* __restrict__ index,
-                                                           const int* __restrict__ n_in, int Vc, int kv, const int* __restrict__ vids,
-                                                           int Nv, int K, int first, const int* __restrict__ first_dev,
-                                                           float* st_seg, float* st_score, int* st_video, int* st_level, int* st_rank,
-                                                           int* st_n) {
-  __shared__ float c_score[MM_MAX_CAND], c_seg[MM_MAX_CAND * 2];
-  __shared__ int c_video[MM_MAX_CAND], c_level[MM_MAX_CAND], c_rank[MM_MAX_CAND];
-  __shared__ unsigned char alive[MM_MAX_CAND];
-  const int s = blockIdx.x, lane = threadIdx.x;
+// LDS of one merging wavefront: the staged candidates' score, segment, video position, level and rank, and who is still alive.
+struct MmLds {
+  float *score, *seg;
+  int *video, *level, *rank;
+  unsigned char* alive;
+};
+#define MM_LDS_DECL(L)                                                                   \
+  __shared__ float mm_score[MM_MAX_CAND], mm_seg[MM_MAX_CAND * 2];                       \
+  __shared__ int mm_video[MM_MAX_CAND], mm_level[MM_MAX_CAND], mm_rank[MM_MAX_CAND];     \
+  __shared__ unsigned char mm_alive[MM_MAX_CAND];                                        \
+  const MmLds L = {mm_score, mm_seg, mm_video, mm_level, mm_rank, mm_alive}
+
+// What both merge kernels run for sentence s: stage its K state entries and the cnt * kv entries of its cnt pairs, then pick.
+// pair_of(slot, p, v): the chunk's pair index and the store position of the sentence's slot-th pair.  K + cnt * kv <= MM_MAX_CAND is
+// the caller's to guarantee.
+template <typename PairOf>
+__device__ __forceinline__ void mm_merge_sentence(const MmLds c, const float* __restrict__ seg, const float* __restrict__ score,
+                                                  const int* __restrict__ level, const int* __restrict__ index,
+                                                  const int* __restrict__ n_in, const int s, const int cnt, const int kv, const int Nv,
+                                                  const int K, const bool fresh, float* st_seg, float* st_score, int* st_video,
+                                                  int* st_level, int* st_rank, int* st_n, const int lane, PairOf pair_of) {
   const long o = (long)s * K;
-  const bool fresh = first_dev ? first_dev[0] != 0 : first != 0;
   const int ns = fresh ? 0 : min(max(st_n[s], 0), K);
-  const int N = K + Vc * kv;                  // (<= MM_MAX_CAND: checked by the host)
+  const int N = K + cnt * kv;
   for (int i = lane; i < N; i += 64) {
     bool ok;
     long src = 0;
@@ -306,8 +316,8 @@ __global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restri
     } else {
       const int e = i - K, slot = e / kv;
       r = e - slot * kv;
-      const long p = (long)s * Vc + slot;
-      v = vids[slot];
+      long p;
+      pair_of(slot, p, v);
       src = p * kv + r;
       ok = v >= 0 && v < Nv && r < n_in[p] && index[src] >= 0;
     }
@@ -317,14 +327,14 @@ __global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restri
       ok = isfinite(sc);
     }
     if (ok) {
-      c_score[i] = sc;
-      c_video[i] = v;
-      c_rank[i] = r;
-      c_seg[i * 2 + 0] = i < K ? st_seg[src * 2 + 0] : seg[src * 2 + 0];
-      c_seg[i * 2 + 1] = i < K ? st_seg[src * 2 + 1] : seg[src * 2 + 1];
-      c_level[i] = i < K ? st_level[src] : level[src];
+      c.score[i] = sc;
+      c.video[i] = v;
+      c.rank[i] = r;
+      c.seg[i * 2 + 0] = i < K ? st_seg[src * 2 + 0] : seg[src * 2 + 0];
+      c.seg[i * 2 + 1] = i < K ? st_seg[src * 2 + 1] : seg[src * 2 + 1];
+      c.level[i] = i < K ? st_level[src] : level[src];
     }
-    alive[i] = ok;
+    c.alive[i] = ok;
   }
   __syncthreads();
   int np = 0;
@@ -332,8 +342,8 @@ __global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restri
     float bs = 0.f;
     int bv = 0, br = 0, bi = -1;
     for (int i = lane; i < N; i += 64)
-      if (alive[i] && mm_before(c_score[i], c_video[i], c_rank[i], i, bs, bv, br, bi)) {
-        bs = c_score[i]; bv = c_video[i]; br = c_rank[i]; bi = i;
+      if (c.alive[i] && mm_before(c.score[i], c.video[i], c.rank[i], i, bs, bv, br, bi)) {
+        bs = c.score[i]; bv = c.video[i]; br = c.rank[i]; bi = i;
       }
 #pragma unroll
     for (int w = 32; w > 0; w >>= 1) {
@@ -343,13 +353,13 @@ __global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restri
     }
     if (bi < 0) break;                        // nothing left
     if (lane == 0) {
-      st_seg[(o + np) * 2 + 0] = c_seg[bi * 2 + 0];
-      st_seg[(o + np) * 2 + 1] = c_seg[bi * 2 + 1];
+      st_seg[(o + np) * 2 + 0] = c.seg[bi * 2 + 0];
+      st_seg[(o + np) * 2 + 1] = c.seg[bi * 2 + 1];
       st_score[o + np] = bs;
       st_video[o + np] = bv;
-      st_level[o + np] = c_level[bi];
+      st_level[o + np] = c.level[bi];
       st_rank[o + np] = br;
-      alive[bi] = 0;
+      c.alive[bi] = 0;
     }
     __syncthreads();
   }
@@ -362,6 +372,23 @@ __global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restri
     st_rank[o + p] = -1;
   }
   if (lane == 0) st_n[s] = np;
+}
+
+__global__ __launch_bounds__(64) void merge_moments_kernel(const float* __restrict__ seg, const float* __restrict__ score,
+                                                           const int* __restrict__ level, const int* __restrict__ index,
+                                                           const int* __restrict__ n_in, int Vc, int kv, const int* __restrict__ vids,
+                                                           int Nv, int K, int first, const int* __restrict__ first_dev,
+                                                           float* st_seg, float* st_score, int* st_video, int* st_level, int* st_rank,
+                                                           int* st_n) {
+  MM_LDS_DECL(c);
+  const int s = blockIdx.x;
+  const bool fresh = first_dev ? first_dev[0] != 0 : first != 0;
+  // (K + Vc * kv <= MM_MAX_CAND: checked by the host)
+  mm_merge_sentence(c, seg, score, level, index, n_in, s, Vc, kv, Nv, K, fresh, st_seg, st_score, st_video, st_level, st_rank, st_n,
+                    threadIdx.x, [&](int slot, long& p, int& v) {
+                      p = (long)s * Vc + slot;
+                      v = vids[slot];
+                    });
 }
 
 extern "C" int drn_merge_moments(const float* seg, const float* score, const int32_t* level, const int32_t* index, const int32_t* n,
@@ -380,4 +407,48 @@ extern "C" int drn_merge_moments(const float* seg, const float* score, const int
   merge_moments_kernel<<<S, 64, 0, (hipStream_t)stream>>>(seg, score, level, index, n, Vc, kv, vids, Nv, K, first, first_dev, st_seg,
                                                           st_score, st_video, st_level, st_rank, st_n);
   return drn_launch_status("drn_merge_moments");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same ranking for a chunk of P pairs in ANY assignment to sentences (Grounder.search(candidates=)): sentence s owns the pairs
+// [pair_off[s], pair_off[s + 1]) of the chunk and pair p is the video at store position pair_video[p].  Nothing read from pair_off is
+// trusted: the offsets are clamped to [0, P], a negative or decreasing range is empty and a range longer than the LDS holds is cut,
+// so a bad table ranks the wrong pairs but indexes nothing outside LDS or the inputs.  A sentence without a pair in the chunk re-ranks
+// its own state, which is the identity.
+__global__ __launch_bounds__(64) void merge_moments_ragged_kernel(const float* __restrict__ seg, const float* __restrict__ score,
+                                                                  const int* __restrict__ level, const int* __restrict__ index,
+                                                                  const int* __restrict__ n_in, int P, int kv,
+                                                                  const int* __restrict__ pair_video, const int* __restrict__ pair_off,
+                                                                  int Nv, int K, int first, const int* __restrict__ first_dev,
+                                                                  float* st_seg, float* st_score, int* st_video, int* st_level,
+                                                                  int* st_rank, int* st_n) {
+  MM_LDS_DECL(c);
+  const int s = blockIdx.x;
+  const bool fresh = first_dev ? first_dev[0] != 0 : first != 0;
+  const int lo = min(max(pair_off[s], 0), P), hi = min(max(pair_off[s + 1], 0), P);
+  const int cnt = min(max(hi - lo, 0), (MM_MAX_CAND - K) / kv);          // (K + kv <= MM_MAX_CAND: checked by the host)
+  mm_merge_sentence(c, seg, score, level, index, n_in, s, cnt, kv, Nv, K, fresh, st_seg, st_score, st_video, st_level, st_rank, st_n,
+                    threadIdx.x, [&](int slot, long& p, int& v) {
+                      p = lo + slot;                                     // (< lo + cnt <= hi <= P)
+                      v = pair_video[p];
+                    });
+}
+
+extern "C" int drn_merge_moments_ragged(const float* seg, const float* score, const int32_t* level, const int32_t* index,
+                                        const int32_t* n, int S, int P, int kv, const int32_t* pair_video, const int32_t* pair_off, int Nv,
+                                        int K, int first, const int32_t* first_dev, float* st_seg, float* st_score, int32_t* st_video,
+                                        int32_t* st_level, int32_t* st_rank, int32_t* st_n, void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(seg && score && level && index && n && pair_video && pair_off && st_seg && st_score && st_video && st_level &&
+                    st_rank && st_n,
+                "drn_merge_moments_ragged: null pointer");
+  DRN_CHECK_ARG(S > 0 && P > 0 && Nv >= 0, "drn_merge_moments_ragged: bad args (S = %d sentences, P = %d pairs, Nv = %d videos)", S, P, Nv);
+  DRN_CHECK_ARG(K >= 1, "drn_merge_moments_ragged: K = %d, at least 1 moment per sentence", K);
+  DRN_CHECK_ARG(kv >= 1, "drn_merge_moments_ragged: kv = %d, at least 1 slot per pair", kv);
+  DRN_CHECK_ARG((long)K + (long)kv <= MM_MAX_CAND, "drn_merge_moments_ragged: K + kv = %ld candidates for one pair (max %d)",
+                (long)K + (long)kv, MM_MAX_CAND);
+  DRN_CHECK_ARG((long)P * kv <= 0x7fffffffL, "drn_merge_moments_ragged: more than 2^31 chunk entries");
+  merge_moments_ragged_kernel<<<S, 64, 0, (hipStream_t)stream>>>(seg, score, level, index, n, P, kv, pair_video, pair_off, Nv, K, first,
+                                                                 first_dev, st_seg, st_score, st_video, st_level, st_rank, st_n);
+  return drn_launch_status("drn_merge_moments_ragged");
 }

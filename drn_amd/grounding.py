@@ -8,7 +8,13 @@ Nothing crosses to the host until the caller asks (Moments.tolist).
 Grounder.search answers "in which video, and where": S sentences against every video of a resident FeatureStore.  The sentences are
 encoded ONCE; the store is walked in chunks of equal shape (store.gather with a device index buffer -> forward_heads_shared with the
 encoded gates, pair p = (sentence p // Vc, chunk slot p % Vc) -> post-processor -> drn_select_moments), and drn_merge_moments keeps
-each sentence's best moments across the chunks on the device (Hits)."""
+each sentence's best moments across the chunks on the device (Hits).
+
+Grounder.search(candidates=) looks for each sentence only in that sentence's own list of videos: plan_pairs cuts the ragged list of
+(sentence, video) pairs into steps of equal shape, the same fronts and trunk run on a step's pairs, and drn_merge_moments_ragged ranks
+them.  Grounder.ground_stored is the one-video-per-sentence case without a ranking: ground() on videos that are already resident."""
+import collections
+
 import numpy as np
 import torch
 
@@ -72,6 +78,83 @@ def group_by_video(names):
     return unique, torch.tensor(index, dtype=torch.int64)
 
 
+PairPlan = collections.namedtuple("PairPlan", "vids pair_q pair_v pair_video pair_off")
+
+
+def _pairs_csr(candidates, num_videos):
+    """candidates -> (ids int64, offsets int64 (S + 1,)): sentence s lists ids[offsets[s]:offsets[s + 1]].  Accepted: a sequence of S
+    sequences of store positions, or the CSR pair itself as a 2-TUPLE of numpy arrays / host tensors (ids, offsets).  A position
+    outside [0, num_videos) raises."""
+    is_array = lambda c: isinstance(c, np.ndarray) or torch.is_tensor(c)
+    try:
+        if isinstance(candidates, tuple) and len(candidates) == 2 and all(is_array(c) for c in candidates):
+            ids, off = (np.asarray(c).astype(np.int64).reshape(-1) for c in candidates)
+            if off.size < 1 or off[0] != 0 or off[-1] != ids.size or (np.diff(off) < 0).any():
+                raise DrnError("plan_pairs: offsets must rise from 0 to the number of ids (%d)" % ids.size)
+        else:
+            lists = [np.asarray(c if is_array(c) else list(c)).astype(np.int64).reshape(-1) for c in candidates]
+            off = np.concatenate([[0], np.cumsum([l.size for l in lists])]).astype(np.int64)
+            ids = np.concatenate(lists + [np.zeros(0, np.int64)])
+    except (TypeError, ValueError):
+        raise DrnError("plan_pairs: candidates must be sequences of store positions (resolve names with ids_of), or (ids, offsets)")
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= int(num_videos)):
+        raise DrnError("plan_pairs: video positions outside [0, %d)" % int(num_videos))
+    return ids, off
+
+
+def plan_pairs(candidates, num_videos, pairs, slots, cap):
+    """Cut a ragged list of (sentence, video) pairs into chunks of ONE shape -> PairPlan of int32 arrays with a leading chunk axis:
+    vids (C, slots) store positions, -1 past the chunk's videos; pair_q (C, pairs) the pair's sentence; pair_v (C, pairs) its slot in
+    vids; pair_video (C, pairs) its store position; pair_off (C, S + 1): sentence s owns the pairs [pair_off[s], pair_off[s + 1]) of
+    the chunk.  Padded pairs sit after pair_off[S] with pair_video -1, pair_q 0 and pair_v 0 (in range for both fronts: whatever they
+    compute there is outside every sentence's range).
+    candidates: S sequences of store positions, or the CSR pair (ids, offsets) as a 2-tuple of arrays.  A sentence's list is a SET
+    (duplicates are dropped) and may be empty.  The distinct pairs are ordered by (video, sentence) -- a video's pairs lie together, so
+    the store path projects each video as few times as possible -- and cut greedily: a new chunk starts when the next pair would make
+    it more than `pairs` pairs, more than `slots` distinct videos, or more than `cap` pairs of that pair's sentence.  Within a chunk the
+    pairs are then sorted stably by sentence.  No pairs at all: zero chunks.  Pure numpy; deterministic."""
+    pairs, slots, cap = int(pairs), int(slots), int(cap)
+    if pairs < 1 or slots < 1 or cap < 1:
+        raise DrnError("plan_pairs: pairs, slots and cap must be at least 1 (got %d, %d, %d)" % (pairs, slots, cap))
+    ids, off = _pairs_csr(candidates, num_videos)
+    S = int(off.size) - 1
+    if S < 1:
+        raise DrnError("plan_pairs: no sentences")
+    return _plan(_distinct_pairs(ids, off), S, pairs, slots, cap)
+
+
+def _distinct_pairs(ids, off):
+    """The distinct (sentence, video) pairs of a CSR list as keys video * S + sentence, ascending: ordered by (video, sentence)."""
+    S = int(off.size) - 1
+    return np.unique(ids * S + np.repeat(np.arange(S, dtype=np.int64), np.diff(off)))
+
+
+def _plan(key, S, pairs, slots, cap):
+    vid, sen = key // S, key % S
+    cuts = [0]
+    if key.size > pairs or np.unique(vid).size > slots or (key.size and int(np.bincount(sen).max()) > cap):
+        n, nv, last, per = 0, 0, -1, {}
+        for i, (v, q) in enumerate(zip(vid.tolist(), sen.tolist())):
+            if n + 1 > pairs or nv + (v != last) > slots or per.get(q, 0) + 1 > cap:
+                cuts.append(i)
+                n, nv, last, per = 0, 0, -1, {}
+            n, nv, last = n + 1, nv + (v != last), v
+            per[q] = per.get(q, 0) + 1
+    # (otherwise everything fits one chunk, which is what the greedy walk would find)
+    C = len(cuts) if key.size else 0
+    cuts.append(int(key.size))
+    plan = PairPlan(np.full((C, slots), -1, np.int32), np.zeros((C, pairs), np.int32), np.zeros((C, pairs), np.int32),
+                    np.full((C, pairs), -1, np.int32), np.zeros((C, S + 1), np.int32))
+    for c in range(C):
+        v, q = vid[cuts[c]:cuts[c + 1]], sen[cuts[c]:cuts[c + 1]]
+        order = np.argsort(q, kind="stable")
+        uniq, slot = np.unique(v, return_inverse=True)
+        plan.vids[c, :uniq.size] = uniq
+        plan.pair_q[c, :q.size], plan.pair_v[c, :q.size], plan.pair_video[c, :q.size] = q[order], slot.reshape(-1)[order], v[order]
+        plan.pair_off[c, 1:] = np.cumsum(np.bincount(q, minlength=S))
+    return plan
+
+
 class _GroundGraph(object):
     """One captured grounding path: the static inputs, the hipGraph, the static Moments fields and the stamp it was captured under."""
     __slots__ = ("inputs", "graph", "out", "stamp", "stream")
@@ -91,7 +174,8 @@ class Grounder(object):
     (functional.packed), which are re-made when a parameter's version moves: every graph carries the address and _version of each
     parameter and the WeightCopies epoch, and a call under another stamp captures again.  Running
     statistics changed IN PLACE keep their address and are re-read by the scale/shift launches of every replay.  `captures` counts the captures made.
-    search() shares all of this: its per-chunk body is one more signature among the max_graphs."""
+    search() shares all of this: its per-chunk body is one more signature among the max_graphs, and that of search(candidates=)
+    another.  ground_stored() runs eagerly whatever `graph` says."""
 
     # Pairs (sentence, video) per chunk that search() allows itself by default.  A CHOICE, not a measurement: conv0's input g0 holds
     # T * (D + 256) elements per pair -- 2.1 MiB at T = 256, D = 4096 in bf16 -- so 512 pairs are 1.1 GiB of g0, and the trunk's
@@ -220,7 +304,8 @@ class Grounder(object):
 
     # -- search across the videos of a store -----------------------------------------------------------------------------------------
     @torch.no_grad()
-    def search(self, query_tokens, query_length, store, top_k=None, per_video=1, videos=None, chunk=None, T=None):
+    def search(self, query_tokens, query_length, store, top_k=None, per_video=1, videos=None, chunk=None, T=None, candidates=None,
+               pairs=None):
         """The best top_k (default: the Grounder's) moments of each of the S sentences across the videos of `store` (a FeatureStore on
         the GPU in the model's compute dtype) -> Hits.  per_video: at most that many moments of one video compete (the first per_video
         survivors of the pair's temporal NMS at nms_overlap).  videos: names or store positions to search, default the whole store.
@@ -238,27 +323,33 @@ class Grounder(object):
         store may be a drn_amd.SearchIndex built from the store for this model: every keyword means what it means above and the Hits
         are the same bit for bit, but a chunk's front is ONE launch (drn_gate_gather_packed reads the projected rows) instead of
         store.gather, the cast, the prop_fc GEMM, the position embedding and the gate pass.  A stale index (index.is_current(model) is
-        False) raises before any launch."""
+        False) raises before any launch.
+        candidates: instead of videos=, EACH sentence's own videos -- S lists of names or store positions, or the CSR pair
+        (ids, offsets) as a 2-tuple of arrays; a list is a set and may be empty (that sentence gets n = 0).  Only the listed
+        (sentence, video) pairs run the trunk.  plan_pairs cuts them into steps of one shape: at most `pairs` pairs (default
+        SEARCH_PAIR_BUDGET, the same choice as above, or the number of distinct pairs when that is smaller), at most `chunk` video slots (default min(pairs, the distinct candidate videos))
+        and at most (MERGE_MAX_CAND - top_k) // per_video pairs of one sentence; padded pairs are skipped by the ranking.  T defaults to
+        the largest count among all candidate videos.  All steps' arrays and first-chunk words go up in one copy; a step runs the same
+        front on its pairs (pair_q, pair_v instead of p // Vc, p % Vc), select_moments and drn_merge_moments_ragged.  The Hits of
+        candidates=[all videos] * S are those of the search without candidates.  graph=True: one more signature,
+        ("pairs", store, S, pairs, chunk, T, per_video, top_k): other lists that cut to the same shape replay the same graph."""
         from ._lib import MERGE_MAX_CAND
         from .index import SearchIndex
+        if candidates is not None and videos is not None:
+            raise DrnError("Grounder.search: candidates= and videos= exclude each other")
+        if pairs is not None and candidates is None:
+            raise DrnError("Grounder.search: pairs= is the step size of a search with candidates=")
         model = self.model
         indexed = isinstance(store, SearchIndex)
-        resident = store.rows if indexed else store.feats
         K = self.top_k if top_k is None else int(top_k)
         kv = int(per_video)
-        if model.training:
-            raise DrnError("Grounder.search is inference only: call model.eval() first")
-        for t in (query_tokens, query_length):
-            if not t.is_cuda:
-                raise DrnError("Grounder.search runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
-        if not resident.is_cuda:
-            raise DrnError("Grounder.search needs a store on the GPU (this one lives on %s); there is no CPU fallback" % store.device)
-        if store.dtype != model.compute_dtype:
-            raise DrnError("Grounder.search: the store holds %s, the model computes in %s" % (store.dtype, model.compute_dtype))
+        resident = self._check_resident("Grounder.search", query_tokens, query_length, store)
         if kv < 1 or K < 1:
             raise DrnError("Grounder.search: per_video and top_k must be at least 1 (got %d, %d)" % (kv, K))
         if indexed:
             store.check(model, "Grounder.search")
+        if candidates is not None:
+            return self._search_pairs(query_tokens, query_length, store, K, kv, candidates, chunk, pairs, T, resident.device)
         ids = np.arange(len(store), dtype=np.int32) if videos is None else store.ids_of(videos).numpy()
         if ids.size == 0:
             raise DrnError("Grounder.search: no videos to search")
@@ -314,6 +405,131 @@ class Grounder(object):
             ent.inputs[1].copy_(first[c])
             ent.graph.replay()
         return Hits(*[t.clone() for t in ent.out])
+
+    def _check_resident(self, what, query_tokens, query_length, store):
+        """The refusals search() and ground_stored() share, before anything is read from the device -> the resident tensor."""
+        from .index import SearchIndex
+        resident = store.rows if isinstance(store, SearchIndex) else store.feats
+        if self.model.training:
+            raise DrnError("%s is inference only: call model.eval() first" % what)
+        for t in (query_tokens, query_length):
+            if not t.is_cuda:
+                raise DrnError("%s runs on an MI355X only (inputs on %s); no CPU fallback" % (what, t.device))
+        if not resident.is_cuda:
+            raise DrnError("%s needs a store on the GPU (this one lives on %s); there is no CPU fallback" % (what, store.device))
+        if store.dtype != self.model.compute_dtype:
+            raise DrnError("%s: the store holds %s, the model computes in %s" % (what, store.dtype, self.model.compute_dtype))
+        return resident
+
+    @staticmethod
+    def _upload_plan(plan, extra, dev):
+        """ONE pinned upload of a PairPlan: row c = vids | pair_q | pair_v | pair_video | pair_off | extra[c] of chunk c -> the (C, width)
+        int32 device tensor and split(row) -> the six contiguous views of one row, so that a captured graph's static copy of a chunk is
+        filled with one copy."""
+        host = np.concatenate(list(plan) + [extra], axis=1).astype(np.int32)
+        ends = np.cumsum([a.shape[1] for a in plan] + [extra.shape[1]]).tolist()
+        split = lambda row: tuple(row[a:b] for a, b in zip([0] + ends[:-1], ends))
+        return torch.from_numpy(np.ascontiguousarray(host)).pin_memory().to(dev, non_blocking=True), split
+
+    def _pair_front(self, k, store, T, vid, pq, pv, gates):
+        """One step's pairs through the front and the trunk -> select_moments(k)'s five fields, one row per pair."""
+        from .index import SearchIndex
+        if isinstance(store, SearchIndex):
+            return self._select(k, store, vid, pq, pv, list(gates), T, entry="forward_heads_packed")
+        feats, pse, _ = store.gather(vid, T=T)
+        return self._select(k, None, None, feats, pse, video_index=pv, query_index=pq, gates=list(gates))
+
+    def _search_pairs(self, query_tokens, query_length, store, K, kv, candidates, chunk, pairs, T, dev):
+        """search(candidates=) after the refusals both forms share."""
+        from ._lib import MERGE_MAX_CAND
+        S = int(query_tokens.shape[0])
+        if S < 1:
+            raise DrnError("Grounder.search: no sentences")
+        if not (isinstance(candidates, tuple) and len(candidates) == 2 and all(isinstance(c, np.ndarray) or torch.is_tensor(c) for c in candidates)):
+            candidates = [store.ids_of(c).numpy() for c in candidates]            # (names -> positions, list by list)
+        ids, off = _pairs_csr(candidates, len(store))
+        if off.size - 1 != S:
+            raise DrnError("Grounder.search: %d candidate lists for %d sentences" % (off.size - 1, S))
+        cap = (MERGE_MAX_CAND - K) // kv
+        if cap < 1:
+            raise DrnError("Grounder.search: top_k + per_video = %d exceeds the %d candidates one ranking step holds" % (K + kv, MERGE_MAX_CAND))
+        distinct, key = np.unique(ids), _distinct_pairs(ids, off)
+        # (a short list of pairs is not padded up to the budget)
+        pairs = min(self.SEARCH_PAIR_BUDGET, max(1, int(key.size))) if pairs is None else int(pairs)
+        slots = min(pairs, max(int(distinct.size), 1)) if chunk is None else int(chunk)
+        if pairs < 1 or slots < 1:
+            raise DrnError("Grounder.search: pairs and chunk must be at least 1 (got %d, %d)" % (pairs, slots))
+        plan = _plan(key, S, pairs, slots, cap)
+        C = int(plan.vids.shape[0])
+        if C == 0:                                                # nobody listed anything: every sentence's hits are empty
+            fill = lambda shape, dt, v: torch.full(shape, v, dtype=dt, device=dev)
+            return Hits(fill((S, K, 2), torch.float32, 0), fill((S, K), torch.float32, 0), fill((S, K), torch.int32, -1),
+                        fill((S, K), torch.int32, -1), fill((S, K), torch.int32, -1), fill((S,), torch.int32, 0))
+        T = int(store.nprops[distinct].max()) if T is None else int(T)
+        rows, split = self._upload_plan(plan, (np.arange(C) == 0).astype(np.int32).reshape(C, 1), dev)
+        gates = [g.contiguous() for g in self.model.encode_query(query_tokens, query_length)]
+
+        def body(row, seg, score, video, level, rank, n, *g):
+            vid, pq, pv, pvideo, poff, flag = split(row)
+            mom = self._pair_front(kv, store, T, vid, pq, pv, g)
+            return ops.merge_moments_ragged(mom, pvideo, poff, len(store), (seg, score, video, level, rank, n), flag)
+
+        ent = None
+        if self.graph:
+            sig = ("pairs", store, S, pairs, slots, T, kv, K)
+            ent, _ = self._entry(sig, body, dev, lambda: [rows[0].clone()] + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates])
+        if ent is None:
+            state = ops.merge_state(S, K, dev)
+            for c in range(C):
+                body(rows[c], *(state + tuple(gates)))
+            return Hits(*state)
+        for dst, src in zip(ent.inputs[7:], gates):
+            dst.copy_(src)
+        for c in range(C):
+            ent.inputs[0].copy_(rows[c])
+            ent.graph.replay()
+        return Hits(*[t.clone() for t in ent.out])
+
+    @torch.no_grad()
+    def ground_stored(self, query_tokens, query_length, store, videos, pairs=None, T=None):
+        """ground() on videos that are already on the device: sentence q is grounded in videos[q] (Q names or store positions; a video
+        may be named by many sentences) of a FeatureStore or a SearchIndex -> Moments, bit for bit those of
+        ground(query_tokens, query_length, *store.gather(unique, T)[:2], video_index) with unique, video_index = group_by_video(videos).
+        T: the padded proposal count, default the largest count among the named videos.  The sentences are encoded once; the Q pairs
+        run in steps of `pairs` (default min(SEARCH_PAIR_BUDGET, Q)) cut by plan_pairs, a step's select_moments(top_k) rows are scattered
+        into their sentences' rows of the result, padded pairs' rows are dropped.  No ranking across videos, so a pair without a
+        candidate keeps Moments' fallback moment.  No host synchronisation.  Eager only: graph=True does not apply here."""
+        from .index import SearchIndex
+        resident = self._check_resident("Grounder.ground_stored", query_tokens, query_length, store)
+        if isinstance(store, SearchIndex):
+            store.check(self.model, "Grounder.ground_stored")
+        Q = int(query_tokens.shape[0])
+        ids = store.ids_of(videos).numpy().astype(np.int64)
+        if Q < 1 or ids.size != Q:
+            raise DrnError("Grounder.ground_stored: %d videos for %d sentences (one each, at least one)" % (ids.size, Q))
+        if int(ids.min()) < 0 or int(ids.max()) >= len(store):
+            raise DrnError("Grounder.ground_stored: video positions outside [0, %d)" % len(store))
+        pairs = min(self.SEARCH_PAIR_BUDGET, Q) if pairs is None else int(pairs)
+        if pairs < 1:
+            raise DrnError("Grounder.ground_stored: pairs must be at least 1 (got %d)" % pairs)
+        distinct = np.unique(ids)
+        plan = plan_pairs((ids, np.arange(Q + 1)), len(store), pairs, min(pairs, int(distinct.size)), pairs)
+        T = int(store.nprops[distinct].max()) if T is None else int(T)
+        dev, k, C = resident.device, self.top_k, int(plan.vids.shape[0])
+        # where a pair's rows go: its sentence's row, or -- a padded pair -- a scratch row of its own past the Q real ones
+        real = plan.pair_video >= 0
+        dest = np.where(real, plan.pair_q, Q + np.arange(pairs, dtype=np.int32)[None, :])
+        rows, split = self._upload_plan(plan, dest, dev)
+        gates = [g.contiguous() for g in self.model.encode_query(query_tokens, query_length)]
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        out = (torch.empty((Q + pairs, k, 2), dtype=torch.float32, device=dev), torch.empty((Q + pairs, k), dtype=torch.float32, device=dev),
+               i32(Q + pairs, k), i32(Q + pairs, k), i32(Q + pairs))
+        for c in range(C):
+            vid, pq, pv, _, _, where = split(rows[c])
+            where = where.long()
+            for dst, src in zip(out, self._pair_front(k, store, T, vid, pq, pv, gates)):
+                dst.index_copy_(0, where, src)
+        return Moments(*[t[:Q] for t in out])
 
 
 def search(model, query_tokens, query_length, store, top_k=5, nms_overlap=0.45, fused=False, **kw):

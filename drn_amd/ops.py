@@ -1239,6 +1239,36 @@ def merge_moments(moments, vids, num_videos, state, first):
     return state
 
 
+def merge_moments_ragged(moments, pair_video, pair_off, num_videos, state, first):
+    """merge_moments for one chunk of P pairs in any assignment to sentences (drn_merge_moments_ragged): pair_video (P,) int32 on the
+    device = the store position of pair p's video (outside [0, num_videos): a padded pair, skipped), pair_off (S + 1,) int32 on the
+    device = sentence s owns the pairs [pair_off[s], pair_off[s + 1]) of the chunk; pairs outside every range take no part.  state,
+    first, the candidates and the order are merge_moments'.  A sentence without a pair keeps its state (first false) or is left
+    empty (first true).  No host synchronisation: pair_off is not read back, the launch clamps what it reads from it."""
+    seg, score, level, index, n = moments
+    st_seg, st_score, st_video, st_level, st_rank, st_n = state
+    _need_gpu(seg, score, level, index, n, pair_video, pair_off, *state)
+    P, kv = (int(x) for x in score.shape)
+    S, k = (int(x) for x in st_score.shape)
+    flag = first if torch.is_tensor(first) else None
+    if flag is not None:
+        _need_gpu(flag)
+    for name, t, dt, shape in (("seg", seg, torch.float32, (P, kv, 2)), ("score", score, torch.float32, (P, kv)),
+                               ("level", level, torch.int32, (P, kv)), ("index", index, torch.int32, (P, kv)), ("n", n, torch.int32, (P,)),
+                               ("pair_video", pair_video, torch.int32, (P,)), ("pair_off", pair_off, torch.int32, (S + 1,)),
+                               ("state seg", st_seg, torch.float32, (S, k, 2)), ("state score", st_score, torch.float32, (S, k)),
+                               ("state video", st_video, torch.int32, (S, k)), ("state level", st_level, torch.int32, (S, k)),
+                               ("state rank", st_rank, torch.int32, (S, k)), ("state n", st_n, torch.int32, (S,)),
+                               ("first", flag, torch.int32, (1,))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.DrnError("merge_moments_ragged: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    check(lib().drn_merge_moments_ragged(_p(seg), _p(score), _p(level), _p(index), _p(n), S, P, kv, _p(pair_video), _p(pair_off),
+                                         int(num_videos), k, 0 if flag is not None else int(bool(first)), _p(flag), _p(st_seg),
+                                         _p(st_score), _p(st_video), _p(st_level), _p(st_rank), _p(st_n), _stream()),
+          "drn_merge_moments_ragged")
+    return state
+
+
 # ---------------------------------------------------------------------------------------------
 # query-encoder glue (drn_amd/csrc/qenc.hip)
 # ---------------------------------------------------------------------------------------------

@@ -550,6 +550,18 @@ int drn_select_moments(const float* det, const float* scores, const int32_t* cou
 int drn_merge_moments(const float* seg, const float* score, const int32_t* level, const int32_t* index, const int32_t* n, int S, int Vc,
                       int kv, const int32_t* vids, int Nv, int K, int first, const int32_t* first_dev, float* st_seg, float* st_score,
                       int32_t* st_video, int32_t* st_level, int32_t* st_rank, int32_t* st_n, void* stream);
+/* drn_merge_moments for a chunk of P pairs in ANY assignment to sentences (a shortlist of videos per sentence): pair_video [P] = the
+ * store position of pair p's video (outside [0, Nv): a padded pair, skipped), pair_off [S + 1] = sentence s owns the pairs
+ * [pair_off[s], pair_off[s + 1]) of the chunk; both on the device.  Pairs outside every range take no part.  Same candidates, same
+ * exceptions, same total order (a pair's position in its sentence's range standing in for the chunk slot), same state and same
+ * first / first_dev as drn_merge_moments.  A sentence without a pair in the chunk keeps its state bit for bit (first == 0) or is left
+ * empty (first != 0).  Nothing read from pair_off is trusted: offsets are clamped to [0, P], a negative or decreasing range is empty,
+ * and at most (DRN_MERGE_MAX_CAND - K) / kv pairs of a range are read -- a caller that wants every pair ranked keeps its ranges within
+ * that.  K + kv <= DRN_MERGE_MAX_CAND, refused otherwise.  One wavefront per sentence, no host synchronisation. */
+int drn_merge_moments_ragged(const float* seg, const float* score, const int32_t* level, const int32_t* index, const int32_t* n, int S,
+                             int P, int kv, const int32_t* pair_video, const int32_t* pair_off, int Nv, int K, int first,
+                             const int32_t* first_dev, float* st_seg, float* st_score, int32_t* st_video, int32_t* st_level,
+                             int32_t* st_rank, int32_t* st_n, void* stream);
 
 /* ---- query-encoder glue (drn_amd/csrc/qenc.hip; model/language_module.py:17-63), all fp32 ----------------------
  * Word embedding lookup written time-major (L, B, E) and its dense gradient (row padding_idx stays zero). */

@@ -9,7 +9,12 @@
   kernel   drn_gate_gather_packed alone at the search's largest step (512 pairs) and at 64 pairs: launch-inclusive microseconds per
            call over ~0.3 s windows and the bytes it WRITES (Q T (C + P) elements) over that time.
 
-    python scripts/bench_search.py [--out profiles/search_bench.json] [--rounds 5]"""
+    python scripts/bench_search.py [--out profiles/search_bench.json] [--rounds 5]
+
+  --shortlist  instead of the above -> profiles/search_pairs_bench.json: S = 8 sentences, each with its own N random candidates of
+           the 64 videos (N in {4, 16, 64 = all}), Grounder.search(candidates=) beside the full cartesian search of the same
+           Grounders, on the store and on the index, eager and by graph replay; same store, same protocol.  At N = all the two
+           searches do the same device work and their Hits are compared field for field."""
 import argparse
 import json
 import os
@@ -79,6 +84,72 @@ def bench_search(model, store, index, T, S, rounds, window_s=0.3):
     return res
 
 
+def bench_shortlist(model, where, name, T, S, N, rounds, window_s=0.3):
+    """Shortlists of N videos per sentence (drawn without replacement, seed N) beside the cartesian search of all NV videos: the same
+    two Grounders (eager, graph) run both, interleaved."""
+    import numpy as np
+    from drn_amd import Grounder
+    tok, qlen = sentences(S, 7)
+    g = np.random.RandomState(N)
+    lists = [sorted(int(v) for v in g.permutation(NV)[:N]) for _ in range(S)]
+    eager, graphed = Grounder(model, top_k=10), Grounder(model, top_k=10, graph=True)
+    variants = {"cartesian_eager": lambda: eager.search(tok, qlen, where, per_video=2),
+                "shortlist_eager": lambda: eager.search(tok, qlen, where, per_video=2, candidates=lists),
+                "cartesian_graph": lambda: graphed.search(tok, qlen, where, per_video=2),
+                "shortlist_graph": lambda: graphed.search(tok, qlen, where, per_video=2, candidates=lists)}
+    hits = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(getattr(hits[a], f), getattr(hits[b], f)) for f in STATE)
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    distinct = len(set(v for l in lists for v in l))
+    res = {"resident": name, "T": T, "S": S, "videos": NV, "candidates_per_sentence": N, "pairs": S * N, "cartesian_pairs": S * NV,
+           "distinct_candidate_videos": distinct, "top_k": 10, "per_video": 2, "rounds": rounds, "graph_captures": graphed.captures,
+           "shortlist_graph_equals_eager": same("shortlist_graph", "shortlist_eager"),
+           "shortlist_equals_cartesian": same("shortlist_eager", "cartesian_eager") if N == NV else None, "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_min": min(ts), "ms_per_search_max": max(ts),
+                              "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    med = lambda k: res["variants"][k]["ms_per_search_median"]
+    res["shortlist_over_cartesian"] = {"eager": med("shortlist_eager") / med("cartesian_eager"),
+                                       "graph": med("shortlist_graph") / med("cartesian_graph")}
+    return res
+
+
+def main_shortlist(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex
+    out = args.out or os.path.join(ROOT, "profiles", "search_pairs_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, store and index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s; min and max of the rounds beside it",
+                      "clock": "host clock around searches ending in a device synchronise",
+                      "what": "Grounder.search(candidates=) with N random videos per sentence beside Grounder.search over all videos"},
+           "shortlist": []}
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        index = SearchIndex.build(model, store)
+        for name, where in (("store", store), ("index", index)):
+            for N in (4, 16, NV):
+                res["shortlist"].append(bench_shortlist(model, where, name, T, 8, N, args.rounds))
+                print(json.dumps({"shortlist": res["shortlist"][-1]}), flush=True)
+                json.dump(res, open(out, "w"), indent=1)
+        del store, index
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def bench_build(model, store, rounds):
     from drn_amd import SearchIndex
     index = SearchIndex.build(model, store)
@@ -122,11 +193,15 @@ def bench_kernel(index, T, Q, rounds, window_s=0.3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search_bench.json"))
+    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (profiles/search_pairs_bench.json with --shortlist)")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.shortlist:
+        return main_shortlist(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, store and index resident",
