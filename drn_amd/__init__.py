@@ -6,3 +6,4 @@ __version__ = "0.1.0"
 from .grounding import Grounder, Hits, Moments, group_by_video, search  # noqa: E402,F401
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
 from .index import SearchIndex  # noqa: E402,F401
+from .search_eval import SearchRecall, evaluate_search, search_batches  # noqa: E402,F401

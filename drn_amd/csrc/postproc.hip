@@ -452,3 +452,71 @@ extern "C" int drn_merge_moments_ragged(const float* seg, const float* score, co
                                                                  first_dev, st_seg, st_score, st_video, st_level, st_rank, st_n);
   return drn_launch_status("drn_merge_moments_ragged");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Corpus recall of a search: where, in a sentence's Hits, does the right moment of the right video first appear?  One wavefront
+// per sentence; only the first m = min(max(n[s], 0), K) entries are read.  Column i < I: the first position whose video is the
+// ground truth's and whose un-clamped tIoU with the ground truth (eval_recall_kernel's expression, in double on the float32
+// segment) is >= ious[i]; a NaN among the four bounds is no hit (fmin / fmax would drop it and call the pair identical).  Column I:
+// the number of DISTINCT videos ranked before the first entry of the ground truth's video -- its position in the video ranking,
+// whatever per_video was.  K where there is none.  The video column is staged in LDS for the distinct count.
+__global__ __launch_bounds__(64) void search_recall_kernel(const float* __restrict__ seg, const int* __restrict__ video,
+                                                           const int* __restrict__ n, const int* __restrict__ gt_video,
+                                                           const void* __restrict__ gt, int gt_f64, const double* __restrict__ ious,
+                                                           int K, int I, int* __restrict__ out) {
+  __shared__ int vcol[MM_MAX_CAND];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const long o = (long)s * K;
+  const int m = min(max(n[s], 0), K);          // (K <= MM_MAX_CAND: checked by the host)
+  const int gv = gt_video[s];
+  for (int p = lane; p < m; p += 64) vcol[p] = video[o + p];
+  __syncthreads();
+  const double g0 = gt_f64 ? ((const double*)gt)[s * 2] : (double)((const float*)gt)[s * 2];
+  const double g1 = gt_f64 ? ((const double*)gt)[s * 2 + 1] : (double)((const float*)gt)[s * 2 + 1];
+  const bool gt_ok = gv >= 0 && !(g0 != g0) && !(g1 != g1);
+  int* __restrict__ row = out + (long)s * (I + 1);
+  for (int i = 0; i < I; ++i) {
+    const double thr = ious[i];
+    int first = K;
+    if (gt_ok)
+      for (int p = lane; p < m; p += 64) {
+        if (vcol[p] != gv) continue;
+        const double x1 = (double)seg[(o + p) * 2], x2 = (double)seg[(o + p) * 2 + 1];
+        if (x1 != x1 || x2 != x2) continue;
+        const double iou = (fmin(g1, x2) - fmax(g0, x1)) / (fmax(g1, x2) - fmin(g0, x1));
+        if (iou >= thr) { first = p; break; }  // (a lane's positions ascend: its first hit is its smallest)
+      }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) first = min(first, __shfl_xor(first, w, 64));
+    if (lane == 0) row[i] = first;
+  }
+  int p0 = m;
+  if (gv >= 0)
+    for (int p = lane; p < m; p += 64)
+      if (vcol[p] == gv) { p0 = p; break; }
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) p0 = min(p0, __shfl_xor(p0, w, 64));
+  const bool found = p0 < m;                   // (wave-uniform; gv < 0 leaves p0 = m)
+  int distinct = 0;                            // entries before p0 that are the first of their video
+  for (int p = lane; found && p < p0; p += 64) {
+    const int v = vcol[p];
+    bool seen = false;
+    for (int j = 0; j < p && !seen; ++j) seen = vcol[j] == v;
+    distinct += !seen;
+  }
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) distinct += __shfl_xor(distinct, w, 64);
+  if (lane == 0) row[I] = found ? distinct : K;
+}
+
+extern "C" int drn_search_recall(const float* seg, const int32_t* video, const int32_t* n, const int32_t* gt_video, const void* gt,
+                                 int gt_is_f64, const double* ious, int S, int K, int I, int32_t* first_hit, void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(S >= 1, "drn_search_recall: S = %d, at least 1 sentence", S);
+  DRN_CHECK_ARG(K >= 1, "drn_search_recall: K = %d, at least 1 hit slot per sentence", K);
+  DRN_CHECK_ARG(I >= 1, "drn_search_recall: I = %d, at least 1 IoU threshold", I);
+  DRN_CHECK_ARG(K <= MM_MAX_CAND, "drn_search_recall: K = %d hit slots per sentence (max %d)", K, MM_MAX_CAND);
+  DRN_CHECK_ARG(seg && video && n && gt_video && gt && ious && first_hit, "drn_search_recall: null pointer");
+  search_recall_kernel<<<S, 64, 0, (hipStream_t)stream>>>(seg, video, n, gt_video, gt, gt_is_f64, ious, K, I, first_hit);
+  return drn_launch_status("drn_search_recall");
+}

@@ -146,6 +146,39 @@ def recall_from_first_hits(first_hits, ious, topks):
     return [float((fh[:, q] < k).sum()) / total for q in range(len(ious)) for k in topks]
 
 
+def search_first_hits(rows, gt_video, gt, ious, K):
+    """Where the right moment of the right video first appears in a search's hits: the host twin of drn_search_recall
+    (ops.search_recall), for callers that hold host records.  rows: Hits.tolist()'s, per sentence [[video, start, end, score], ...]
+    best first (the first K are read); gt_video[s]: the annotated video as rows name it (a store position; negative: none);
+    gt[s]: [start, end] as fractions of the video.  -> (S, len(ious) + 1) int32 array:
+      column i < len(ious)  the position of the first row in the right video whose tIoU with gt[s] is >= ious[i] -- calculate_IoU's
+                            un-clamped expression in doubles; a disjoint pair is negative, 0/0 and a NaN bound are no hit;
+      last column           the number of DISTINCT videos ranked before the first row of the right video: its place in the video
+                            ranking, however many moments per video competed;
+    K where there is none.  recall_from_first_hits turns columns of either kind into recalls."""
+    K, ious = int(K), [float(x) for x in ious]
+    out = np.full((len(rows), len(ious) + 1), K, dtype=np.int32)
+    for s, hits in enumerate(rows):
+        gv, (g0, g1) = int(gt_video[s]), (float(x) for x in gt[s])
+        if gv < 0:
+            continue
+        hits, before = hits[:max(K, 0)], set()
+        for p, (v, x1, x2) in enumerate((h[0], float(h[1]), float(h[2])) for h in hits):
+            if v != gv:
+                before.add(v)
+                continue
+            if out[s, -1] == K:
+                out[s, -1] = len(before)
+            if g0 != g0 or g1 != g1 or x1 != x1 or x2 != x2:
+                continue
+            with np.errstate(invalid="ignore", divide="ignore"):      # (x / 0 as IEEE has it, not ZeroDivisionError)
+                iou = float(np.float64(min(g1, x2) - max(g0, x1)) / np.float64(max(g1, x2) - min(g0, x1)))
+            for i, thr in enumerate(ious):
+                if out[s, i] == K and iou >= thr:
+                    out[s, i] = p
+    return out
+
+
 def results_entries(queries, gts, boxes):
     """results_entry for a whole batch with ONE device->host copy per field (all clips' detections / scores concatenated on
     the device first) instead of two per clip."""

@@ -1269,6 +1269,31 @@ def merge_moments_ragged(moments, pair_video, pair_off, num_videos, state, first
     return state
 
 
+def search_recall(hits, gt_video, gt, ious):
+    """Score a search against ground truth on the device (drn_search_recall): hits = Grounder.search's Hits (or anything with its seg
+    (S, K, 2) float32, video (S, K) int32 and n (S,) int32), gt_video (S,) int32 store positions, gt (S, 2) float32 / float64 start and
+    end as fractions of the video, ious (I,) float64 -- all on the device -> first_hit (S, I + 1) int32 on the device: column i < I
+    the position of the first hit in the right video with tIoU >= ious[i], column I the number of distinct videos ranked before the
+    right one, K where there is none (metrics.search_first_hits is the host twin; metrics.recall_from_first_hits turns either kind
+    of column into recalls).  No host synchronisation."""
+    seg, video, n = hits.seg, hits.video, hits.n
+    _need_gpu(seg, video, n, gt_video, gt, ious)
+    if video.dim() != 2:
+        raise _lib.DrnError("search_recall: video must be a (S, K) tensor, not %s" % (tuple(video.shape),))
+    S, K = (int(x) for x in video.shape)
+    I = int(ious.numel())
+    if gt.dtype not in (torch.float32, torch.float64):
+        raise _lib.DrnError("search_recall: gt must be float32 or float64, not %s" % gt.dtype)
+    for name, t, dt, shape in (("seg", seg, torch.float32, (S, K, 2)), ("video", video, torch.int32, (S, K)), ("n", n, torch.int32, (S,)),
+                               ("gt_video", gt_video, torch.int32, (S,)), ("gt", gt, gt.dtype, (S, 2)), ("ious", ious, torch.float64, (I,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("search_recall: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    out = torch.empty((S, I + 1), dtype=torch.int32, device=video.device)
+    check(lib().drn_search_recall(_p(seg), _p(video), _p(n), _p(gt_video), _p(gt), int(gt.dtype == torch.float64), _p(ious), S, K, I,
+                                  _p(out), _stream()), "drn_search_recall")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # query-encoder glue (drn_amd/csrc/qenc.hip)
 # ---------------------------------------------------------------------------------------------

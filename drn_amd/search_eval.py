@@ -1,0 +1,75 @@
+"""Is a search any good?  Corpus recall of Grounder.search against annotated sentences, scored on the device.
+
+evaluate_search runs every batch of sentences through Grounder.search (a FeatureStore or a SearchIndex, cartesian or with per-sentence
+candidates, eagerly or by graph replay) and scores the Hits where they lie (ops.search_recall, one launch per batch): how often is the
+right moment of the right video among the first k hits, and how often is the right video among the first k videos.  The batch tables
+stay on the device and cross in ONE copy at the end of the pass; nothing inside the loop waits for the device.
+metrics.search_first_hits is the host twin, for callers that hold Hits.tolist() records."""
+import collections
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import DrnError
+from .metrics import recall_from_first_hits
+from .store import _upload
+
+SearchRecall = collections.namedtuple("SearchRecall", "n ious topks moment video first_hits")
+SearchRecall.__doc__ = """n sentences scored at the tIoU thresholds `ious` and the depths `topks`.  moment: recall of the right moment in
+the right video, in run_evaluate's order (for iou: for topk); video: recall of the right video, one per topk, counted in the ranking
+of DISTINCT videos; first_hits (n, len(ious) + 1) int32 numpy array, ops.search_recall's rows in the order the sentences were seen."""
+
+
+def search_batches(loader):
+    """What evaluate_search reads, (names, query_tokens, query_length, gt) per batch, from what exists: a StoreLoader goes through its
+    host_batches() (nothing is gathered: the search reads the store itself), any other iterable of collate_data 8-tuples through
+    elements 0, 4, 5 and 3."""
+    if hasattr(loader, "host_batches"):
+        for names, _, gt, tok, qlen, _, _ in loader.host_batches():
+            yield names, tok, qlen, gt
+    else:
+        for batch in loader:
+            yield batch[0], batch[4], batch[5], batch[3]
+
+
+def _positions(names, store):
+    """The store positions of a batch's ground-truth videos, on the host; a name the store lacks raises."""
+    ids = []
+    for name in names:
+        if name not in store.index:
+            raise DrnError("evaluate_search: the store has no video named %s" % (name,))
+        ids.append(store.index[name])
+    return torch.tensor(ids, dtype=torch.int32)
+
+
+@torch.no_grad()
+def evaluate_search(grounder, batches, store, ious=(0.5, 0.7), topks=(1, 10, 100), per_video=1, candidates=None, **search_kw):
+    """batches: an iterable of (names, query_tokens, query_length, gt) -- names[q] the video sentence q is annotated in, gt (S, 2) its
+    start and end as fractions of that video; tensors on the host or on the device (search_batches adapts a loader).  store: the
+    FeatureStore or SearchIndex to search.  Every batch runs grounder.search(..., top_k=max(topks), per_video=per_video, **search_kw)
+    -- search_kw: chunk, T, pairs, videos -- and one drn_search_recall launch on its Hits.  candidates: None, or a callable
+    (names, query_tokens, query_length) -> what search(candidates=) accepts, called once per batch (a retriever's shortlist).
+    A batch's names are resolved against store.index on the host before anything of that batch is launched; the ground truth goes
+    up through pinned non-blocking copies; the tables are concatenated and copied ONCE, after the last batch.  Works with
+    Grounder(graph=True): search()'s graph is the body, the recall launch sits outside it.  -> SearchRecall; no batches: n = 0 and
+    recalls of 0.  On weights that were not trained on the annotations the numbers say nothing about the model."""
+    ious, topks = [float(x) for x in ious], [int(k) for k in topks]
+    if not ious or not topks:
+        raise DrnError("evaluate_search: at least one IoU threshold and one top-k")
+    K, I, dev = max(topks), len(ious), store.device
+    ious_dev, tables = None, []
+    for names, tok, qlen, gt in batches:
+        gt_video = _positions(names, store)
+        if gt.dtype not in (torch.float32, torch.float64):
+            gt = gt.double()
+        up = lambda t: t if t.is_cuda else _upload(t, dev)
+        if ious_dev is None:
+            ious_dev = up(torch.tensor(ious, dtype=torch.float64))
+        tok, qlen = up(tok), up(qlen)
+        cands = candidates(names, tok, qlen) if candidates is not None else None
+        hits = grounder.search(tok, qlen, store, top_k=K, per_video=per_video, candidates=cands, **search_kw)
+        tables.append(ops.search_recall(hits, up(gt_video), up(gt).contiguous(), ious_dev))
+    fh = torch.cat(tables).cpu().numpy() if tables else np.zeros((0, I + 1), dtype=np.int32)
+    return SearchRecall(int(fh.shape[0]), ious, topks, recall_from_first_hits(fh[:, :I], ious, topks),
+                        recall_from_first_hits(fh[:, I:], ious[:1], topks), fh)

@@ -511,6 +511,23 @@ class Trainer(object):
             self.model.train(was_training)
         return out
 
+    def evaluate_search(self, loader, store, grounder=None, **kw):
+        """Corpus recall of a search over `store` (a FeatureStore or a SearchIndex) for every annotated sentence of `loader` (a
+        StoreLoader, or any iterable of collate_data batches; only names, tokens, lengths and ground truth are read) ->
+        drn_amd.search_eval.SearchRecall.  kw: evaluate_search's ious, topks, per_video, candidates and search()'s chunk, T, pairs,
+        videos.  grounder: a Grounder of this model to search with (its options, its graphs); default Grounder(model).  The model
+        is run in eval mode and put back into the mode it was in, as predict() does."""
+        from .grounding import Grounder
+        from .search_eval import evaluate_search, search_batches
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            if grounder is None:
+                grounder = Grounder(self.model)
+            return evaluate_search(grounder, search_batches(loader), store, **kw)
+        finally:
+            self.model.train(was_training)
+
     def fit(self, train_loader, test_loader, n_epoch=None, eval_freq=1, snapshot_pref=None, dataset="Charades", id2word=None,
             start_epoch=0, rank=0):
         """main.py:142-190: train, validate every eval_freq epochs, keep the best-R@1 and best-R@5 checkpoints.

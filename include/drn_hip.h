@@ -562,6 +562,19 @@ int drn_merge_moments_ragged(const float* seg, const float* score, const int32_t
                              int P, int kv, const int32_t* pair_video, const int32_t* pair_off, int Nv, int K, int first,
                              const int32_t* first_dev, float* st_seg, float* st_score, int32_t* st_video, int32_t* st_level,
                              int32_t* st_rank, int32_t* st_n, void* stream);
+/* Corpus recall of a search, on the device: scores the Hits of S sentences (drn_merge_moments' state: seg [S][K][2], video [S][K],
+ * n [S]) against ground truth -- gt_video [S] = store position of the annotated video, gt [S][2] = start and end as fractions of it,
+ * fp64 or fp32 (gt_is_f64); ious: device array of I doubles.  first_hit [S][I + 1], with m = min(max(n[s], 0), K):
+ *   column i < I  the smallest position p in [0, m) with video[s][p] == gt_video[s] and tIoU(seg[s][p], gt[s]) >= ious[i], K when none;
+ *                 tIoU is drn_eval_recall's un-clamped (min(g1, x2) - max(g0, x1)) / (max(g1, x2) - min(g0, x1)) in double on the
+ *                 float32 segment -- a disjoint pair is negative, 0/0 and a NaN bound are no hit;
+ *   column I      the number of DISTINCT videos among video[s][0:p0], p0 = the smallest position in [0, m) of gt_video[s]'s video, K
+ *                 when there is none: the ground-truth video's place in the VIDEO ranking, whatever per_video was.
+ * Entries at or past n[s] are not read.  A gt_video that is negative or names no video of the row yields K in every column.
+ * recall@k counts first_hit < k.  K <= DRN_MERGE_MAX_CAND (a Hits table cannot be larger), refused otherwise.  One wavefront per
+ * sentence, no host synchronisation. */
+int drn_search_recall(const float* seg, const int32_t* video, const int32_t* n, const int32_t* gt_video, const void* gt, int gt_is_f64,
+                      const double* ious /*device*/, int S, int K, int I, int32_t* first_hit, void* stream);
 
 /* ---- query-encoder glue (drn_amd/csrc/qenc.hip; model/language_module.py:17-63), all fp32 ----------------------
  * Word embedding lookup written time-major (L, B, E) and its dense gradient (row padding_idx stays zero). */

@@ -14,7 +14,12 @@
   --shortlist  instead of the above -> profiles/search_pairs_bench.json: S = 8 sentences, each with its own N random candidates of
            the 64 videos (N in {4, 16, 64 = all}), Grounder.search(candidates=) beside the full cartesian search of the same
            Grounders, on the store and on the index, eager and by graph replay; same store, same protocol.  At N = all the two
-           searches do the same device work and their Hits are compared field for field."""
+           searches do the same device work and their Hits are compared field for field.
+
+  --evaluate   instead of the above -> profiles/search_eval_bench.json: one evaluation pass over 8 batches of S = 8 annotated sentences
+           (drn_amd.evaluate_search: search, drn_search_recall on the Hits, ONE copy at the end of the pass) beside the same batches
+           scored on the host (search, Hits.tolist(), metrics.search_first_hits, per batch), on the store and on the index, eager and
+           by graph replay; same store, same protocol.  The two tables are compared."""
 import argparse
 import json
 import os
@@ -150,6 +155,85 @@ def main_shortlist(args):
     print("wrote", out)
 
 
+def bench_evaluate(model, where, name, T, rounds, S=8, nbatches=8, window_s=0.3):
+    """One pass = nbatches batches of S sentences, sentence q of batch b annotated in video (b * S + q) % NV with a random ground truth
+    (host tensors, as search_batches yields them; the tokens are resident, as a caller that evaluates repeatedly keeps them).
+    device: evaluate_search.  host: per batch search -> Hits.tolist() (a synchronise and six copies) -> metrics.search_first_hits."""
+    import numpy as np
+    from drn_amd import Grounder, evaluate_search
+    from drn_amd.metrics import search_first_hits
+    ious, K, kv = (0.5, 0.7), 10, 2
+    g = torch.Generator().manual_seed(T)
+    batches = []
+    for b in range(nbatches):
+        tok, qlen = sentences(S, 100 + b)
+        start = torch.rand(S, generator=g, dtype=torch.float64) * 0.5
+        gt = torch.stack([start, start + 0.1 + torch.rand(S, generator=g, dtype=torch.float64) * 0.4], dim=1)
+        batches.append((["V%03d" % ((b * S + q) % NV) for q in range(S)], tok, qlen, gt))
+    eager, graphed = Grounder(model, top_k=K), Grounder(model, top_k=K, graph=True)
+
+    def on_host(grounder):
+        parts = []
+        for names, tok, qlen, gt in batches:
+            rows = grounder.search(tok, qlen, where, top_k=K, per_video=kv).tolist()
+            parts.append(search_first_hits(rows, [where.index[n] for n in names], gt.tolist(), ious, K))
+        return np.concatenate(parts)
+    on_device = lambda grounder: evaluate_search(grounder, batches, where, ious=ious, topks=(1, K), per_video=kv).first_hits
+    variants = {"device_eager": lambda: on_device(eager), "host_eager": lambda: on_host(eager),
+                "device_graph": lambda: on_device(graphed), "host_graph": lambda: on_host(graphed)}
+    tables = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 2)
+        reps[k] = max(3, int(window_s * 1e3 / window(fn, 3)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]) / nbatches)
+    ref = tables["host_eager"]
+    res = {"resident": name, "T": T, "S": S, "batches_per_pass": nbatches, "videos": NV, "pairs_per_step": S * NV, "top_k": K,
+           "per_video": kv, "ious": list(ious), "rounds": rounds, "graph_captures": graphed.captures,
+           "tables_equal_host_eager": {k: bool((tables[k] == ref).all()) for k in variants},
+           "sentences_hit_at_any_depth": int((ref[:, :len(ious)] < K).any(axis=1).sum()),
+           "videos_found": int((ref[:, len(ious)] < K).sum()), "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_batch_median": statistics.median(ts), "ms_per_batch_min": min(ts), "ms_per_batch_max": max(ts),
+                              "ms_per_batch_rounds": ts, "passes_per_window": reps[k]}
+    med = lambda k: res["variants"][k]["ms_per_batch_median"]
+    res["device_over_host"] = {"eager": med("device_eager") / med("host_eager"), "graph": med("device_graph") / med("host_graph")}
+    return res
+
+
+def main_evaluate(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex
+    out = args.out or os.path.join(ROOT, "profiles", "search_eval_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, store and index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s of whole passes, per batch; "
+                                                        "min and max of the rounds beside it",
+                      "clock": "host clock around passes that end with the table on the host",
+                      "what": "evaluate_search (drn_search_recall per batch, one copy per pass) beside search + Hits.tolist() + "
+                              "metrics.search_first_hits per batch; synthetic weights: the recalls mean nothing"},
+           "evaluate": []}
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        index = SearchIndex.build(model, store)
+        for name, where in (("store", store), ("index", index)):
+            res["evaluate"].append(bench_evaluate(model, where, name, T, args.rounds))
+            print(json.dumps({"evaluate": res["evaluate"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        del store, index
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def bench_build(model, store, rounds):
     from drn_amd import SearchIndex
     index = SearchIndex.build(model, store)
@@ -193,14 +277,17 @@ def bench_kernel(index, T, Q, rounds, window_s=0.3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (profiles/search_pairs_bench.json with --shortlist)")
+    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
+    ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
     if args.shortlist:
         return main_shortlist(args)
+    if args.evaluate:
+        return main_evaluate(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
