@@ -409,7 +409,7 @@ class Grounder(object):
     def _check_resident(self, what, query_tokens, query_length, store):
         """The refusals search() and ground_stored() share, before anything is read from the device -> the resident tensor."""
         from .index import SearchIndex
-        resident = store.rows if isinstance(store, SearchIndex) else store.feats
+        resident = store.resident if isinstance(store, SearchIndex) else store.feats
         if self.model.training:
             raise DrnError("%s is inference only: call model.eval() first" % what)
         for t in (query_tokens, query_length):

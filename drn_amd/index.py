@@ -9,7 +9,13 @@ runs exactly those launches once per video and keeps their outputs for the real 
   feature row with zero bounds, i.e. what conv0 is fed past a video's proposals and for an empty chunk slot.
 
 Grounder.search(tokens, lengths, index) then builds conv0's input of a chunk with ONE launch (drn_gate_gather_packed) and runs the
-trunk as before.  The index is bound to the weights it was built from (is_current / refresh)."""
+trunk as before.  The index is bound to the weights it was built from (is_current / refresh).
+
+SearchIndex.build(..., quantize="mxfp8") keeps the prop_fc columns in block-scaled FP8 instead (the MX layout: OCP e4m3fn codes, one
+power-of-two scale per 32 columns; mx8_quantize below is the definition, drn_quantize_rows_mx8 its device twin): codes
+(P_total + 1, Dp) u8, scales (P_total + 1, Dp / 32) u8 and pos (P_total + 1, P) in the compute dtype -- Dp + Dp / 32 + P * itemsize
+bytes a row instead of (Dp + P) * itemsize.  drn_gate_gather_packed_q8 dequantises inside the same one launch.  A dequantised value is
+exact in fp32 and bf16, so the quantised index answers bit for bit like index.dequantized(), a plain index of the dequantised rows."""
 import weakref
 
 import numpy as np
@@ -20,18 +26,58 @@ from ._lib import DrnError
 from .store import FeatureStore, _upload
 
 
+MX8_BLOCK, MX8_EMIN = 32, -110
+QUANTIZE = (None, "mxfp8")
+
+
+def mx8_quantize(x):
+    """x (n, C) float32 / bfloat16 (finite), C % 32 == 0 -> (codes (n, C) uint8, scales (n, C / 32) uint8): THE DEFINITION of the
+    format.  Per block of 32 columns: amax = max |x| in fp32 = m * 2^k, m in [0.5, 1) (frexp); e = k - 9 if m <= 0.875 else k - 8 --
+    the smallest e with amax <= 448 * 2^e -- a zero block takes e = -110, and e is clamped to [-110, 127] (with the lower bound every
+    dequantised value is zero or a normal number in fp32 and bf16); scale byte = e + 127, an e8m0 exponent and the fp32 exponent
+    field of 2^e; code = e4m3fn(x * 2^-e), round to nearest even, the sign kept where the value rounds to zero."""
+    if x.dim() != 2 or x.shape[1] % MX8_BLOCK:
+        raise DrnError("mx8_quantize: x must be (n, C) with C a multiple of %d (got %s)" % (MX8_BLOCK, tuple(x.shape)))
+    n, C = x.shape
+    blocks = x.float().reshape(n, C // MX8_BLOCK, MX8_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    m, k = torch.frexp(amax)
+    e = torch.where(m <= 0.875, k - 9, k - 8)
+    e = torch.where(amax == 0, torch.full_like(e, MX8_EMIN), e).clamp(MX8_EMIN, 127)
+    codes = torch.ldexp(blocks, -e.unsqueeze(2)).to(torch.float8_e4m3fn).view(torch.uint8).reshape(n, C)
+    return codes, (e + 127).to(torch.uint8)
+
+
+def mx8_dequantize(codes, scales, dtype=torch.float32):
+    """float(code) * 2^(scale - 127) per block of 32 columns -> (n, C) in `dtype`: exact in float32 and in bfloat16.  (A code is
+    decoded through the table of all 256 e4m3fn values, built on the host.)"""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 \
+            or codes.shape[0] != scales.shape[0] or codes.shape[1] != scales.shape[1] * MX8_BLOCK:
+        raise DrnError("mx8_dequantize: codes (n, C) and scales (n, C / %d) must be uint8" % MX8_BLOCK)
+    n, C = codes.shape
+    table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(codes.device)
+    vals = table[codes.long()].reshape(n, C // MX8_BLOCK, MX8_BLOCK)
+    return torch.ldexp(vals, (scales.to(torch.int32) - 127).unsqueeze(2)).reshape(n, C).to(dtype)
+
+
 class SearchIndex(object):
     """names, index, nprops, D, dtype, device, nbytes and len() with FeatureStore's meaning (positions are store positions); rows,
     prop_off (device int32, the index's own copy of the store's table), pad_row (the position of the pad row), Dp (the zero-padded
     feature width the model's front runs on: 512 for D = 500 in bf16, D otherwise), P (position-embedding width).  The index holds no
-    reference to the store's features (only a weak one to the store, for refresh): the store may be dropped."""
+    reference to the store's features (only a weak one to the store, for refresh): the store may be dropped.
+    quantize: None, or "mxfp8" -- then rows is None and the table is codes (P_total + 1, Dp) u8 | scales (P_total + 1, Dp / 32) u8 |
+    pos (P_total + 1, P) in dtype, the pad row quantised like any other.  resident: the tensor that says where the index lives."""
 
     # Rows (videos x T) one build step projects by default.  A CHOICE, not a measurement: 8192 rows of D = 4096 in bf16 are 64 MiB of
     # pooled features and as much again of projected rows per step, and a GEMM of that height fills the device.
     BUILD_ROWS = 8192
 
     def __init__(self):
-        self.rows = self.prop_off = None
+        self.rows = self.prop_off = self.codes = self.scales = self.pos = self.quantize = None
+
+    @property
+    def resident(self):
+        return self.codes if self.rows is None else self.rows
 
     def __len__(self):
         return len(self.names)
@@ -39,9 +85,21 @@ class SearchIndex(object):
     ids_of = FeatureStore.ids_of
 
     @staticmethod
-    def bytes_of(proposals, width, dtype, videos):
-        """Device bytes of an index: the packed rows with the pad row, and prop_off (int32)."""
-        return (int(proposals) + 1) * int(width) * torch.empty((), dtype=dtype).element_size() + (int(videos) + 1) * 4
+    def bytes_of(proposals, width, dtype, videos, quantize=None, P=None):
+        """Device bytes of an index: the packed rows with the pad row, and prop_off (int32).  width = Dp + P.  quantize="mxfp8" needs
+        P, the position columns' share of width: a row is then Dp codes, Dp / 32 scales and P elements of dtype."""
+        if quantize not in QUANTIZE:
+            raise DrnError("SearchIndex: quantize must be None or \"mxfp8\" (got %r)" % (quantize,))
+        item = torch.empty((), dtype=dtype).element_size()
+        if quantize is None:
+            row = int(width) * item
+        else:
+            if P is None or not 0 <= int(P) <= int(width) or (int(width) - int(P)) % MX8_BLOCK:
+                raise DrnError("SearchIndex: a quantised row needs P, and width - P a multiple of %d (got width %s, P %s)"
+                               % (MX8_BLOCK, width, P))
+            Dp = int(width) - int(P)
+            row = Dp + Dp // MX8_BLOCK + int(P) * item
+        return (int(proposals) + 1) * row + (int(videos) + 1) * 4
 
     @staticmethod
     def _stamp(model):
@@ -49,11 +107,15 @@ class SearchIndex(object):
         return tuple((id(p), p.data_ptr(), p._version) for p in ps) + (model.compute_dtype,)
 
     @classmethod
-    def build(cls, model, store, chunk=None, max_bytes=None):
+    def build(cls, model, store, chunk=None, max_bytes=None, quantize=None):
         """Walk the whole store once, in store order, in chunks of `chunk` videos (one shape: the last chunk is padded with position
         -1): store.gather on device positions with T = the store's largest proposal count -> model.prepare_input(split_gate=True)
         (cast, prop_fc, position embedding), eval mode under no_grad -> the real proposals' rows copied into the packed table on the
-        device, no host synchronisation.  Raises DrnError BEFORE anything is allocated when the index would exceed max_bytes."""
+        device, no host synchronisation.  Raises DrnError BEFORE anything is allocated when the index would exceed max_bytes.
+        quantize="mxfp8": each chunk's selected rows are quantised straight into codes / scales (one drn_quantize_rows_mx8 launch per
+        destination slice); max_bytes is checked against the quantised size."""
+        if quantize not in QUANTIZE:
+            raise DrnError("SearchIndex.build: quantize must be None or \"mxfp8\" (got %r)" % (quantize,))
         if model.training:
             raise DrnError("SearchIndex.build is inference only: call model.eval() first")
         if not store.feats.is_cuda:
@@ -71,11 +133,21 @@ class SearchIndex(object):
         self.T = int(self.nprops.max()) if len(self.names) else 0
         total = int(self.nprops.sum())
         self.pad_row = total
-        self.nbytes = self.bytes_of(total, self.Dp + self.P, self.dtype, len(self.names))
+        self.quantize = quantize
+        if quantize is not None and self.Dp % MX8_BLOCK:
+            raise DrnError("SearchIndex.build: quantize=%r needs a feature width that is a multiple of %d (the model's front runs on %d "
+                           "columns)" % (quantize, MX8_BLOCK, self.Dp))
+        self.nbytes = self.bytes_of(total, self.Dp + self.P, self.dtype, len(self.names), quantize=quantize, P=self.P)
         if max_bytes is not None and self.nbytes > max_bytes:
-            raise DrnError("SearchIndex: %d videos (%d proposals x %d, %s) need %d bytes on the device, max_bytes is %d"
-                           % (len(self.names), total, self.Dp + self.P, self.dtype, self.nbytes, max_bytes))
-        self.rows = torch.empty((total + 1, self.Dp + self.P), dtype=self.dtype, device=self.device)
+            raise DrnError("SearchIndex: %d videos (%d proposals x %d, %s%s) need %d bytes on the device, max_bytes is %d"
+                           % (len(self.names), total, self.Dp + self.P, self.dtype, ", " + quantize if quantize else "", self.nbytes,
+                              max_bytes))
+        if quantize is None:
+            self.rows = torch.empty((total + 1, self.Dp + self.P), dtype=self.dtype, device=self.device)
+        else:
+            self.codes = torch.empty((total + 1, self.Dp), dtype=torch.uint8, device=self.device)
+            self.scales = torch.empty((total + 1, self.Dp // MX8_BLOCK), dtype=torch.uint8, device=self.device)
+            self.pos = torch.empty((total + 1, self.P), dtype=self.dtype, device=self.device)
         self.prop_off = store.prop_off.clone()
         self._fill(model, store, chunk)
         return self
@@ -118,11 +190,16 @@ class SearchIndex(object):
                     raise DrnError("SearchIndex.build: the model's input stage did not produce the projected rows")
                 Z, G0 = prep.Z.view(Vc * T, Dp), prep.G0.view(Vc * T, Dp + self.P)
                 first = int(off[min(c * Vc, Nv)])
-                for idx, dst in ((plan[at:at + n], self.rows[first:first + n]),) + \
-                        (((plan[-1:], self.rows[self.pad_row:]),) if c == pad_chunk else ()):
-                    if idx.numel():
-                        dst[:, :Dp] = Z.index_select(0, idx)
-                        dst[:, Dp:] = G0[:, Dp:].index_select(0, idx)
+                for idx, lo, hi in ((plan[at:at + n], first, first + n),) + \
+                        (((plan[-1:], self.pad_row, self.pad_row + 1),) if c == pad_chunk else ()):
+                    if not idx.numel():
+                        continue
+                    if self.quantize is None:
+                        self.rows[lo:hi, :Dp] = Z.index_select(0, idx)
+                        self.rows[lo:hi, Dp:] = G0[:, Dp:].index_select(0, idx)
+                    else:
+                        ops.quantize_rows_mx8(Z.index_select(0, idx), self.codes[lo:hi], self.scales[lo:hi])
+                        self.pos[lo:hi] = G0[:, Dp:].index_select(0, idx)
                 at += n
         self.stamp = self._stamp(model)
         self._chunk, self._store = chunk, weakref.ref(store)
@@ -147,6 +224,18 @@ class SearchIndex(object):
             raise DrnError("SearchIndex.refresh: the store does not hold the index's videos and proposals on the GPU")
         self._fill(model, store, self._chunk)
         return self
+
+    def dequantized(self):
+        """A plain SearchIndex holding mx8_dequantize(codes, scales) next to pos in its rows -- what this index really holds, and the
+        index it answers like bit for bit.  The same names, tables and stamp: it is current for the same model."""
+        if self.quantize is None:
+            raise DrnError("SearchIndex.dequantized: this index is not quantised")
+        plain = SearchIndex()
+        for name in ("names", "index", "nprops", "D", "dtype", "device", "Dp", "P", "T", "pad_row", "prop_off", "stamp", "_chunk", "_store"):
+            setattr(plain, name, getattr(self, name))
+        plain.rows = torch.cat([mx8_dequantize(self.codes, self.scales, self.dtype), self.pos], dim=1)
+        plain.nbytes = self.bytes_of(self.pad_row, self.Dp + self.P, self.dtype, len(self.names))
+        return plain
 
     def check(self, model, what="SearchIndex"):
         if not self.is_current(model):

@@ -259,7 +259,8 @@ class mainModel(nn.Module):
         """forward_heads_shared for Q (sentence, video) pairs whose query-independent front is already in a drn_amd.SearchIndex:
         pair p is sentence pair_q[p] of the S encoded `gates` over the video at store position vids[pair_v[p]], its first T proposals
         (the pad row past them, and for a slot or position out of range).  vids (Vc,), pair_q / pair_v (Q,): contiguous int32 on the
-        device, read by the launch itself.  ONE launch (ops.gate_gather_packed) writes conv0's (Q, T, Dp+P) input -- no pooling, no
+        device, read by the launch itself.  ONE launch (ops.gate_gather_packed, or ops.gate_gather_packed_q8 on an index built with
+        quantize="mxfp8") writes conv0's (Q, T, Dp+P) input -- no pooling, no
         cast, no prop_fc, no position embedding, no level-0 index_select -- and the trunk is the one every forward runs, with the
         level-1.. gates gathered by pair_q.  A stale index raises before any launch.  Eval mode under torch.no_grad() only."""
         if self.training:
@@ -267,14 +268,18 @@ class mainModel(nn.Module):
         if torch.is_grad_enabled():
             raise DrnError("forward_heads_packed is inference only: run it under torch.no_grad()")
         index.check(self, "forward_heads_packed")
-        for t in (index.rows, vids, pair_q, pair_v) + tuple(gates):
+        for t in (index.resident, vids, pair_q, pair_v) + tuple(gates):
             if not t.is_cuda:
                 raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
         pad = index.Dp - index.D
         gate0 = F.pad(gates[0], (0, pad)) if pad else gates[0]
-        g0 = torch.empty((int(pair_q.numel()), int(T), index.Dp + index.P), dtype=index.dtype, device=index.rows.device)
-        ops.gate_gather_packed(index.rows, index.pad_row, index.prop_off, gate0.contiguous(), pair_q, pair_v, vids, g0, int(T), index.Dp,
-                               index.P, ops.dtype_code(index.rows))
+        g0 = torch.empty((int(pair_q.numel()), int(T), index.Dp + index.P), dtype=index.dtype, device=index.resident.device)
+        if index.quantize is None:
+            ops.gate_gather_packed(index.rows, index.pad_row, index.prop_off, gate0.contiguous(), pair_q, pair_v, vids, g0, int(T), index.Dp,
+                                   index.P, ops.dtype_code(index.rows))
+        else:                                              # block-scaled FP8 codes, dequantised inside the same one launch
+            ops.gate_gather_packed_q8(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off,
+                                      gate0.contiguous(), pair_q, pair_v, vids, g0, int(T), index.Dp, index.P, ops.dtype_code(g0))
         qidx = pair_q.long()
         return self._trunk_heads(g0, [None] + [g.index_select(0, qidx) for g in gates[1:]])
 

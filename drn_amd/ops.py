@@ -648,6 +648,52 @@ def gate_gather_packed(rows, pad_row, prop_off, gate, pq, pv, vids, out, L, C, P
         "drn_gate_gather_packed"))
 
 
+def quantize_rows_mx8(x, codes, scales):
+    """x (n, C) float32 / bfloat16, C % 32 == 0 -> codes (n, C) uint8 (OCP e4m3fn) and scales (n, C / 32) uint8 (e8m0: one
+    power-of-two scale per 32 columns), written in place by one launch (drn_quantize_rows_mx8; drn_amd.index.mx8_quantize is the
+    definition).  All three with unit column stride; codes / scales may be row slices of wider tables."""
+    for name, t, width in (("codes", codes, int(x.shape[-1])), ("scales", scales, int(x.shape[-1]) // 32)):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1 or tuple(t.shape) != (int(x.shape[0]), width):
+            raise _lib.DrnError("quantize_rows_mx8: %s must be a (%d, %d) uint8 tensor with unit column stride" % (name, x.shape[0], width))
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.DrnError("quantize_rows_mx8: x must be (n, C) with unit column stride")
+    _need_gpu(x, codes, scales)
+    _timed("quantize_rows_mx8", 0, lambda: check(lib().drn_quantize_rows_mx8(
+        _p(x), x.stride(0), int(x.shape[0]), int(x.shape[1]), _p(codes), codes.stride(0), _p(scales), scales.stride(0), dtype_code(x),
+        _stream()), "drn_quantize_rows_mx8"))
+
+
+def gate_gather_packed_q8(codes, scales, pos, pad_row, prop_off, gate, pq, pv, vids, out, L, C, P, dtype, pq_host=None):
+    """gate_gather_packed on a quantised index (drn_gate_gather_packed_q8): the gated columns of row src are
+    float(codes[src, c]) * 2^(scales[src, c // 32] - 127) -- codes (n_rows, >= C) and scales (n_rows, >= C / 32) uint8 as
+    quantize_rows_mx8 writes them -- and the position columns pos[src, :P] in out's dtype (pos None with P = 0).  Everything else as
+    there; the output is bit for bit gate_gather_packed's on rows holding the dequantised values."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or codes.stride(1) != 1 \
+            or scales.stride(1) != 1 or codes.shape[0] != scales.shape[0] or codes.shape[1] < C or scales.shape[1] * 32 < C:
+        raise _lib.DrnError("gate_gather_packed_q8: codes (n_rows, >= C) and scales (n_rows, >= C / 32) must be uint8 with unit column stride")
+    if (pos is None) != (P == 0) or (pos is not None and (pos.dim() != 2 or pos.stride(1) != 1 or pos.dtype != out.dtype
+                                                          or pos.shape[0] != codes.shape[0] or pos.shape[1] < P)):
+        raise _lib.DrnError("gate_gather_packed_q8: pos must be (n_rows, >= P) of out's dtype with unit column stride (None with P = 0)")
+    _need_gpu(codes, scales, pos, prop_off, gate, pq, pv, vids, out)
+    Q = int(pq.numel())
+    for name, t, n in (("pq", pq, Q), ("pv", pv, Q), ("vids", vids, int(vids.numel())), ("prop_off", prop_off, int(prop_off.numel()))):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n or n < 1:
+            raise _lib.DrnError("gate_gather_packed_q8: %s must be a contiguous 1-d int32 tensor (pq and pv of the same length)" % name)
+    if gate.dim() != 2 or gate.stride(1) != 1 or gate.dtype != torch.float32:
+        raise _lib.DrnError("gate_gather_packed_q8: gate must be (S, C) float32 with unit column stride")
+    if out.dim() != 3 or tuple(out.shape[:2]) != (Q, L) or not out.is_contiguous() or dtype_code(out) != dtype:
+        raise _lib.DrnError("gate_gather_packed_q8: out must be a contiguous (%d, %d, >= C + P) tensor of the given dtype" % (Q, L))
+    host = None
+    if pq_host is not None:
+        if pq_host.is_cuda or pq_host.dtype != torch.int32 or not pq_host.is_contiguous() or pq_host.numel() != Q:
+            raise _lib.DrnError("gate_gather_packed_q8: pq_host must be a contiguous int32 host tensor of %d entries" % Q)
+        host = ctypes.c_void_p(pq_host.data_ptr())
+    _timed("gate_gather_packed_q8", 0, lambda: check(lib().drn_gate_gather_packed_q8(
+        _p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
+        int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(gate), gate.stride(0), int(gate.shape[0]), _p(pq), host, _p(pv), _p(vids),
+        int(vids.numel()), _p(out), int(out.shape[2]), Q, L, C, P, dtype, _stream()), "drn_gate_gather_packed_q8"))
+
+
 def pool_props_lds_rows(B, D, dtype):
     """Rows of one video the LDS path of drn_pool_props holds for B clips of D elements (0: the element-wise path)."""
     return int(lib().drn_pool_props_lds_rows(int(B), int(D), int(dtype)))

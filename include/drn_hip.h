@@ -265,6 +265,25 @@ int drn_gate_gather_fwd(const void* z, int ld_z, const float* gate, int ldg, con
 int drn_gate_gather_packed(const void* rows, int ld_rows, int n_rows, int pad_row, const int32_t* prop_off, int Nv, const float* gate,
                            int ldg, int S, const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv,
                            const int32_t* vids, int Vc, void* out, int ld_out, int Q, int L, int C, int P, int dtype, void* stream);
+/* Rows in block-scaled FP8 (drn_amd/csrc/qindex.hip; the MX layout: OCP e4m3fn codes, one power-of-two scale per 32 columns).
+ * x (n, C) in `dtype`, unit column stride, C % 32 == 0 -> codes (n, C) and scales (n, C / 32), both uint8.  Per block of 32 columns:
+ *   amax = max |x| in fp32 = m * 2^k with m in [0.5, 1);  e = k - 9 if m <= 0.875 else k - 8 (the smallest e with amax <= 448 * 2^e),
+ *   e = -110 for a zero block, e clamped to [-110, 127];  scales[.] = e + 127 (an e8m0 exponent = the fp32 exponent field of 2^e);
+ *   codes[.] = e4m3fn(x * 2^-e), round to nearest even, the sign kept where the value rounds to zero;  value = float(code) * 2^e,
+ * which is exact in fp32 and in bf16.  drn_amd.index.mx8_quantize is the same definition on the host.  x and codes 16-byte aligned
+ * with row strides that are 16-byte multiples; bytes of codes / scales past a row's width are not written.  One launch, no workspace. */
+int drn_quantize_rows_mx8(const void* x, int ld_x, int n, int C, uint8_t* codes, int ld_codes, uint8_t* scales, int ld_scales, int dtype,
+                          void* stream);
+/* drn_gate_gather_packed on a quantised index: the C gated columns of row src are codes[src] / scales[src] as drn_quantize_rows_mx8
+ * writes them, the P position columns pos[src] in `dtype` (pos NULL with P = 0); pairs, slots, videos, the pad row, the clamps and
+ * pq_host as there:
+ *   out[p*L+t][c] = dtype(float(codes[src][c]) * 2^(scales[src][c/32] - 127) * gate[pq[p]][c]) for c < C
+ *   out[p*L+t][C+j] = pos[src][j] for j < P
+ * -- bit for bit drn_gate_gather_packed on rows that hold the dequantised values.  C % 32 == 0; ld_codes a multiple of 16. */
+int drn_gate_gather_packed_q8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos,
+                              int n_rows, int pad_row, const int32_t* prop_off, int Nv, const float* gate, int ldg, int S,
+                              const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids,
+                              int Vc, void* out, int ld_out, int Q, int L, int C, int P, int dtype, void* stream);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */

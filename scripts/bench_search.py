@@ -19,7 +19,14 @@
   --evaluate   instead of the above -> profiles/search_eval_bench.json: one evaluation pass over 8 batches of S = 8 annotated sentences
            (drn_amd.evaluate_search: search, drn_search_recall on the Hits, ONE copy at the end of the pass) beside the same batches
            scored on the host (search, Hits.tolist(), metrics.search_first_hits, per batch), on the store and on the index, eager and
-           by graph replay; same store, same protocol.  The two tables are compared."""
+           by graph replay; same store, same protocol.  The two tables are compared.
+
+  --quantized  instead of the above -> profiles/search_q8_bench.json: a SearchIndex built with quantize="mxfp8" (block-scaled FP8 codes,
+           dequantised inside drn_gate_gather_packed_q8) beside the plain index of the same store, by the same Grounders in one process:
+           nbytes of both (and SearchIndex.bytes_of, which they must equal), ms per build, ms per search (S in {1, 8}, T in {256, 32},
+           eager and by graph replay), the two gather kernels alone at 512 and 64 pairs, and -- from evaluate_search on random
+           annotations -- the two recall tables and the share of sentences whose first hit names the same video on both indexes.
+           The quantised Hits are compared field for field with those of index.dequantized()."""
 import argparse
 import json
 import os
@@ -275,12 +282,180 @@ def bench_kernel(index, T, Q, rounds, window_s=0.3):
                     "that figure is not an HBM rate"}
 
 
+def bench_q8_search(model, plain, q, ref, T, S, rounds, window_s=0.3):
+    """The plain index (the code every search on an index runs without this option) and the quantised one, interleaved."""
+    from drn_amd import Grounder
+    tok, qlen = sentences(S, 7)
+    eager, graphed = Grounder(model, top_k=10), Grounder(model, top_k=10, graph=True)
+    variants = {"plain_eager": lambda: eager.search(tok, qlen, plain, per_video=2),
+                "q8_eager": lambda: eager.search(tok, qlen, q, per_video=2),
+                "plain_graph": lambda: graphed.search(tok, qlen, plain, per_video=2),
+                "q8_graph": lambda: graphed.search(tok, qlen, q, per_video=2)}
+    hits = {k: fn() for k, fn in variants.items()}
+    twin = eager.search(tok, qlen, ref, per_video=2)
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(getattr(a, f), getattr(b, f)) for f in STATE)
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    res = {"T": T, "S": S, "videos": len(plain), "pairs_per_step": S * len(plain), "top_k": 10, "per_video": 2, "rounds": rounds,
+           "graph_captures": graphed.captures,
+           "q8_hits_equal_dequantized_twin": {"eager": same(hits["q8_eager"], twin), "graph": same(hits["q8_graph"], twin)},
+           "q8_hits_equal_plain": same(hits["q8_eager"], hits["plain_eager"]), "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_min": min(ts), "ms_per_search_max": max(ts),
+                              "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    v = res["variants"]
+    for mode in ("eager", "graph"):
+        diff = v["q8_" + mode]["ms_per_search_median"] - v["plain_" + mode]["ms_per_search_median"]
+        spread = v["plain_" + mode]["ms_per_search_max"] - v["plain_" + mode]["ms_per_search_min"]
+        res["q8_minus_plain_" + mode] = {"ms": diff, "plain_max_minus_min_ms": spread, "a_difference": abs(diff) > spread}
+    return res
+
+
+def bench_q8_build(model, store, rounds):
+    from drn_amd import SearchIndex
+    plain, q = SearchIndex.build(model, store), SearchIndex.build(model, store, quantize="mxfp8")
+    ts = {"plain": [], "q8": []}
+    for _ in range(max(rounds, 3)):
+        ts["plain"].append(window(lambda: SearchIndex.build(model, store), 1))
+        ts["q8"].append(window(lambda: SearchIndex.build(model, store, quantize="mxfp8"), 1))
+    total, width = int(store.nprops.sum()), plain.Dp + plain.P
+    item = torch.empty((), dtype=plain.dtype).element_size()
+    res = {"videos": len(store), "proposals": total, "store_nbytes": store.nbytes, "Dp": plain.Dp, "P": plain.P,
+           "plain_nbytes": plain.nbytes, "q8_nbytes": q.nbytes,
+           "plain_bytes_of": SearchIndex.bytes_of(total, width, plain.dtype, len(store)),
+           "q8_bytes_of": SearchIndex.bytes_of(total, width, plain.dtype, len(store), quantize="mxfp8", P=plain.P),
+           "plain_row_bytes": width * item, "q8_row_bytes": plain.Dp + plain.Dp // 32 + plain.P * item,
+           "q8_storage_nbytes": sum(t.untyped_storage().nbytes() for t in (q.codes, q.scales, q.pos, q.prop_off))}
+    res["q8_over_plain_bytes"] = res["q8_nbytes"] / res["plain_nbytes"]
+    for k in ts:
+        res[k + "_ms_per_build_median"], res[k + "_ms_per_build_rounds"] = statistics.median(ts[k]), ts[k]
+    return plain, q, res
+
+
+def bench_q8_kernels(plain, q, T, Q, rounds, window_s=0.3):
+    """bench_kernel's protocol for both gather kernels on the same pairs, interleaved round by round."""
+    from drn_amd import ops
+    dev = plain.rows.device
+    S = Q // NV
+    gate = torch.randn(S, plain.Dp, device=dev)
+    pair = torch.arange(Q, dtype=torch.int32, device=dev)
+    pq, pv = torch.div(pair, NV, rounding_mode="floor"), torch.remainder(pair, NV)
+    vids = torch.arange(NV, dtype=torch.int32, device=dev)
+    outs = [torch.empty((Q, T, plain.Dp + plain.P), dtype=plain.dtype, device=dev) for _ in range(2)]
+    launch = {"gate_gather_packed": lambda o: ops.gate_gather_packed(plain.rows, plain.pad_row, plain.prop_off, gate, pq, pv, vids, o, T,
+                                                                     plain.Dp, plain.P, ops.BF16),
+              "gate_gather_packed_q8": lambda o: ops.gate_gather_packed_q8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, gate, pq, pv,
+                                                                           vids, o, T, q.Dp, q.P, ops.BF16)}
+
+    def run(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(outs[i & 1])
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    reps = {}
+    for k, fn in launch.items():
+        run(fn, 10)
+        reps[k] = max(20, int(window_s / (run(fn, 20) * 1e-6)))
+    ts = {k: [] for k in launch}
+    for _ in range(rounds):
+        for k, fn in launch.items():
+            ts[k].append(run(fn, reps[k]))
+    written = outs[0].numel() * outs[0].element_size()
+    res = {"Q": Q, "T": T, "C": plain.Dp, "P": plain.P, "dtype": "bf16", "bytes_written": written,
+           "note": "launch-inclusive; both kernels write the same bytes; the quantised one reads 4736 instead of 8704 bytes per source row"}
+    for k in launch:
+        us = statistics.median(ts[k])
+        res[k] = {"us_median": us, "us_min": min(ts[k]), "us_max": max(ts[k]), "us_rounds": ts[k], "launches_per_window": reps[k],
+                  "written_bytes_per_s": written / (us * 1e-6)}
+    return res
+
+
+def bench_q8_recall(model, plain, q, T, S=8, nbatches=8):
+    """evaluate_search on both indexes over bench_evaluate's batches (random annotations, synthetic weights: the recalls say nothing
+    about the model, only how far the two indexes' answers are apart), and the first hits' videos side by side."""
+    from drn_amd import Grounder, evaluate_search
+    ious, topks, kv = (0.5, 0.7), (1, 10), 2
+    g = torch.Generator().manual_seed(T)
+    batches = []
+    for b in range(nbatches):
+        tok, qlen = sentences(S, 100 + b)
+        start = torch.rand(S, generator=g, dtype=torch.float64) * 0.5
+        gt = torch.stack([start, start + 0.1 + torch.rand(S, generator=g, dtype=torch.float64) * 0.4], dim=1)
+        batches.append((["V%03d" % ((b * S + i) % NV) for i in range(S)], tok, qlen, gt))
+    grounder = Grounder(model, top_k=10)
+    res = {"T": T, "sentences": S * nbatches, "ious": list(ious), "topks": list(topks), "per_video": kv,
+           "note": "synthetic weights and random annotations: these recalls say nothing about the model"}
+    tables = {}
+    for name, where in (("plain", plain), ("q8", q)):
+        r = evaluate_search(grounder, batches, where, ious=ious, topks=topks, per_video=kv)
+        tables[name] = r.first_hits
+        res[name] = {"moment": r.moment, "video": r.video}
+    res["first_hit_rows_equal"] = float((tables["plain"] == tables["q8"]).all(axis=1).mean())
+    same_video = same_top10 = 0
+    for _, tok, qlen, _ in batches:
+        a, b = grounder.search(tok, qlen, plain, per_video=kv), grounder.search(tok, qlen, q, per_video=kv)
+        same_video += int((a.video[:, 0] == b.video[:, 0]).sum())
+        same_top10 += int((a.video == b.video).all(dim=1).sum())
+    res["first_hit_same_video_share"] = same_video / (S * nbatches)
+    res["top10_same_videos_in_order_share"] = same_top10 / (S * nbatches)
+    return res
+
+
+def main_quantized(args):
+    from bench_store import build_store
+    out = args.out or os.path.join(ROOT, "profiles", "search_q8_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, both indexes resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s; min and max of the rounds beside it",
+                      "clock": "host clock around searches ending in a device synchronise; device events for the kernel windows",
+                      "what": "SearchIndex.build(quantize=\"mxfp8\") beside the plain SearchIndex of the same store; a difference smaller "
+                              "than the plain index's own max - min across rounds is no difference"},
+           "build": [], "search": [], "kernel": [], "recall": []}
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        plain, q, b = bench_q8_build(model, store, args.rounds)
+        res["build"].append(dict(b, T=T))
+        print(json.dumps({"build": res["build"][-1]}), flush=True)
+        ref = q.dequantized()
+        for S in (1, 8):
+            res["search"].append(bench_q8_search(model, plain, q, ref, T, S, args.rounds))
+            print(json.dumps({"search": res["search"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        del ref
+        for Q in (512, 64):
+            res["kernel"].append(bench_q8_kernels(plain, q, T, Q, args.rounds))
+            print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+        res["recall"].append(bench_q8_recall(model, plain, q, T))
+        print(json.dumps({"recall": res["recall"][-1]}), flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+        del store, plain, q
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate)")
+    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
+                                            "search_q8_bench.json with --quantized)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
+    ap.add_argument("--quantized", action="store_true", help="measure a SearchIndex built with quantize=\"mxfp8\" beside the plain index")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
@@ -288,6 +463,8 @@ def main():
         return main_shortlist(args)
     if args.evaluate:
         return main_evaluate(args)
+    if args.quantized:
+        return main_quantized(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
