@@ -1,0 +1,237 @@
+// conv0 of a search on a quantised index WITHOUT the gather (drn_amd.Grounder(conv0="mxfp8")): the block-scaled FP8 codes of the index
+// are conv0's A operand as they lie -- the 32-column blocks run along conv0's K dimension -- and the sentence gate, which the gather
+// kernel multiplies into the activations, multiplies conv0's weight instead:  (z * g) W = z (diag(g) W).
+//   drn_gate_quantize_weights_mx8  once per search: the S gated copies of conv0's feature weights in the index's own format
+//   drn_conv0_mx8                  per chunk: the implicit GEMM over three taps, reading index rows and gated weights from memory
+// drn_amd/index.py has both definitions in plain torch (mx8_gate_weights, mx8_conv0_reference).
+#include "mx8.h"
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// ---------------------------------------------------------------- gated weights
+// quantize_rows_mx8_kernel (qindex.hip) on rows that are products: row (s, tap, n) of Dp columns, column c = gate[s][c] * w[tap][n][c]
+// for c < D (ONE fp32 multiply) and zero for D <= c < Dp.  The same lane / block assignment and the same arithmetic (mx8.h).
+__global__ __launch_bounds__(256) void gate_quantize_weights_mx8_kernel(const float* __restrict__ w, int ld_w, const float* __restrict__ gate,
+                                                                        int ldg, int rows_per_s /* 3 * Cout */, int D, long total,
+                                                                        int gpr /* Dp / 16 */, uint8_t* __restrict__ codes, int ld_codes,
+                                                                        uint8_t* __restrict__ scales, int ld_scales) {
+  for (long b = (long)blockIdx.x * 256; b < total; b += (long)gridDim.x * 256) {
+    const long i = b + threadIdx.x;
+    const bool active = i < total;
+    const long row = active ? i / gpr : 0;
+    const int g = active ? (int)(i - row * gpr) : 0;
+    const int s = (int)(row / rows_per_s), wr = (int)(row - (long)s * rows_per_s);
+    float v[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int c = g * 16 + k;
+      const int cc = min(c, D - 1);
+      const float prod = gate[(long)s * ldg + cc] * w[(long)wr * ld_w + cc];
+      v[k] = (active && c < D) ? prod : 0.f;
+    }
+    u32x4 q;
+    const int e = mx8_quantize16(v, q);
+    if (!active) continue;
+    *(u32x4*)(codes + row * ld_codes + g * 16) = q;
+    if ((g & 1) == 0) scales[row * ld_scales + (g >> 1)] = (uint8_t)(e + 127);
+  }
+}
+
+extern "C" int drn_gate_quantize_weights_mx8(const float* w, int ld_w, const float* gate, int ldg, int S, int Cout, int D, int Dp,
+                                             uint8_t* wcodes, int ld_wcodes, uint8_t* wscales, int ld_wscales, void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(w && gate && wcodes && wscales, "drn_gate_quantize_weights_mx8: null pointer");
+  DRN_CHECK_ARG(S > 0 && Cout > 0 && D > 0 && Dp >= D, "drn_gate_quantize_weights_mx8: bad args (S %d, Cout %d, D %d, Dp %d)", S, Cout, D, Dp);
+  DRN_CHECK_ARG(Dp % MX8_BLOCK == 0, "drn_gate_quantize_weights_mx8: Dp = %d is not a multiple of the block of %d columns", Dp, MX8_BLOCK);
+  DRN_CHECK_ARG(ld_w >= D && ldg >= D && ld_wcodes >= Dp && ld_wscales >= Dp / MX8_BLOCK,
+                "drn_gate_quantize_weights_mx8: a row stride is shorter than its row");
+  DRN_CHECK_ARG(ld_wcodes % 16 == 0 && (((uintptr_t)wcodes) & 15) == 0,
+                "drn_gate_quantize_weights_mx8: wcodes and its row stride must be 16-byte multiples");
+  DRN_CHECK_ARG((long)S * 3 * Cout <= 0x7fffffffL, "drn_gate_quantize_weights_mx8: more than 2^31 rows");
+  const long total = (long)S * 3 * Cout * (Dp / 16);
+  gate_quantize_weights_mx8_kernel<<<ew_blocks(total, 256, 8192), 256, 0, (hipStream_t)stream>>>(w, ld_w, gate, ldg, 3 * Cout, D, total, Dp / 16,
+                                                                                             wcodes, ld_wcodes, wscales, ld_wscales);
+  return drn_launch_status("drn_gate_quantize_weights_mx8");
+}
+
+// ---------------------------------------------------------------- conv0 on the codes
+// One workgroup = 4 waves = 16 * MI output rows of ONE pair (an M tile never spans two pairs: they may belong to different sentences) x
+// up to 256 output channels, wave w owning channels [64 w, 64 w + 64) as 4 fragments of 16.  No LDS: both operands of
+// v_mfma_scale_f32_16x16x128_f8f6f4 come from memory directly, a lane's A fragment from one index row (row l & 15 of the fragment), its B
+// fragment from one gated-weight row (channel l & 15); the four waves read the same index rows and meet in the vector cache.
+// The operand map of the instruction, ESTABLISHED with one-hot probes on an MI355X and held by the exact-integer test
+// (tests/test_search_mx8conv_gpu.py) -- it is NOT "32 contiguous K per lane": with g = l >> 4, registers 0-3 of a lane's fragment hold
+// k = 16 g + 0..15 and registers 4-7 hold k = 64 + 16 g + 0..15 (two 16-byte loads 64 columns apart), while the lane's scale byte
+// (byte 0 of the scale register, op_sel 0) applies to K block g, k in [32 g, 32 g + 32), of row / column l & 15 -- values that OTHER
+// lanes hold (groups 2 (g & 1), 2 (g & 1) + 1, registers 0-3 for g < 2, registers 4-7 for g >= 2).
+// K runs tap by tap over ceil(C / 128) steps -- a 16-byte half or a block past C is zero codes (with scale byte 127: byte 0 would be
+// 2^-127, not zero, and 255 is NaN) -- then over P / 32 steps of
+// v_mfma_f32_16x16x32_bf16 on the position columns into the same accumulators (C/D: column l & 15, row 4 (l >> 4) + i, whatever the
+// operand format).  A tap row outside [0, L) is zero codes / zero position values.  No split-K, no atomics: an accumulator sums its K in
+// one fixed order, whatever else the launch holds.
+// Every address is a function of the tables and the work-item number, clamped as in gate_gather_packed_q8_kernel (pq into [0, S), the
+// slot and the video to the pad row, src into [0, n_rows), the channel into [0, Cout), the columns into [0, C)): a masked fragment is
+// loaded from its clamped address and then replaced by zeros, so no activation value and no mask moves an access.
+template <int MI, typename OUT>
+__global__ __launch_bounds__(256) void conv0_mx8_kernel(const uint8_t* __restrict__ codes, int ld_codes, const uint8_t* __restrict__ scales,
+                                                        int ld_scales, const bf16_t* __restrict__ pos, int ld_pos, int n_rows, int pad_row,
+                                                        const int* __restrict__ prop_off, int Nv, const uint8_t* __restrict__ wcodes,
+                                                        const uint8_t* __restrict__ wscales, const bf16_t* __restrict__ wpos, int S,
+                                                        const int* __restrict__ pq, const int* __restrict__ pv, const int* __restrict__ vids,
+                                                        int Vc, OUT* __restrict__ raw, int ld_raw, int Q, int L, int C, int P, int Cout) {
+  constexpr int NJ = 4;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int mtiles = (L + 16 * MI - 1) / (16 * MI), ngroups = (Cout + 255) / 256;
+  int b = blockIdx.x;
+  const int ng = b % ngroups;
+  b /= ngroups;
+  const int mt = b % mtiles, p = b / mtiles;
+  const int n0 = ng * 256 + wave * 64;
+  if (p >= Q || n0 >= Cout) return;                     // (wave-uniform; the kernel has no barrier)
+  const int q = min(max(pq[p], 0), S - 1), slot = pv[p];
+  const int vd = (slot >= 0 && slot < Vc) ? vids[slot] : -1;
+  int base = 0, cnt = 0;
+  if (vd >= 0 && vd < Nv) {
+    base = prop_off[vd];
+    cnt = prop_off[vd + 1] - base;
+  }
+  const int r = lane & 15, kq = lane >> 4;
+  const int t0 = mt * 16 * MI;
+  const int cblocks = C / MX8_BLOCK;
+  long ncol[NJ];                                         // this lane's weight row inside a (sentence, tap) plane, clamped
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) ncol[j] = min(n0 + 16 * j + r, Cout - 1);
+  f32x4 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int tap = 0; tap < 3; ++tap) {
+    long src[MI];
+    bool live[MI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int u = t0 + 16 * i + r + tap - 1;
+      live[i] = u >= 0 && u < L;
+      src[i] = min(max(u >= 0 && u < cnt ? base + u : pad_row, 0), n_rows - 1);
+    }
+    const long plane = ((long)q * 3 + tap) * Cout;
+    const uint8_t* wc = wcodes + plane * C;
+    const uint8_t* ws = wscales + plane * cblocks;
+    for (int k0 = 0; k0 < C; k0 += 128) {
+      const int c_lo = k0 + 16 * kq, c_hi = c_lo + 64;   // this lane's two runs of 16 columns ...
+      const int kb = k0 / MX8_BLOCK + kq;                // ... and the block of 32 columns its scale byte speaks for
+      const bool lo_in = c_lo < C, hi_in = c_hi < C, kin = kb < cblocks;
+      const int c_lo_c = min(c_lo, C - 16), c_hi_c = min(c_hi, C - 16), kbc = min(kb, cblocks - 1);
+      const u32x4 zero = {0u, 0u, 0u, 0u};
+      i32x8 a[MI], bw[NJ];
+      int sa[MI], sb[NJ];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const uint8_t* ap = codes + src[i] * ld_codes;
+        u32x4 lo = *(const u32x4*)(ap + c_lo_c), hi = *(const u32x4*)(ap + c_hi_c);
+        const unsigned sc = scales[src[i] * ld_scales + kbc];
+        lo = (lo_in && live[i]) ? lo : zero;
+        hi = (hi_in && live[i]) ? hi : zero;
+        a[i] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        sa[i] = (kin && live[i]) ? (int)sc : 127;
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const uint8_t* bp = wc + ncol[j] * C;
+        u32x4 lo = *(const u32x4*)(bp + c_lo_c), hi = *(const u32x4*)(bp + c_hi_c);
+        const unsigned sc = ws[ncol[j] * cblocks + kbc];
+        lo = lo_in ? lo : zero;
+        hi = hi_in ? hi : zero;
+        bw[j] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        sb[j] = kin ? (int)sc : 127;
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        if (n0 + 16 * j >= Cout) break;                  // (wave-uniform)
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], bw[j], acc[i][j], 0 /* cbsz: A is e4m3 */, 0 /* blgp: B is e4m3 */,
+                                                                       0, sa[i], 0, sb[j]);
+      }
+    }
+    for (int j0 = 0; j0 < P; j0 += 32) {
+      bf16x8 a[MI], bw[NJ];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const bf16x8 v = *(const bf16x8*)(pos + src[i] * ld_pos + j0 + 8 * kq);
+        a[i] = live[i] ? v : bf16x8{};
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) bw[j] = *(const bf16x8*)(wpos + ((long)tap * Cout + ncol[j]) * P + j0 + 8 * kq);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        if (n0 + 16 * j >= Cout) break;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], bw[j], acc[i][j], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int n = n0 + 16 * j + r;
+      if (n >= Cout) continue;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int t = t0 + 16 * i + 4 * kq + x;
+        if (t < L) raw[((long)p * L + t) * ld_raw + n] = (OUT)acc[i][j][x];
+      }
+    }
+}
+
+template <typename OUT>
+static void launch_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const bf16_t* pos, int ld_pos, int n_rows,
+                             int pad_row, const int* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const bf16_t* wpos, int S,
+                             const int* pq, const int* pv, const int* vids, int Vc, OUT* raw, int ld_raw, int Q, int L, int C, int P, int Cout,
+                             hipStream_t st) {
+  const int ngroups = cdiv(Cout, 256);
+#define CONV0_MX8_LAUNCH(MI)                                                                                                          \
+  conv0_mx8_kernel<MI, OUT><<<(unsigned)((long)Q * cdiv(L, 16 * MI) * ngroups), 256, 0, st>>>(                                        \
+      codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales, wpos, S, pq, pv, vids, Vc, raw, \
+      ld_raw, Q, L, C, P, Cout)
+  // rows of one pair per workgroup: as many as the sequence fills, up to 64
+  if (L <= 16) CONV0_MX8_LAUNCH(1);
+  else if (L <= 32) CONV0_MX8_LAUNCH(2);
+  else CONV0_MX8_LAUNCH(4);
+#undef CONV0_MX8_LAUNCH
+}
+
+extern "C" int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                             int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
+                             int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, void* raw,
+                             int ld_raw, int out_f32, int Q, int L, int C, int P, int Cout, void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && raw && (P == 0 || (pos && wpos)),
+                "drn_conv0_mx8: null pointer");
+  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
+                "drn_conv0_mx8: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", n_rows, pad_row, Nv, S,
+                Vc, Q, L, C, P, Cout);
+  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "drn_conv0_mx8: C = %d is not a multiple of the block of %d columns", C, MX8_BLOCK);
+  DRN_CHECK_ARG(P % 32 == 0, "drn_conv0_mx8: P = %d is not a multiple of the 32 columns of a position step", P);
+  DRN_CHECK_ARG(Cout % 16 == 0, "drn_conv0_mx8: Cout = %d is not a multiple of 16", Cout);
+  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL && (long)Q * cdiv(L, 16) * cdiv(Cout, 256) <= 0x7fffffffL, "drn_conv0_mx8: more than 2^31 rows");
+  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_raw >= Cout,
+                "drn_conv0_mx8: a row stride is shorter than its row");
+  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
+                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
+                "drn_conv0_mx8: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples");
+  if (pq_host)
+    for (int p = 0; p < Q; ++p)
+      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "drn_conv0_mx8: pair %d reads sentence %d of %d", p, (int)pq_host[p], S);
+  hipStream_t st = (hipStream_t)stream;
+  if (out_f32)
+    launch_conv0_mx8<float>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales,
+                            (const bf16_t*)wpos, S, pq, pv, vids, Vc, (float*)raw, ld_raw, Q, L, C, P, Cout, st);
+  else
+    launch_conv0_mx8<bf16_t>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales,
+                             (const bf16_t*)wpos, S, pq, pv, vids, Vc, (bf16_t*)raw, ld_raw, Q, L, C, P, Cout, st);
+  return drn_launch_status("drn_conv0_mx8");
+}

@@ -7,13 +7,7 @@
 //   e = -110 for a zero block, e clamped to [-110, 127];  scale byte = e + 127 (an e8m0 exponent = the fp32 exponent field of 2^e);
 //   code = e4m3fn(x * 2^-e), round to nearest even, the sign kept where the value rounds to zero;  value = float(code) * 2^e.
 // 2^e is a power of two and a code has 3 mantissa bits, so the value is exact in fp32 and in bf16.
-#include "vec.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-#define MX8_BLOCK 32
-#define MX8_EMIN (-110)
+#include "mx8.h"
 
 // ---------------------------------------------------------------- quantise rows
 // x (n, C) -> codes (n, C) u8, scales (n, C / 32) u8.  One lane owns 16 neighbouring columns of one row -- 16-byte loads of x (two
@@ -44,25 +38,9 @@ __global__ __launch_bounds__(256) void quantize_rows_mx8_kernel(const T* __restr
         for (int k = 0; k < N; ++k) v[j * N + k] = t[k];
       }
     }
-    float amax = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) amax = fmaxf(amax, fabsf(v[k]));
-    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-    // frexp on the bits: amax = (1 + frac / 2^23) * 2^(E - 127) = m * 2^(E - 126), m <= 0.875 <=> frac <= 0.75 * 2^23.  Zero and the
-    // fp32 subnormals have E = 0 and fall below the clamp, as the definition has them.
-    const unsigned bits = __float_as_uint(amax);
-    int e = (int)(bits >> 23) - 126 - 9 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = min(max(e, MX8_EMIN), 127);
-    const float inv = __uint_as_float((unsigned)(127 - e) << 23);       // 2^-e (e <= 121 for any fp32 amax: a normal number)
-    if (!active) continue;
     u32x4 w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int p = 0;
-      p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, p, false);
-      p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, p, true);
-      w[j] = (unsigned)p;
-    }
+    const int e = mx8_quantize16(v, w);          // (the arithmetic, shared with conv0's gated weights: mx8.h)
+    if (!active) continue;
     *(u32x4*)(codes + row * ld_codes + g * 16) = w;
     if ((g & 1) == 0) scales[row * ld_scales + (g >> 1)] = (uint8_t)(e + 127);
   }

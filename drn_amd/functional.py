@@ -843,6 +843,43 @@ def conv_block(xs, conv, bn, training, dtype, gate=None, up=None, relu=True, tai
     return list(res), None
 
 
+def conv0_mx8_weights(weight, gate0, D, Dp, out=None):
+    """conv0's operands for ops.conv0_mx8, made once per search: (wcodes (S, 3, Cout, Dp) u8, wscales (S, 3, Cout, Dp / 32) u8,
+    wpos (3, Cout, P) bf16 or None) from conv0's fp32 parameter `weight` (Cout, D + P, 3) and the level-0 gate `gate0` (S, D) fp32.
+    The tap-major fp32 copy (3, Cout, D + P) the launch reads comes out of the re-laid-copy cache (`packed`, keyed on the parameter's
+    version like every other copy); ONE launch (ops.gate_quantize_weights_mx8) gates and quantises its feature columns for all S
+    sentences, and the position columns are cast to bf16.  out: the three tensors to write into (a captured graph's static buffers)."""
+    Cout, P = int(weight.shape[0]), int(weight.shape[1]) - int(D)
+    S, dev = int(gate0.shape[0]), weight.device
+    w = packed(weight, (2, 0, 1), ops.F32)
+    if out is None:
+        out = (torch.empty((S, 3, Cout, Dp), dtype=torch.uint8, device=dev), torch.empty((S, 3, Cout, Dp // 32), dtype=torch.uint8, device=dev),
+               torch.empty((3, Cout, P), dtype=torch.bfloat16, device=dev) if P else None)
+    wcodes, wscales, wpos = out
+    ops.gate_quantize_weights_mx8(w[:, :, :D], gate0, D, Dp, wcodes, wscales)
+    if P:
+        wpos.copy_(w[:, :, D:])
+    return wcodes, wscales, wpos
+
+
+def conv0_mx8_block(index, wq, pair_q, pair_v, vids, L, conv, bn, gate, dt):
+    """conv0 -> eval BatchNorm -> ReLU (-> level-1 gate) of Q (sentence, video) pairs straight from a quantised SearchIndex:
+    ops.conv0_mx8 writes raw (Q, L, Cout) from the index's codes and the gated weights `wq` (conv0_mx8_weights), then the unfused
+    eval path's own launches (bn_eval_scale_shift + bn_apply_multi) as conv_block runs them -> (out, gated), gated None without gate."""
+    wcodes, wscales, wpos = wq
+    Q, Cout, dev, code = int(pair_q.numel()), int(conv.weight.shape[0]), index.codes.device, code_of(dt)
+    raw = torch.empty((Q, L, Cout), dtype=dt, device=dev)
+    ops.conv0_mx8(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off, wcodes, wscales, wpos, pair_q,
+                  pair_v, vids, raw, L, index.Dp, index.P)
+    ss = torch.empty((2, Cout), dtype=torch.float32, device=dev)
+    ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
+    out = torch.empty((Q, L, Cout), dtype=dt, device=dev)
+    gated = torch.empty((Q, L, Cout), dtype=dt, device=dev) if gate is not None else None
+    ops.bn_apply_multi([dict(raw=raw, ld_raw=Cout, ss=ss, out=out, ld_out=Cout, M=Q * L, L=L, up=None, ld_up=0, gate=gate, gated=gated,
+                             ld_gated=Cout)], Cout, code, relu=True)
+    return out, gated
+
+
 class _PlainConvFn(torch.autograd.Function):
     """Conv1d(k, stride, pad=(k-1)//2) [+ bias] [-> ReLU] without BatchNorm: the factory variants of model/basic_blocks.py:5-33
     that DRN itself never instantiates (use_bn=False) and the FPN top blocks (model/FPN.py:86-103).  Same implicit-GEMM

@@ -175,16 +175,24 @@ class Grounder(object):
     parameter and the WeightCopies epoch, and a call under another stamp captures again.  Running
     statistics changed IN PLACE keep their address and are re-read by the scale/shift launches of every replay.  `captures` counts the captures made.
     search() shares all of this: its per-chunk body is one more signature among the max_graphs, and that of search(candidates=)
-    another.  ground_stored() runs eagerly whatever `graph` says."""
+    another.  ground_stored() runs eagerly whatever `graph` says.
+    conv0="mxfp8": search (cartesian, videos=, candidates=), ground_stored and evaluate_search run conv0 on block-scaled FP8 MFMAs
+    straight from a SearchIndex built with quantize="mxfp8" (mainModel.forward_heads_packed(conv0="mxfp8")): no gather launch and no
+    (pairs, T, Dp + P) buffer; the sentence gate is folded into conv0's weights, which are quantised to the index's format ONCE per
+    search (one launch, outside a captured graph, into the buffer the graph reads).  Lossy: the scores differ from the default path's.
+    A store, a plain index or an fp32 model raise before any launch.  ground() is not affected."""
 
     # Pairs (sentence, video) per chunk that search() allows itself by default.  A CHOICE, not a measurement: conv0's input g0 holds
     # T * (D + 256) elements per pair -- 2.1 MiB at T = 256, D = 4096 in bf16 -- so 512 pairs are 1.1 GiB of g0, and the trunk's
     # activations a small multiple of that: a few GiB of a 288 GiB device, beside a store that is meant to fill most of it.
     SEARCH_PAIR_BUDGET = 512
 
-    def __init__(self, model, top_k=5, nms_overlap=0.45, fused=False, graph=False, max_graphs=4):
+    def __init__(self, model, top_k=5, nms_overlap=0.45, fused=False, graph=False, max_graphs=4, conv0=None):
         if int(top_k) < 1:
             raise DrnError("Grounder: top_k must be at least 1")
+        if conv0 not in (None, "mxfp8"):
+            raise DrnError("Grounder: conv0 must be None or \"mxfp8\" (got %r)" % (conv0,))
+        self.conv0 = conv0
         self.model, self.top_k, self.nms_overlap = model, int(top_k), float(nms_overlap)
         self.fused, self.graph, self.max_graphs = bool(fused), bool(graph), int(max_graphs)
         self._graphs = {}
@@ -348,6 +356,7 @@ class Grounder(object):
             raise DrnError("Grounder.search: per_video and top_k must be at least 1 (got %d, %d)" % (kv, K))
         if indexed:
             store.check(model, "Grounder.search")
+        model.check_conv0(self.conv0, store, "Grounder.search")
         if candidates is not None:
             return self._search_pairs(query_tokens, query_length, store, K, kv, candidates, chunk, pairs, T, resident.device)
         ids = np.arange(len(store), dtype=np.int32) if videos is None else store.ids_of(videos).numpy()
@@ -380,8 +389,13 @@ class Grounder(object):
         pair = torch.arange(S * Vc, dtype=torch.int32, device=dev)
         pair_q, pair_v = torch.div(pair, Vc, rounding_mode="floor"), torch.remainder(pair, Vc)
 
+        ng, mx = len(gates), self.conv0 is not None
+
         def body(vid, flag, pq, pv, seg, score, video, level, rank, n, *g):
-            if indexed:
+            if mx:                                               # g: the gates, then conv0's gated weights (made outside this body)
+                mom = self._select(kv, store, vid, pq, pv, list(g[:ng]), T, entry="forward_heads_packed", conv0=self.conv0,
+                                   conv0_weights=tuple(g[ng:]))
+            elif indexed:
                 mom = self._select(kv, store, vid, pq, pv, list(g), T, entry="forward_heads_packed")
             else:
                 feats, pse, _ = store.gather(vid, T=T)
@@ -390,16 +404,19 @@ class Grounder(object):
 
         ent = None
         if self.graph:
-            sig = ("search", store, S, Vc, T, kv, K)             # (the key keeps the store, whose addresses the graph holds, alive)
-            ent, _ = self._entry(sig, body, dev, lambda: [vids[0].clone(), first[0].clone(), pair_q, pair_v]
-                                 + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates])
+            sig = ("search", store, S, Vc, T, kv, K, self.conv0)  # (the key keeps the store, whose addresses the graph holds, alive)
+            ent, fresh = self._entry(sig, body, dev, lambda: [vids[0].clone(), first[0].clone(), pair_q, pair_v]
+                                     + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates] + self._conv0_weights(store, gates))
         if ent is None:
             state = ops.merge_state(S, K, dev)
+            wq = tuple(self._conv0_weights(store, gates))
             for c in range(nchunks):
-                body(vids[c], first[c], pair_q, pair_v, *(state + tuple(gates)))
+                body(vids[c], first[c], pair_q, pair_v, *(state + tuple(gates) + wq))
             return Hits(*state)
         for dst, src in zip(ent.inputs[10:], gates):
             dst.copy_(src)
+        if mx and not fresh:                                     # (a fresh capture made them from these very gates)
+            self._conv0_weights(store, gates, out=ent.inputs[10 + ng:])
         for c in range(nchunks):
             ent.inputs[0].copy_(vids[c])
             ent.inputs[1].copy_(first[c])
@@ -431,9 +448,19 @@ class Grounder(object):
         split = lambda row: tuple(row[a:b] for a, b in zip([0] + ends[:-1], ends))
         return torch.from_numpy(np.ascontiguousarray(host)).pin_memory().to(dev, non_blocking=True), split
 
-    def _pair_front(self, k, store, T, vid, pq, pv, gates):
+    def _conv0_weights(self, store, gates, out=None):
+        """conv0's gated, quantised weights for this search's sentences as a list (empty without conv0="mxfp8"): ONE launch per search,
+        whatever the number of chunks.  out: a captured graph's static copies, written in place."""
+        if self.conv0 is None:
+            return []
+        return list(self.model.conv0_mx8_weights(store, gates[0], out=None if out is None else tuple(out)))
+
+    def _pair_front(self, k, store, T, vid, pq, pv, gates, wq=()):
         """One step's pairs through the front and the trunk -> select_moments(k)'s five fields, one row per pair."""
         from .index import SearchIndex
+        if self.conv0 is not None:
+            return self._select(k, store, vid, pq, pv, list(gates), T, entry="forward_heads_packed", conv0=self.conv0,
+                                conv0_weights=tuple(wq))
         if isinstance(store, SearchIndex):
             return self._select(k, store, vid, pq, pv, list(gates), T, entry="forward_heads_packed")
         feats, pse, _ = store.gather(vid, T=T)
@@ -469,22 +496,28 @@ class Grounder(object):
         rows, split = self._upload_plan(plan, (np.arange(C) == 0).astype(np.int32).reshape(C, 1), dev)
         gates = [g.contiguous() for g in self.model.encode_query(query_tokens, query_length)]
 
+        ng, mx = len(gates), self.conv0 is not None
+
         def body(row, seg, score, video, level, rank, n, *g):
             vid, pq, pv, pvideo, poff, flag = split(row)
-            mom = self._pair_front(kv, store, T, vid, pq, pv, g)
+            mom = self._pair_front(kv, store, T, vid, pq, pv, g[:ng], g[ng:])
             return ops.merge_moments_ragged(mom, pvideo, poff, len(store), (seg, score, video, level, rank, n), flag)
 
         ent = None
         if self.graph:
-            sig = ("pairs", store, S, pairs, slots, T, kv, K)
-            ent, _ = self._entry(sig, body, dev, lambda: [rows[0].clone()] + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates])
+            sig = ("pairs", store, S, pairs, slots, T, kv, K, self.conv0)
+            ent, fresh = self._entry(sig, body, dev, lambda: [rows[0].clone()] + list(ops.merge_state(S, K, dev)) + [g.clone() for g in gates]
+                                     + self._conv0_weights(store, gates))
         if ent is None:
             state = ops.merge_state(S, K, dev)
+            wq = tuple(self._conv0_weights(store, gates))
             for c in range(C):
-                body(rows[c], *(state + tuple(gates)))
+                body(rows[c], *(state + tuple(gates) + wq))
             return Hits(*state)
         for dst, src in zip(ent.inputs[7:], gates):
             dst.copy_(src)
+        if mx and not fresh:
+            self._conv0_weights(store, gates, out=ent.inputs[7 + ng:])
         for c in range(C):
             ent.inputs[0].copy_(rows[c])
             ent.graph.replay()
@@ -503,6 +536,7 @@ class Grounder(object):
         resident = self._check_resident("Grounder.ground_stored", query_tokens, query_length, store)
         if isinstance(store, SearchIndex):
             store.check(self.model, "Grounder.ground_stored")
+        self.model.check_conv0(self.conv0, store, "Grounder.ground_stored")
         Q = int(query_tokens.shape[0])
         ids = store.ids_of(videos).numpy().astype(np.int64)
         if Q < 1 or ids.size != Q:
@@ -524,15 +558,16 @@ class Grounder(object):
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
         out = (torch.empty((Q + pairs, k, 2), dtype=torch.float32, device=dev), torch.empty((Q + pairs, k), dtype=torch.float32, device=dev),
                i32(Q + pairs, k), i32(Q + pairs, k), i32(Q + pairs))
+        wq = self._conv0_weights(store, gates)
         for c in range(C):
             vid, pq, pv, _, _, where = split(rows[c])
             where = where.long()
-            for dst, src in zip(out, self._pair_front(k, store, T, vid, pq, pv, gates)):
+            for dst, src in zip(out, self._pair_front(k, store, T, vid, pq, pv, gates, wq)):
                 dst.index_copy_(0, where, src)
         return Moments(*[t[:Q] for t in out])
 
 
-def search(model, query_tokens, query_length, store, top_k=5, nms_overlap=0.45, fused=False, **kw):
-    """Grounder(model, top_k, nms_overlap, fused).search(query_tokens, query_length, store, **kw) for a one-off question; keep a
-    Grounder to search by graph replay."""
-    return Grounder(model, top_k=top_k, nms_overlap=nms_overlap, fused=fused).search(query_tokens, query_length, store, **kw)
+def search(model, query_tokens, query_length, store, top_k=5, nms_overlap=0.45, fused=False, conv0=None, **kw):
+    """Grounder(model, top_k, nms_overlap, fused, conv0=conv0).search(query_tokens, query_length, store, **kw) for a one-off question;
+    keep a Grounder to search by graph replay."""
+    return Grounder(model, top_k=top_k, nms_overlap=nms_overlap, fused=fused, conv0=conv0).search(query_tokens, query_length, store, **kw)

@@ -60,6 +60,59 @@ def mx8_dequantize(codes, scales, dtype=torch.float32):
     return torch.ldexp(vals, (scales.to(torch.int32) - 127).unsqueeze(2)).reshape(n, C).to(dtype)
 
 
+def mx8_gate_weights(W, gate, D, Dp):
+    """The sentence gate folded into conv0's weight and quantised to the index's format: THE DEFINITION of what
+    drn_gate_quantize_weights_mx8 writes.  W: conv0's fp32 parameter (Cout, D + P, 3); gate: the level-0 gate (S, D) in fp32.
+    Wg[s, tap, n, c] = gate[s, c] * W[n, c, tap] for c < D (one fp32 multiply), zero for D <= c < Dp; the result is mx8_quantize of Wg
+    viewed as (S * 3 * Cout, Dp) -> (wcodes (S, 3, Cout, Dp) u8, wscales (S, 3, Cout, Dp / 32) u8), K contiguous as a B fragment
+    wants it."""
+    D, Dp = int(D), int(Dp)
+    if W.dim() != 3 or W.shape[2] != 3 or W.shape[1] < D or gate.dim() != 2 or gate.shape[1] != D or Dp < D or Dp % MX8_BLOCK:
+        raise DrnError("mx8_gate_weights: W must be (Cout, >= D, 3), gate (S, D), and Dp >= D a multiple of %d" % MX8_BLOCK)
+    S, Cout = int(gate.shape[0]), int(W.shape[0])
+    Wg = torch.zeros((S, 3, Cout, Dp), dtype=torch.float32, device=W.device)
+    Wg[..., :D] = gate.float()[:, None, None, :] * W.detach().float()[:, :D, :].permute(2, 0, 1)[None]
+    codes, scales = mx8_quantize(Wg.view(S * 3 * Cout, Dp))
+    return codes.view(S, 3, Cout, Dp), scales.view(S, 3, Cout, Dp // MX8_BLOCK)
+
+
+def mx8_conv0_reference(index, wcodes, wscales, Wpos, pair_q, pair_v, vids, L):
+    """The oracle of drn_conv0_mx8, in float64 on the host: raw (Q, L, Cout),
+      raw[p, t, n] = sum_tap sum_c dq(index)[src(p, t + tap - 1), c] * dq(w)[pair_q[p], tap, n, c]
+                   + sum_tap sum_j pos[src(p, t + tap - 1), j] * Wpos[tap, n, j]
+    index: anything with codes / scales / pos (None or width 0: no position part) / prop_off / pad_row as a quantised SearchIndex has
+    them; Wpos (3, Cout, P): W[n, D + j, tap] rounded to the index's dtype.  src(p, u), 0 <= u < L, is drn_gate_gather_packed_q8's
+    row: prop_off[v] + u while u is below video v = vids[pair_v[p]]'s proposal count (a video with more than L proposals is cut at L),
+    else pad_row, as for a slot or a position out of range.  A tap at u < 0 or u >= L contributes zero (the conv's own zero padding, not
+    the pad row).  No bias."""
+    cpu = lambda t: t.detach().cpu()
+    codes, scales, off = cpu(index.codes), cpu(index.scales), cpu(index.prop_off).long()
+    z = mx8_dequantize(codes, scales).double()
+    S, _, Cout, C = wcodes.shape
+    w = mx8_dequantize(cpu(wcodes).reshape(S * 3 * Cout, C), cpu(wscales).reshape(S * 3 * Cout, C // MX8_BLOCK)).double().view(S, 3, Cout, C)
+    pos = getattr(index, "pos", None)
+    pos = None if pos is None or pos.shape[1] == 0 or Wpos is None else cpu(pos).double()
+    wp = cpu(Wpos).double() if pos is not None else None
+    pq, pv, vd = cpu(pair_q).long().tolist(), cpu(pair_v).long().tolist(), cpu(vids).long().tolist()
+    L, Nv, pad = int(L), int(off.numel()) - 1, int(index.pad_row)
+    raw = torch.zeros((len(pq), L, Cout), dtype=torch.float64)
+    for p in range(len(pq)):
+        v = vd[pv[p]] if 0 <= pv[p] < len(vd) else -1
+        base, cnt = (int(off[v]), int(off[v + 1] - off[v])) if 0 <= v < Nv else (0, 0)
+        src = torch.tensor([base + u if u < cnt else pad for u in range(L)])
+        x = z[src]
+        xp = pos[src] if pos is not None else None
+        for tap in range(3):
+            lo, hi = max(0, 1 - tap), min(L, L + 1 - tap)                 # output rows t whose tap row u = t + tap - 1 is in [0, L)
+            if hi <= lo:
+                continue
+            u = slice(lo + tap - 1, hi + tap - 1)
+            raw[p, lo:hi] += x[u] @ w[pq[p], tap].t()
+            if xp is not None:
+                raw[p, lo:hi] += xp[u] @ wp[tap].t()
+    return raw
+
+
 class SearchIndex(object):
     """names, index, nprops, D, dtype, device, nbytes and len() with FeatureStore's meaning (positions are store positions); rows,
     prop_off (device int32, the index's own copy of the store's table), pad_row (the position of the pad row), Dp (the zero-padded

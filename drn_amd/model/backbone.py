@@ -20,15 +20,21 @@ class Backbone(nn.Module):
             self.add_module(name, conv_block(cin, cout, kernel_size=k, stride=stride))
             self.blocks.append(name)
 
-    def forward_from_stage(self, g0, gates, tail=None):
+    def forward_from_stage(self, g0, gates, tail=None, conv0=None):
         """g0: (B, T, D+P) channels-last = cat(q0 * prop_fc(x), position feats) (drn_amd.functional.input_stage);
         gates[i]: (B, C_i) fp32.  The gate of level i+1 is fused into level i's BN-apply pass.  g0 may arrive in float32
         inside a bfloat16 model (feature dim not a 16-byte multiple in bf16): conv0 then runs on the exact-f32 kernels
         and its outputs are cast to the model's compute dtype.  tail: the EmbedTail input_stage returned with g0 (conv0's
-        backward then produces the position-embedding gradients itself and skips those columns of its input gradient)."""
+        backward then produces the position-embedding gradients itself and skips those columns of its input gradient).
+        conv0: level 0's (out, gated) computed elsewhere (functional.conv0_mx8_block); g0 is then not read and the loop starts at
+        level 1."""
         outs, x = [], g0
         dt = self.compute_dtype
         for idx in range(self.num_layers):
+            if idx == 0 and conv0 is not None:
+                outs.append(DF.cast_act(conv0[0], dt))
+                x = DF.cast_act(conv0[1], dt) if conv0[1] is not None else None
+                continue
             nxt = gates[idx + 1] if idx + 1 < self.num_layers else None
             conv, bn = conv_bn(getattr(self, self.blocks[idx]), "Backbone." + self.blocks[idx])
             if idx == 0 and x.shape[2] > conv.weight.shape[1]:

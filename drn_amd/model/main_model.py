@@ -161,9 +161,10 @@ class mainModel(nn.Module):
         g0._drn_tail = tail          # rides on the tensor object to forward_trunk (a caller that replaces g0 simply loses it)
         return g0, gates
 
-    def _trunk_heads(self, g0, gates):
-        """Backbone (gates[1:] only: level 0 is already applied), FPN, heads -> (locations, box_cls, box_reg, iou_scores)."""
-        backbone_feats = self.backbone_net.forward_from_stage(g0, gates, tail=getattr(g0, "_drn_tail", None))
+    def _trunk_heads(self, g0, gates, conv0=None):
+        """Backbone (gates[1:] only: level 0 is already applied), FPN, heads -> (locations, box_cls, box_reg, iou_scores).
+        conv0: level 0's (out, gated) instead of g0 (forward_heads_packed(conv0="mxfp8"))."""
+        backbone_feats = self.backbone_net.forward_from_stage(g0, gates, tail=getattr(g0, "_drn_tail", None), conv0=conv0)
         feats = self.fpn.forward_nlc(backbone_feats)
         head = self.fcos.head
         logits, reg, iou, geo = head.forward_nlc(feats)
@@ -255,22 +256,61 @@ class mainModel(nn.Module):
         ops.gate_gather_fwd(prep.Z, D, gate0.contiguous(), pos, ld_pos, vid, V, g0, D + P, Q, T, D, P, code, vid_host=vid_host)
         return self._trunk_heads(g0, gates)
 
-    def forward_heads_packed(self, index, vids, pair_q, pair_v, gates, T):
+    CONV0 = (None, "mxfp8")
+
+    def check_conv0(self, conv0, index, what):
+        """The refusals of the conv0="mxfp8" path, before any launch: the mode's name, a quantised SearchIndex, a bfloat16 model."""
+        from ..index import SearchIndex
+        if conv0 not in self.CONV0:
+            raise DrnError("%s: conv0 must be None or \"mxfp8\" (got %r)" % (what, conv0))
+        if conv0 is None:
+            return
+        if not isinstance(index, SearchIndex):
+            raise DrnError("%s: conv0=\"mxfp8\" reads a SearchIndex built with quantize=\"mxfp8\", not a feature store" % what)
+        if index.quantize != "mxfp8":
+            raise DrnError("%s: conv0=\"mxfp8\" needs an index built with quantize=\"mxfp8\" (this one is plain)" % what)
+        if self.compute_dtype != torch.bfloat16 or index.dtype != torch.bfloat16:
+            raise DrnError("%s: conv0=\"mxfp8\" needs a bfloat16 model (the position columns run on bf16 MFMAs); this one computes in %s"
+                           % (what, self.compute_dtype))
+
+    def conv0_mx8_weights(self, index, gate0, out=None):
+        """The operands of conv0 on block-scaled FP8 MFMAs for the S sentences of `gate0` (encode_query's level-0 gate, (S, D) fp32):
+        DF.conv0_mx8_weights on backbone conv0's weight at the index's widths -- one launch, made once per search."""
+        from .basic_blocks import conv_bn
+        conv, _ = conv_bn(getattr(self.backbone_net, self.backbone_net.blocks[0]), "Backbone.forward_conv0")
+        return DF.conv0_mx8_weights(conv.weight, gate0.contiguous(), index.D, index.Dp, out=out)
+
+    def forward_heads_packed(self, index, vids, pair_q, pair_v, gates, T, conv0=None, conv0_weights=None):
         """forward_heads_shared for Q (sentence, video) pairs whose query-independent front is already in a drn_amd.SearchIndex:
         pair p is sentence pair_q[p] of the S encoded `gates` over the video at store position vids[pair_v[p]], its first T proposals
         (the pad row past them, and for a slot or position out of range).  vids (Vc,), pair_q / pair_v (Q,): contiguous int32 on the
         device, read by the launch itself.  ONE launch (ops.gate_gather_packed, or ops.gate_gather_packed_q8 on an index built with
         quantize="mxfp8") writes conv0's (Q, T, Dp+P) input -- no pooling, no
         cast, no prop_fc, no position embedding, no level-0 index_select -- and the trunk is the one every forward runs, with the
-        level-1.. gates gathered by pair_q.  A stale index raises before any launch.  Eval mode under torch.no_grad() only."""
+        level-1.. gates gathered by pair_q.  A stale index raises before any launch.  Eval mode under torch.no_grad() only.
+        conv0="mxfp8" (a quantised index, a bfloat16 model): there is no g0 buffer and no gather launch -- conv0 reads the index's
+        codes in place on block-scaled FP8 MFMAs (ops.conv0_mx8), with the level-0 gate folded into its weights, which are quantised
+        to the index's format as well (conv0_weights: conv0_mx8_weights(index, gates[0]), made here when not given) -- then the
+        unfused eval path's BatchNorm / ReLU / level-1 gate launches; blocks 1 and 2, the FPN and the heads run as ever.  Lossy in one
+        more place than the quantised index: the gated weights' own rounding to e4m3."""
         if self.training:
             raise DrnError("forward_heads_packed is inference only: call model.eval() first")
         if torch.is_grad_enabled():
             raise DrnError("forward_heads_packed is inference only: run it under torch.no_grad()")
         index.check(self, "forward_heads_packed")
+        self.check_conv0(conv0, index, "forward_heads_packed")
         for t in (index.resident, vids, pair_q, pair_v) + tuple(gates):
             if not t.is_cuda:
                 raise DrnError("drn_amd.mainModel runs on an MI355X only (inputs on %s); no CPU fallback" % t.device)
+        if conv0 is not None:
+            from .basic_blocks import conv_bn
+            wq = self.conv0_mx8_weights(index, gates[0]) if conv0_weights is None else conv0_weights
+            qidx = pair_q.long()
+            conv, bn = conv_bn(getattr(self.backbone_net, self.backbone_net.blocks[0]), "Backbone.forward_conv0")
+            c0 = DF.conv0_mx8_block(index, wq, pair_q, pair_v, vids, int(T), conv, bn, gates[1].index_select(0, qidx), self.compute_dtype)
+            if self.taps is not None:
+                self.taps["conv0_mx8"] = c0
+            return self._trunk_heads(None, [None] + [g.index_select(0, qidx) for g in gates[1:]], conv0=c0)
         pad = index.Dp - index.D
         gate0 = F.pad(gates[0], (0, pad)) if pad else gates[0]
         g0 = torch.empty((int(pair_q.numel()), int(T), index.Dp + index.P), dtype=index.dtype, device=index.resident.device)

@@ -694,6 +694,76 @@ def gate_gather_packed_q8(codes, scales, pos, pad_row, prop_off, gate, pq, pv, v
         int(vids.numel()), _p(out), int(out.shape[2]), Q, L, C, P, dtype, _stream()), "drn_gate_gather_packed_q8"))
 
 
+def gate_quantize_weights_mx8(w, gate, D, Dp, wcodes, wscales):
+    """conv0's gated weights of S sentences in the index's block-scaled FP8 format, one launch (drn_gate_quantize_weights_mx8;
+    drn_amd.index.mx8_gate_weights is the definition): w (3, Cout, >= D) float32, tap-major with unit column stride and contiguous
+    rows (functional.packed(weight, (2, 0, 1), F32)), gate (S, >= D) float32 -> wcodes (S, 3, Cout, >= Dp) and wscales
+    (S, 3, Cout, >= Dp / 32) uint8, written in place; their leading three dims contiguous (column slices of wider buffers are allowed),
+    columns [D, Dp) zero codes."""
+    D, Dp = int(D), int(Dp)
+    if w.dim() != 3 or w.shape[0] != 3 or w.dtype != torch.float32 or w.stride(2) != 1 or w.stride(0) != w.shape[1] * w.stride(1) \
+            or w.shape[2] < D:
+        raise _lib.DrnError("gate_quantize_weights_mx8: w must be (3, Cout, >= D) float32, tap-major with unit column stride")
+    if gate.dim() != 2 or gate.stride(1) != 1 or gate.dtype != torch.float32 or gate.shape[1] < D:
+        raise _lib.DrnError("gate_quantize_weights_mx8: gate must be (S, >= D) float32 with unit column stride")
+    S, Cout = int(gate.shape[0]), int(w.shape[1])
+    if D < 1 or Dp < D or Dp % 32:
+        raise _lib.DrnError("gate_quantize_weights_mx8: Dp = %d must be a multiple of 32 and at least D = %d" % (Dp, D))
+    for name, t, width in (("wcodes", wcodes, Dp), ("wscales", wscales, Dp // 32)):
+        if t.dtype != torch.uint8 or t.dim() != 4 or tuple(t.shape[:3]) != (S, 3, Cout) or t.shape[3] < width or t.stride(3) != 1 \
+                or t.stride(1) != Cout * t.stride(2) or t.stride(0) != 3 * Cout * t.stride(2):
+            raise _lib.DrnError("gate_quantize_weights_mx8: %s must be a (%d, 3, %d, >= %d) uint8 tensor with unit column stride"
+                                % (name, S, Cout, width))
+    _need_gpu(w, gate, wcodes, wscales)
+    _timed("gate_quantize_weights_mx8", 0, lambda: check(lib().drn_gate_quantize_weights_mx8(
+        _p(w), w.stride(1), _p(gate), gate.stride(0), S, Cout, D, Dp, _p(wcodes), wcodes.stride(2), _p(wscales), wscales.stride(2),
+        _stream()), "drn_gate_quantize_weights_mx8"))
+
+
+def conv0_mx8(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, pv, vids, raw, L, C, P, pq_host=None):
+    """conv0 (k = 3, stride 1, pad 1, no bias) of the input gate_gather_packed_q8 would have written, straight from the quantised
+    index on block-scaled FP8 MFMAs (drn_conv0_mx8; drn_amd.index.mx8_conv0_reference is the definition): codes / scales / pos /
+    pad_row / prop_off / pq / pv / vids / pq_host as there, with pos in bfloat16; wcodes (S, 3, Cout, C) and wscales
+    (S, 3, Cout, C / 32) as gate_quantize_weights_mx8 writes them, contiguous; wpos (3, Cout, P) bfloat16 contiguous (None with
+    P = 0): conv0's position weights, tap-major.  raw: (Q, L, Cout) contiguous, bfloat16 or float32, written in place.
+    C % 32 == 0, P % 32 == 0, Cout % 16 == 0."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or codes.stride(1) != 1 \
+            or scales.stride(1) != 1 or codes.shape[0] != scales.shape[0] or codes.shape[1] < C or scales.shape[1] * 32 < C:
+        raise _lib.DrnError("conv0_mx8: codes (n_rows, >= C) and scales (n_rows, >= C / 32) must be uint8 with unit column stride")
+    if C < 32 or C % 32 or P < 0 or P % 32:
+        raise _lib.DrnError("conv0_mx8: C = %d and P = %d must be multiples of 32 (C at least 32)" % (C, P))
+    if wcodes.dtype != torch.uint8 or wscales.dtype != torch.uint8 or wcodes.dim() != 4 or wscales.dim() != 4 or not wcodes.is_contiguous() \
+            or not wscales.is_contiguous() or wcodes.shape[1] != 3 or wcodes.shape[3] != C \
+            or tuple(wscales.shape) != tuple(wcodes.shape[:3]) + (C // 32,):
+        raise _lib.DrnError("conv0_mx8: wcodes (S, 3, Cout, C) and wscales (S, 3, Cout, C / 32) must be contiguous uint8")
+    S, Cout = int(wcodes.shape[0]), int(wcodes.shape[2])
+    if Cout % 16:
+        raise _lib.DrnError("conv0_mx8: Cout = %d is not a multiple of 16" % Cout)
+    if (pos is None) != (P == 0) or (pos is not None and (pos.dim() != 2 or pos.stride(1) != 1 or pos.dtype != torch.bfloat16
+                                                          or pos.shape[0] != codes.shape[0] or pos.shape[1] < P)):
+        raise _lib.DrnError("conv0_mx8: pos must be (n_rows, >= P) bfloat16 with unit column stride (None with P = 0)")
+    if (wpos is None) != (P == 0) or (wpos is not None and (wpos.dtype != torch.bfloat16 or tuple(wpos.shape) != (3, Cout, P)
+                                                            or not wpos.is_contiguous())):
+        raise _lib.DrnError("conv0_mx8: wpos must be a contiguous (3, %d, %d) bfloat16 tensor (None with P = 0)" % (Cout, P))
+    _need_gpu(codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, raw)
+    Q = int(pq.numel())
+    for name, t, n in (("pq", pq, Q), ("pv", pv, Q), ("vids", vids, int(vids.numel())), ("prop_off", prop_off, int(prop_off.numel()))):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n or n < 1:
+            raise _lib.DrnError("conv0_mx8: %s must be a contiguous 1-d int32 tensor (pq and pv of the same length)" % name)
+    if raw.dim() != 3 or tuple(raw.shape) != (Q, L, Cout) or not raw.is_contiguous() or raw.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.DrnError("conv0_mx8: raw must be a contiguous (%d, %d, %d) bfloat16 or float32 tensor" % (Q, L, Cout))
+    host = None
+    if pq_host is not None:
+        if pq_host.is_cuda or pq_host.dtype != torch.int32 or not pq_host.is_contiguous() or pq_host.numel() != Q:
+            raise _lib.DrnError("conv0_mx8: pq_host must be a contiguous int32 host tensor of %d entries" % Q)
+        host = ctypes.c_void_p(pq_host.data_ptr())
+    flops = 2.0 * Q * L * Cout * 3 * (C + P)
+    _timed("conv0_mx8", flops, lambda: check(lib().drn_conv0_mx8(
+        _p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
+        int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(wcodes), _p(wscales), _p(wpos), S, _p(pq), host, _p(pv), _p(vids),
+        int(vids.numel()), _p(raw), Cout, int(raw.dtype == torch.float32), Q, L, C, P, Cout, _stream()), "drn_conv0_mx8"))
+
+
 def pool_props_lds_rows(B, D, dtype):
     """Rows of one video the LDS path of drn_pool_props holds for B clips of D elements (0: the element-wise path)."""
     return int(lib().drn_pool_props_lds_rows(int(B), int(D), int(dtype)))

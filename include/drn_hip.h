@@ -284,6 +284,28 @@ int drn_gate_gather_packed_q8(const uint8_t* codes, int ld_codes, const uint8_t*
                               int n_rows, int pad_row, const int32_t* prop_off, int Nv, const float* gate, int ldg, int S,
                               const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids,
                               int Vc, void* out, int ld_out, int Q, int L, int C, int P, int dtype, void* stream);
+/* conv0 on a quantised index without the gather (csrc/qconv.hip): the sentence gate multiplies conv0's WEIGHT instead of its input,
+ * (z * g) W = z (diag(g) W), and the gated weights are quantised to the index's own format.
+ * drn_gate_quantize_weights_mx8: w (3, Cout, >= D) fp32, tap-major (w[tap][n][c] = conv0.weight[n][c][tap], row stride ld_w), gate
+ * (S, >= D) fp32 ->
+ *   wcodes (S, 3, Cout, Dp) / wscales (S, 3, Cout, Dp/32) = drn_quantize_rows_mx8's format of the fp32 products gate[s][c] * w[tap][n][c],
+ * columns [D, Dp) zero -- byte for byte drn_amd.index.mx8_gate_weights.  Dp % 32 == 0, D <= Dp; ld_wcodes a multiple of 16 and wcodes
+ * 16-byte aligned (row strides of the (S*3*Cout) rows; bytes past a row's width are not written).  One launch for all S sentences. */
+int drn_gate_quantize_weights_mx8(const float* w, int ld_w, const float* gate, int ldg, int S, int Cout, int D, int Dp, uint8_t* wcodes,
+                                  int ld_wcodes, uint8_t* wscales, int ld_wscales, void* stream);
+/* drn_conv0_mx8: the k = 3, stride 1, pad 1 convolution of the (Q, L, C + P) input drn_gate_gather_packed_q8 would have written,
+ * straight from the index (the same tables, clamps and pq_host refusal), as an implicit GEMM over the three taps:
+ *   raw[p*L+t][n] = sum_tap sum_c  dq(codes, scales)[src(p, t+tap-1)][c] * dq(wcodes, wscales)[pq[p]][tap][n][c]
+ *                 + sum_tap sum_j  pos[src(p, t+tap-1)][j] * wpos[tap][n][j]
+ * the feature part on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3, the scale bytes as they lie), the position part on
+ * v_mfma_f32_16x16x32_bf16 into the same fp32 accumulators; a tap outside [0, L) contributes zero.  No bias, no split-K, no atomics:
+ * a row's value does not depend on which other pairs share the launch.  wcodes (S, 3, Cout, C) / wscales (S, 3, Cout, C/32) contiguous;
+ * pos (n_rows, >= P) and wpos (3, Cout, P) bf16 (NULL with P = 0); raw (Q*L, >= Cout) bf16, or fp32 with out_f32.
+ * C % 32 == 0, P % 32 == 0, Cout % 16 == 0; codes / pos rows 16-byte aligned. */
+int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                  int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos, int S,
+                  const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids, int Vc,
+                  void* raw, int ld_raw, int out_f32, int Q, int L, int C, int P, int Cout, void* stream);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */

@@ -26,7 +26,14 @@
            nbytes of both (and SearchIndex.bytes_of, which they must equal), ms per build, ms per search (S in {1, 8}, T in {256, 32},
            eager and by graph replay), the two gather kernels alone at 512 and 64 pairs, and -- from evaluate_search on random
            annotations -- the two recall tables and the share of sentences whose first hit names the same video on both indexes.
-           The quantised Hits are compared field for field with those of index.dequantized()."""
+           The quantised Hits are compared field for field with those of index.dequantized().
+
+  --mx-conv0   instead of the above -> profiles/search_mx8conv_bench.json: the SAME quantised index searched by Grounder(conv0="mxfp8")
+           (conv0 on block-scaled FP8 MFMAs straight from the codes, the sentence gate folded into quantised weights) beside the default
+           Grounder (drn_gate_gather_packed_q8, then conv0 on bf16 MFMAs), in one process: ms per search (S in {1, 8}, T in {256, 32},
+           eager and by graph replay), drn_conv0_mx8 alone beside gather + conv0 GEMM alone at 512 and 64 pairs, the once-per-search
+           weights launch alone, the first-hit agreement and evaluate_search recalls of the two modes on random annotations, and the
+           largest ratio of drn_conv0_mx8's error to its derived bound on the random case of tests/test_search_mx8conv_gpu.py."""
 import argparse
 import json
 import os
@@ -448,6 +455,176 @@ def main_quantized(args):
     print("wrote", out)
 
 
+def bench_mx_search(model, q, T, S, rounds, window_s=0.3):
+    """The default path on the quantised index (gather, then conv0 on bf16 MFMAs) and conv0="mxfp8" on the same index, interleaved."""
+    from drn_amd import Grounder
+    tok, qlen = sentences(S, 7)
+    g = {"default_eager": Grounder(model, top_k=10), "mx_eager": Grounder(model, top_k=10, conv0="mxfp8"),
+         "default_graph": Grounder(model, top_k=10, graph=True), "mx_graph": Grounder(model, top_k=10, graph=True, conv0="mxfp8")}
+    variants = {k: (lambda gr=gr: gr.search(tok, qlen, q, per_video=2)) for k, gr in g.items()}
+    hits = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(getattr(hits[a], f), getattr(hits[b], f)) for f in STATE)
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    res = {"T": T, "S": S, "videos": len(q), "pairs_per_step": S * len(q), "top_k": 10, "per_video": 2, "rounds": rounds,
+           "mx_graph_equals_mx_eager": same("mx_graph", "mx_eager"), "mx_hits_equal_default": same("mx_eager", "default_eager"),
+           "first_hit_same_video": int((hits["mx_eager"].video[:, 0] == hits["default_eager"].video[:, 0]).sum()), "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_min": min(ts), "ms_per_search_max": max(ts),
+                              "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    v = res["variants"]
+    for mode in ("eager", "graph"):
+        diff = v["mx_" + mode]["ms_per_search_median"] - v["default_" + mode]["ms_per_search_median"]
+        spread = v["default_" + mode]["ms_per_search_max"] - v["default_" + mode]["ms_per_search_min"]
+        res["mx_minus_default_" + mode] = {"ms": diff, "default_max_minus_min_ms": spread, "a_difference": abs(diff) > spread}
+    return res
+
+
+def bench_mx_kernels(model, q, T, Q, rounds, window_s=0.3):
+    """bench_kernel's protocol, launch-inclusive, interleaved: drn_conv0_mx8 alone; the gather and the conv0 GEMM it replaces, each
+    alone and back to back (the GEMM as conv_block launches it, on the gather's output); and the once-per-search weights launch."""
+    from drn_amd import functional as DF, ops
+    from drn_amd.model.basic_blocks import conv_bn
+    dev = q.codes.device
+    S = Q // NV
+    conv, _ = conv_bn(model.backbone_net.forward_conv0, "bench")
+    Cout = int(conv.weight.shape[0])
+    gate = torch.randn(S, q.Dp, device=dev)
+    pair = torch.arange(Q, dtype=torch.int32, device=dev)
+    pq, pv = torch.div(pair, NV, rounding_mode="floor"), torch.remainder(pair, NV)
+    vids = torch.arange(NV, dtype=torch.int32, device=dev)
+    g0 = torch.empty((Q, T, q.Dp + q.P), dtype=q.dtype, device=dev)
+    raws = [torch.empty((Q, T, Cout), dtype=q.dtype, device=dev) for _ in range(2)]
+    with torch.no_grad():
+        wq = DF.conv0_mx8_weights(conv.weight, gate, q.D, q.Dp)
+        wp = DF.packed(conv.weight, (0, 2, 1), ops.BF16)
+    gather = lambda o: ops.gate_gather_packed_q8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, gate, pq, pv, vids, g0, T, q.Dp, q.P, ops.BF16)
+    gemm = lambda o: ops.gemm_nt([ops.gemm_desc(g0, wp, o, Q * T, Cout, q.Dp + q.P, taps=3, stride=1, pad=1, Lout=T, Lsrc=T,
+                                                lda=q.Dp + q.P)], ops.BF16)
+    launch = {"conv0_mx8": lambda o: ops.conv0_mx8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, wq[0], wq[1], wq[2], pq, pv, vids, o, T,
+                                                   q.Dp, q.P),
+              "gate_gather_packed_q8": gather, "conv0_gemm_bf16": gemm, "gather_then_gemm": lambda o: (gather(o), gemm(o)),
+              "gate_quantize_weights_mx8": lambda o: ops.gate_quantize_weights_mx8(DF.packed(conv.weight, (2, 0, 1), ops.F32)[:, :, :q.D], gate,
+                                                                                  q.D, q.Dp, wq[0], wq[1])}
+
+    def run(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(raws[i & 1])
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    reps = {}
+    with torch.no_grad():
+        for k, fn in launch.items():
+            run(fn, 5)
+            reps[k] = max(10, int(window_s / (run(fn, 10) * 1e-6)))
+        ts = {k: [] for k in launch}
+        for _ in range(rounds):
+            for k, fn in launch.items():
+                ts[k].append(run(fn, reps[k]))
+    flop = 2.0 * Q * T * Cout * 3 * (q.Dp + q.P)
+    res = {"Q": Q, "T": T, "S": S, "C": q.Dp, "P": q.P, "Cout": Cout, "flop": flop, "g0_bytes": g0.numel() * g0.element_size(),
+           "gated_weight_bytes": int(wq[0].numel() + wq[1].numel()), "note": "launch-inclusive, device events around windows of ~0.3 s"}
+    for k in launch:
+        us = statistics.median(ts[k])
+        res[k] = {"us_median": us, "us_min": min(ts[k]), "us_max": max(ts[k]), "us_rounds": ts[k], "launches_per_window": reps[k]}
+    for k in ("conv0_mx8", "conv0_gemm_bf16"):
+        res[k]["tflops"] = flop / (res[k]["us_median"] * 1e-6) / 1e12
+    return res
+
+
+def bench_mx_recall(model, q, T, S=8, nbatches=8):
+    """bench_q8_recall's batches through both modes on the same quantised index (random annotations, synthetic weights: the recalls
+    say nothing about the model, only how far the two modes' answers are apart)."""
+    from drn_amd import Grounder, evaluate_search
+    ious, topks, kv = (0.5, 0.7), (1, 10), 2
+    g = torch.Generator().manual_seed(T)
+    batches = []
+    for b in range(nbatches):
+        tok, qlen = sentences(S, 100 + b)
+        start = torch.rand(S, generator=g, dtype=torch.float64) * 0.5
+        gt = torch.stack([start, start + 0.1 + torch.rand(S, generator=g, dtype=torch.float64) * 0.4], dim=1)
+        batches.append((["V%03d" % ((b * S + i) % NV) for i in range(S)], tok, qlen, gt))
+    grounders = {"default": Grounder(model, top_k=10), "mx": Grounder(model, top_k=10, conv0="mxfp8")}
+    res = {"T": T, "sentences": S * nbatches, "ious": list(ious), "topks": list(topks), "per_video": kv,
+           "note": "synthetic weights and random annotations: these recalls say nothing about the model"}
+    tables = {}
+    for name, gr in grounders.items():
+        r = evaluate_search(gr, batches, q, ious=ious, topks=topks, per_video=kv)
+        tables[name] = r.first_hits
+        res[name] = {"moment": r.moment, "video": r.video}
+    res["first_hit_rows_equal"] = float((tables["default"] == tables["mx"]).all(axis=1).mean())
+    same_video = same_top10 = 0
+    worst = 0.0
+    for _, tok, qlen, _ in batches:
+        a, b = grounders["default"].search(tok, qlen, q, per_video=kv), grounders["mx"].search(tok, qlen, q, per_video=kv)
+        same_video += int((a.video[:, 0] == b.video[:, 0]).sum())
+        same_top10 += int((a.video == b.video).all(dim=1).sum())
+        worst = max(worst, float((a.score[:, 0] - b.score[:, 0]).abs().max()))
+    res["first_hit_same_video_share"] = same_video / (S * nbatches)
+    res["top10_same_videos_in_order_share"] = same_top10 / (S * nbatches)
+    res["first_hit_score_largest_abs_difference"] = worst
+    return res
+
+
+def mx_bound_ratio():
+    """The random case of tests/test_search_mx8conv_gpu.py (Dp = 384, P = 256, Cout = 64, L = 40, raw in bf16): the largest
+    |raw - ref| over its derived bound 2^-8 |ref| + K 2^-23 sum |a b|."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_search_mx8conv_gpu import random_case, raw_bound, run_conv0
+    from drn_amd.index import mx8_conv0_reference
+    case = random_case(384, 256, 64, 11)
+    raw = run_conv0(*case, 40, torch.bfloat16)
+    ref = mx8_conv0_reference(*case, 40)
+    return {"Dp": 384, "P": 256, "Cout": 64, "L": 40, "raw": "bf16", "bound": "2^-8 |ref| + 3 (Dp + P) 2^-23 sum |a b|",
+            "largest_error_over_bound": float(((raw.double().cpu() - ref).abs() / raw_bound(*case, 40, ref)).max())}
+
+
+def main_mx_conv0(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex
+    out = args.out or os.path.join(ROOT, "profiles", "search_mx8conv_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, one quantised index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s; min and max of the rounds beside it",
+                      "clock": "host clock around searches ending in a device synchronise; device events for the kernel windows",
+                      "what": "Grounder(conv0=\"mxfp8\") beside the default Grounder on the same SearchIndex(quantize=\"mxfp8\"); a difference "
+                              "smaller than the default path's own max - min across rounds is no difference"},
+           "bound_ratio": mx_bound_ratio(), "search": [], "kernel": [], "recall": []}
+    print(json.dumps({"bound_ratio": res["bound_ratio"]}), flush=True)
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        q = SearchIndex.build(model, store, quantize="mxfp8")
+        del store
+        for S in (1, 8):
+            res["search"].append(bench_mx_search(model, q, T, S, args.rounds))
+            print(json.dumps({"search": res["search"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        for Q in (512, 64):
+            res["kernel"].append(bench_mx_kernels(model, q, T, Q, args.rounds))
+            print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+        res["recall"].append(bench_mx_recall(model, q, T))
+        print(json.dumps({"recall": res["recall"][-1]}), flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+        del q
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -456,6 +633,7 @@ def main():
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
     ap.add_argument("--quantized", action="store_true", help="measure a SearchIndex built with quantize=\"mxfp8\" beside the plain index")
+    ap.add_argument("--mx-conv0", action="store_true", help="measure Grounder(conv0=\"mxfp8\") beside the default path on one quantised index")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
@@ -465,6 +643,8 @@ def main():
         return main_evaluate(args)
     if args.quantized:
         return main_quantized(args)
+    if args.mx_conv0:
+        return main_mx_conv0(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
