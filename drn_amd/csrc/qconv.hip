@@ -7,6 +7,7 @@
 #include "mx8.h"
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- gated weights
 // quantize_rows_mx8_kernel (qindex.hip) on rows that are products: row (s, tap, n) of Dp columns, column c = gate[s][c] * w[tap][n][c]
@@ -234,4 +235,273 @@ extern "C" int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* 
     launch_conv0_mx8<bf16_t>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales,
                              (const bf16_t*)wpos, S, pq, pv, vids, Vc, (bf16_t*)raw, ld_raw, Q, L, C, P, Cout, st);
   return drn_launch_status("drn_conv0_mx8");
+}
+
+// ---------------------------------------------------------------- conv0 on the codes, LDS-staged, with BatchNorm / ReLU / gate in the epilogue
+// drn_conv0_mx8_bn (Grounder(conv0="mxfp8", fused=True)).  One workgroup = 8 waves = MXT_ROWS = 256 rows of the FLATTENED (pair, t) output
+// x up to 256 output channels; wave w owns rows [64 (w & 3), +64) x channels [128 (w >> 2), +128) as 4 x 8 fragments of 16 x 16.  At small
+// L a tile spans several pairs (8 at L = 32); a pair longer than the tile spans several tiles.  The grid, cdiv(Q L, 256) x cdiv(Cout, 256),
+// and the tile -> pair map are functions of (Q, L, Cout) alone.
+// K runs tap-outer: step s = (tap, k0) stages a 256 x 128-byte tile of index codes (row i = the source row of output row i at this tap,
+// zeros where the tap falls outside [0, L)) and a 256 x 128-byte tile of the sentence's gated weights, with one dword of four scale bytes
+// per row, into one of TWO LDS stages (2 x (32 + 32 + 1 + 1) KB = 132 KB, + the 4 KB row table + the 1 KB sentence list = 140,288 bytes:
+// ONE workgroup per CU, two waves per SIMD).  The global
+// loads of step s + 1 are issued into registers before the MFMAs of step s and written to the other stage after them: one barrier per
+// step.  The operand map of the instruction (above) makes a staged tile a plain row copy.  128-byte rows would put rows r and r + 2 on
+// the same banks for ds_read_b128, so the 16-byte slot c of row r lies at slot c ^ ((r >> 1) & 7): each of the instruction's four lane
+// groups (microarchitecture: {0-3, 12-15, 20-27}, ...) then covers all 64 banks once, and the 8 lanes that write one row still cover
+// 128 contiguous bytes.
+// Sentences: all rows of one MFMA share B, so the tile makes one pass of the whole K loop per DISTINCT sentence among its pairs (in the
+// order of first appearance; wave-uniform, found from pq in LDS), staging only that sentence's weights; rows of other sentences are
+// staged as zero codes with scale byte 127 and add +0 to their accumulators.
+// An accumulator therefore sums its own sentence's K in one fixed order -- taps 0..2 x the 128-column steps, then taps 0..2 x the
+// 32-column position steps on v_mfma_f32_16x16x32_bf16 (fragments from memory, as conv0_mx8_kernel) -- whatever else the tile or the
+// launch holds, and whatever the order of the pairs.  (A NaN weight code, or a weight scale byte 255 -- the e8m0 NaN --, of ANOTHER
+// sentence in the same tile is the one exception: 0 x NaN; the quantiser writes neither, its scale bytes end at 254.)  No split-K, no atomics.
+// Addresses: clamped exactly as in conv0_mx8_kernel; a masked row is loaded from its clamped address and then zeroed.
+// Epilogue, from the fp32 accumulator: v = relu(fmaf(acc, scale, shift)) with (scale, shift) = ss[n], ss[Cout + n]
+// (bn_eval_scale_shift's table; ss NULL: v = acc), out = OUT(v), gated = OUT(v * gate[pair][n]) from the UNROUNDED v, as bn_apply_kernel.
+#define MXT_ROWS 256
+#define MXT_TILE (MXT_ROWS * 128)
+// The order of the K loop's memory operations IS its schedule (loads of the next step, then per channel fragment two LDS reads and four
+// MFMAs, then the LDS writes of the next step); left alone, the compiler reads all eight B fragments first (64 registers more, which
+// spill) and writes the next stage before the MFMAs (which waits for the loads just issued).  Nothing moves across this.
+#define MXT_FENCE()                        \
+  do {                                     \
+    asm volatile("" ::: "memory");         \
+    __builtin_amdgcn_sched_barrier(0);     \
+  } while (0)
+
+template <typename OUT>
+__global__ __launch_bounds__(512) void conv0_mx8_tiled_kernel(const uint8_t* __restrict__ codes, int ld_codes, const uint8_t* __restrict__ scales,
+                                                              int ld_scales, const bf16_t* __restrict__ pos, int ld_pos, int n_rows, int pad_row,
+                                                              const int* __restrict__ prop_off, int Nv, const uint8_t* __restrict__ wcodes,
+                                                              const uint8_t* __restrict__ wscales, const bf16_t* __restrict__ wpos, int S,
+                                                              const int* __restrict__ pq, const int* __restrict__ pv, const int* __restrict__ vids,
+                                                              int Vc, const float* __restrict__ ss, const float* __restrict__ gate, int ldg,
+                                                              OUT* __restrict__ out, int ld_out, OUT* __restrict__ gated, int ld_gated, int Q, int L,
+                                                              int C, int P, int Cout) {
+  __shared__ __attribute__((aligned(16))) uint8_t tA[2][MXT_TILE];
+  __shared__ __attribute__((aligned(16))) uint8_t tB[2][MXT_TILE];
+  __shared__ unsigned sA[2][MXT_ROWS], sB[2][MXT_ROWS];
+  __shared__ int qs[MXT_ROWS];                           // the (clamped) sentences of the tile's pairs; -1 once their pass is done
+  __shared__ i32x4 rinfo[MXT_ROWS];                      // per tile row: t, its video's first row and row count, its sentence (-1: past M)
+  constexpr int MI = 4, NJ = 8;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ngroups = (Cout + 255) / 256;
+  const int ng = blockIdx.x % ngroups;
+  const int M = Q * L, m0 = (int)(blockIdx.x / ngroups) * MXT_ROWS;            // (the entry refuses Q L + 256 > 2^31 - 1)
+  const int p0 = m0 / L, p1 = min((m0 + MXT_ROWS - 1) / L, Q - 1), npairs = p1 - p0 + 1;   // (<= 256: L >= 1)
+  const int cblocks = C / MX8_BLOCK, ksteps = (C + 127) / 128, nsteps = 3 * ksteps;
+  const int r = lane & 15, kq = lane >> 4;
+
+  if (tid < MXT_ROWS) {
+    const int m = m0 + tid, p = min(m / L, Q - 1);
+    const int slot = pv[p];
+    const int vd = (slot >= 0 && slot < Vc) ? vids[slot] : -1;
+    int base = 0, cnt = 0;
+    if (vd >= 0 && vd < Nv) {
+      base = prop_off[vd];
+      cnt = prop_off[vd + 1] - base;
+    }
+    rinfo[tid] = i32x4{m - p * L, base, cnt, m < M ? min(max(pq[p], 0), S - 1) : -1};
+  }
+  for (int i = tid; i < npairs; i += 512) qs[i] = min(max(pq[p0 + i], 0), S - 1);
+  __syncthreads();
+  // the source row of tile row R at offset u of its video, clamped; whether it is a row of sentence q with tap u inside [0, L)
+  auto src_of = [&](const i32x4 R, int u) { return (long)min(max(u >= 0 && u < R[2] ? R[1] + u : pad_row, 0), n_rows - 1); };
+  auto live_of = [&](const i32x4 R, int u, int q) { return R[3] == q && u >= 0 && u < L; };
+
+  // staging: thread -> the 16-byte slot (tid & 7) of rows (tid >> 3) + 64 k, k < 4, of both tiles; one scale dword of row tid & 255 of
+  // A (waves 0-3) or of B (waves 4-7)
+  const int srow0 = tid >> 3, sslot = tid & 7;
+  const int dst0 = srow0 * 128 + ((sslot ^ ((srow0 >> 1) & 7)) << 4);          // ((row >> 1) & 7 is the same for rows 64 apart)
+  const bool scaleA = wave < 4;                          // (wave-uniform)
+  const int scrow = tid & 255;
+  // this wave's fragments
+  const int wr = (wave & 3) * 64, n0 = ng * 256 + (wave >> 2) * 128;
+
+  f32x4 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int pi = 0; pi < npairs; ++pi) {
+    const int q = qs[pi];                                // (one address for the whole workgroup)
+    if (q < 0) continue;                                 // (uniform: a sentence that had its pass)
+    // fetch: the global loads of a step into registers, nothing consuming them (no wait); stage: mask them and write them to LDS
+    u32x4 ra[4], rb[4];
+    unsigned rsb[4], keep;                               // keep: bit k = A row k is live, bit 4 = the scale row is live
+    auto fetch = [&](int step) {
+      const int tap = step / ksteps, k0 = (step - tap * ksteps) * 128;
+      const unsigned colc = (unsigned)min(k0 + 16 * sslot, C - 16);
+      const uint8_t* wc = wcodes + ((long)q * 3 + tap) * Cout * C;             // (uniform)
+      keep = 0;
+      int srow = srow0, scr = scrow;                     // (opaque: offsets made of them are computed here, not kept -- and spilled -- across
+      asm volatile("" : "+v"(srow), "+v"(scr));          //  the whole K loop)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const i32x4 R = rinfo[srow + 64 * k];
+        const int u = R[0] + tap - 1;
+        ra[k] = *(const u32x4*)(codes + src_of(R, u) * ld_codes + colc);
+        keep |= (live_of(R, u, q) ? 1u : 0u) << k;
+        rb[k] = *(const u32x4*)(wc + ((unsigned)min(ng * 256 + srow + 64 * k, Cout - 1) * (unsigned)C + colc));
+      }
+      const uint8_t* sp;
+      if (scaleA) {
+        const i32x4 R = rinfo[scr];
+        const int u = R[0] + tap - 1;
+        keep |= (live_of(R, u, q) ? 1u : 0u) << 4;
+        sp = scales + src_of(R, u) * ld_scales;
+      } else {
+        keep |= 1u << 4;
+        sp = wscales + (((long)q * 3 + tap) * Cout + min(ng * 256 + scr, Cout - 1)) * cblocks;
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) rsb[g] = sp[min(k0 / MX8_BLOCK + g, cblocks - 1)];
+    };
+    auto stage = [&](int step, int buf) {
+      const int k0 = (step % ksteps) * 128;
+      const bool col_in = k0 + 16 * sslot < C;
+      const u32x4 zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        *(u32x4*)(&tA[buf][dst0 + 64 * 128 * k]) = (col_in && ((keep >> k) & 1)) ? ra[k] : zero;
+        *(u32x4*)(&tB[buf][dst0 + 64 * 128 * k]) = col_in ? rb[k] : zero;
+      }
+      unsigned rs = 0;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) rs |= ((((keep >> 4) & 1) && k0 / MX8_BLOCK + g < cblocks) ? rsb[g] : 127u) << (8 * g);
+      (scaleA ? sA[buf] : sB[buf])[scrow] = rs;
+    };
+
+    fetch(0);
+    stage(0, 0);
+    __syncthreads();
+    for (int step = 0; step < nsteps; ++step) {
+      const int buf = step & 1;
+      if (step + 1 < nsteps) fetch(step + 1);
+      MXT_FENCE();
+      i32x8 a[MI];
+      int sa[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int row = wr + 16 * i + r, sw = (row >> 1) & 7;
+        const u32x4 lo = *(const u32x4*)(&tA[buf][row * 128 + ((kq ^ sw) << 4)]);
+        const u32x4 hi = *(const u32x4*)(&tA[buf][row * 128 + (((kq + 4) ^ sw) << 4)]);
+        a[i] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        sa[i] = (int)((sA[buf][row] >> (8 * kq)) & 0xffu);
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {                     // (fragments past Cout read clamped rows and are not stored)
+        const int row = (wave >> 2) * 128 + 16 * j + r, sw = (row >> 1) & 7;
+        const u32x4 lo = *(const u32x4*)(&tB[buf][row * 128 + ((kq ^ sw) << 4)]);
+        const u32x4 hi = *(const u32x4*)(&tB[buf][row * 128 + (((kq + 4) ^ sw) << 4)]);
+        const i32x8 bw = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        const int sb = (int)((sB[buf][row] >> (8 * kq)) & 0xffu);
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], bw, acc[i][j], 0 /* cbsz: A is e4m3 */, 0 /* blgp: B is e4m3 */, 0,
+                                                                       sa[i], 0, sb);
+        asm volatile("" : "+v"(acc[0][j]), "+v"(acc[1][j]), "+v"(acc[2][j]), "+v"(acc[3][j])::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (step + 1 < nsteps) stage(step + 1, buf ^ 1);
+      __syncthreads();
+    }
+    // the position columns, fragments from memory
+    if (n0 < Cout) {
+      int rr = r, kk = kq;                               // (opaque, as in fetch)
+      asm volatile("" : "+v"(rr), "+v"(kk));
+      for (int tap = 0; tap < 3; ++tap) {
+        long src[MI];
+        bool live[MI];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const i32x4 R = rinfo[wr + 16 * i + rr];
+          const int u = R[0] + tap - 1;
+          src[i] = src_of(R, u);
+          live[i] = live_of(R, u, q);
+        }
+        for (int j0 = 0; j0 < P; j0 += 32) {
+          bf16x8 a[MI];
+#pragma unroll
+          for (int i = 0; i < MI; ++i) {
+            const bf16x8 v = *(const bf16x8*)(pos + src[i] * ld_pos + j0 + 8 * kk);
+            a[i] = live[i] ? v : bf16x8{};
+          }
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const bf16x8 bw = *(const bf16x8*)(wpos + (unsigned)((tap * Cout + min(n0 + 16 * j + rr, Cout - 1)) * P + j0 + 8 * kk));
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], bw, acc[i][j], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // this sentence is done: strike it from the list (every wave has read qs[pi]: the K loop's barriers lie in between)
+    for (int i = tid; i < npairs; i += 512)
+      if (qs[i] == q) qs[i] = -1;
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int m = m0 + wr + 16 * i + 4 * kq + x;
+      if (m >= M) continue;
+      const float* gp = gated ? gate + (long)(m / L) * ldg : nullptr;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int n = n0 + 16 * j + r;
+        if (n >= Cout) continue;
+        float v = acc[i][j][x];
+        if (ss) v = fmaxf(fmaf(v, ss[n], ss[Cout + n]), 0.f);
+        out[(long)m * ld_out + n] = (OUT)v;
+        if (gated) gated[(long)m * ld_gated + n] = (OUT)(v * gp[n]);
+      }
+    }
+}
+
+extern "C" int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                                int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
+                                int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, const float* ss,
+                                const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q, int L, int C,
+                                int P, int Cout, void* stream) {
+  drn_clear_status();
+  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && out && (P == 0 || (pos && wpos)),
+                "drn_conv0_mx8_bn: null pointer");
+  DRN_CHECK_ARG((gate != nullptr) == (gated != nullptr), "drn_conv0_mx8_bn: gate and gated must come together");
+  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
+                "drn_conv0_mx8_bn: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", n_rows, pad_row, Nv,
+                S, Vc, Q, L, C, P, Cout);
+  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "drn_conv0_mx8_bn: C = %d is not a multiple of the block of %d columns", C, MX8_BLOCK);
+  DRN_CHECK_ARG(P % 32 == 0, "drn_conv0_mx8_bn: P = %d is not a multiple of the 32 columns of a position step", P);
+  DRN_CHECK_ARG(Cout % 16 == 0, "drn_conv0_mx8_bn: Cout = %d is not a multiple of 16", Cout);
+  DRN_CHECK_ARG((long)Cout * C <= 0x7fffffffL && 3L * Cout * P <= 0x7fffffffL, "drn_conv0_mx8_bn: a weight plane of %d x %d is beyond 2^31",
+                Cout, C + P);
+  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL - MXT_ROWS && ((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256) <= 0x7fffffffL,
+                "drn_conv0_mx8_bn: more than 2^31 rows");
+  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_out >= Cout && (!gated || (ld_gated >= Cout && ldg >= Cout)),
+                "drn_conv0_mx8_bn: a row stride is shorter than its row");
+  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
+                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
+                "drn_conv0_mx8_bn: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples");
+  if (pq_host)
+    for (int p = 0; p < Q; ++p)
+      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "drn_conv0_mx8_bn: pair %d reads sentence %d of %d", p, (int)pq_host[p], S);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256));
+  if (out_f32)
+    conv0_mx8_tiled_kernel<float><<<grid, 512, 0, st>>>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv,
+                                                        wcodes, wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (float*)out, ld_out,
+                                                        (float*)gated, ld_gated, Q, L, C, P, Cout);
+  else
+    conv0_mx8_tiled_kernel<bf16_t><<<grid, 512, 0, st>>>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off,
+                                                         Nv, wcodes, wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (bf16_t*)out,
+                                                         ld_out, (bf16_t*)gated, ld_gated, Q, L, C, P, Cout);
+  return drn_launch_status("drn_conv0_mx8_bn");
 }

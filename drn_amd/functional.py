@@ -863,18 +863,25 @@ def conv0_mx8_weights(weight, gate0, D, Dp, out=None):
 
 
 def conv0_mx8_block(index, wq, pair_q, pair_v, vids, L, conv, bn, gate, dt):
-    """conv0 -> eval BatchNorm -> ReLU (-> level-1 gate) of Q (sentence, video) pairs straight from a quantised SearchIndex:
-    ops.conv0_mx8 writes raw (Q, L, Cout) from the index's codes and the gated weights `wq` (conv0_mx8_weights), then the unfused
-    eval path's own launches (bn_eval_scale_shift + bn_apply_multi) as conv_block runs them -> (out, gated), gated None without gate."""
+    """conv0 -> eval BatchNorm -> ReLU (-> level-1 gate) of Q (sentence, video) pairs straight from a quantised SearchIndex, from the
+    index's codes and the gated weights `wq` (conv0_mx8_weights) -> (out, gated), gated None without gate.  Inside fused_eval():
+    bn_eval_scale_shift and ONE ops.conv0_mx8_bn launch that applies the affine map, the ReLU and the gate to its fp32 accumulators.
+    Otherwise ops.conv0_mx8 writes raw (Q, L, Cout), then the unfused eval path's own launches (bn_eval_scale_shift + bn_apply_multi)
+    as conv_block runs them."""
     wcodes, wscales, wpos = wq
     Q, Cout, dev, code = int(pair_q.numel()), int(conv.weight.shape[0]), index.codes.device, code_of(dt)
+    ss = torch.empty((2, Cout), dtype=torch.float32, device=dev)
+    out = torch.empty((Q, L, Cout), dtype=dt, device=dev)
+    gated = torch.empty((Q, L, Cout), dtype=dt, device=dev) if gate is not None else None
+    if FUSED_EVAL:
+        ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
+        ops.conv0_mx8_bn(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off, wcodes, wscales, wpos,
+                         pair_q, pair_v, vids, ss, gate, out, gated, L, index.Dp, index.P)
+        return out, gated
     raw = torch.empty((Q, L, Cout), dtype=dt, device=dev)
     ops.conv0_mx8(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off, wcodes, wscales, wpos, pair_q,
                   pair_v, vids, raw, L, index.Dp, index.P)
-    ss = torch.empty((2, Cout), dtype=torch.float32, device=dev)
     ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
-    out = torch.empty((Q, L, Cout), dtype=dt, device=dev)
-    gated = torch.empty((Q, L, Cout), dtype=dt, device=dev) if gate is not None else None
     ops.bn_apply_multi([dict(raw=raw, ld_raw=Cout, ss=ss, out=out, ld_out=Cout, M=Q * L, L=L, up=None, ld_up=0, gate=gate, gated=gated,
                              ld_gated=Cout)], Cout, code, relu=True)
     return out, gated

@@ -180,7 +180,10 @@ class Grounder(object):
     straight from a SearchIndex built with quantize="mxfp8" (mainModel.forward_heads_packed(conv0="mxfp8")): no gather launch and no
     (pairs, T, Dp + P) buffer; the sentence gate is folded into conv0's weights, which are quantised to the index's format ONCE per
     search (one launch, outside a captured graph, into the buffer the graph reads).  Lossy: the scores differ from the default path's.
-    A store, a plain index or an fp32 model raise before any launch.  ground() is not affected."""
+    A store, a plain index or an fp32 model raise before any launch.  ground() is not affected.
+    conv0="mxfp8" together with fused=True: conv0, its eval BatchNorm, the ReLU and the level-1 gate are ONE launch on LDS-staged FP8
+    tiles (ops.conv0_mx8_bn) that never writes conv0's raw output; without fused it is ops.conv0_mx8 followed by the unfused
+    BatchNorm launches.  The two differ in the last bits of their scores (raw is rounded to bf16 only in the unfused mode)."""
 
     # Pairs (sentence, video) per chunk that search() allows itself by default.  A CHOICE, not a measurement: conv0's input g0 holds
     # T * (D + 256) elements per pair -- 2.1 MiB at T = 256, D = 4096 in bf16 -- so 512 pairs are 1.1 GiB of g0, and the trunk's

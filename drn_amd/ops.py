@@ -720,6 +720,44 @@ def gate_quantize_weights_mx8(w, gate, D, Dp, wcodes, wscales):
         _stream()), "drn_gate_quantize_weights_mx8"))
 
 
+def _conv0_mx8_operands(who, codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, dests, L, C, P, pq_host, wide=False):
+    """The argument checks conv0_mx8 and conv0_mx8_bn share -> (S, Cout, Q, pq_host's pointer or None).  dests: (name, tensor) pairs, each
+    a contiguous (Q, L, Cout) bfloat16 or float32 tensor; wide: a column slice of a contiguous (Q, L, >= Cout) tensor serves as well."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or codes.stride(1) != 1 \
+            or scales.stride(1) != 1 or codes.shape[0] != scales.shape[0] or codes.shape[1] < C or scales.shape[1] * 32 < C:
+        raise _lib.DrnError("%s: codes (n_rows, >= C) and scales (n_rows, >= C / 32) must be uint8 with unit column stride" % who)
+    if C < 32 or C % 32 or P < 0 or P % 32:
+        raise _lib.DrnError("%s: C = %d and P = %d must be multiples of 32 (C at least 32)" % (who, C, P))
+    if wcodes.dtype != torch.uint8 or wscales.dtype != torch.uint8 or wcodes.dim() != 4 or wscales.dim() != 4 or not wcodes.is_contiguous() \
+            or not wscales.is_contiguous() or wcodes.shape[1] != 3 or wcodes.shape[3] != C \
+            or tuple(wscales.shape) != tuple(wcodes.shape[:3]) + (C // 32,):
+        raise _lib.DrnError("%s: wcodes (S, 3, Cout, C) and wscales (S, 3, Cout, C / 32) must be contiguous uint8" % who)
+    S, Cout = int(wcodes.shape[0]), int(wcodes.shape[2])
+    if Cout % 16:
+        raise _lib.DrnError("%s: Cout = %d is not a multiple of 16" % (who, Cout))
+    if (pos is None) != (P == 0) or (pos is not None and (pos.dim() != 2 or pos.stride(1) != 1 or pos.dtype != torch.bfloat16
+                                                          or pos.shape[0] != codes.shape[0] or pos.shape[1] < P)):
+        raise _lib.DrnError("%s: pos must be (n_rows, >= P) bfloat16 with unit column stride (None with P = 0)" % who)
+    if (wpos is None) != (P == 0) or (wpos is not None and (wpos.dtype != torch.bfloat16 or tuple(wpos.shape) != (3, Cout, P)
+                                                            or not wpos.is_contiguous())):
+        raise _lib.DrnError("%s: wpos must be a contiguous (3, %d, %d) bfloat16 tensor (None with P = 0)" % (who, Cout, P))
+    _need_gpu(codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, *[t for _, t in dests])
+    Q = int(pq.numel())
+    for name, t, n in (("pq", pq, Q), ("pv", pv, Q), ("vids", vids, int(vids.numel())), ("prop_off", prop_off, int(prop_off.numel()))):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n or n < 1:
+            raise _lib.DrnError("%s: %s must be a contiguous 1-d int32 tensor (pq and pv of the same length)" % (who, name))
+    for name, t in dests:
+        if t is None or t.dim() != 3 or tuple(t.shape) != (Q, L, Cout) or t.dtype not in (torch.bfloat16, torch.float32) \
+                or not (t.is_contiguous() or (wide and t.stride(2) == 1 and t.stride(1) >= Cout and t.stride(0) == L * t.stride(1))):
+            raise _lib.DrnError("%s: %s must be a contiguous (%d, %d, %d) bfloat16 or float32 tensor" % (who, name, Q, L, Cout))
+    host = None
+    if pq_host is not None:
+        if pq_host.is_cuda or pq_host.dtype != torch.int32 or not pq_host.is_contiguous() or pq_host.numel() != Q:
+            raise _lib.DrnError("%s: pq_host must be a contiguous int32 host tensor of %d entries" % (who, Q))
+        host = ctypes.c_void_p(pq_host.data_ptr())
+    return S, Cout, Q, host
+
+
 def conv0_mx8(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, pv, vids, raw, L, C, P, pq_host=None):
     """conv0 (k = 3, stride 1, pad 1, no bias) of the input gate_gather_packed_q8 would have written, straight from the quantised
     index on block-scaled FP8 MFMAs (drn_conv0_mx8; drn_amd.index.mx8_conv0_reference is the definition): codes / scales / pos /
@@ -727,41 +765,42 @@ def conv0_mx8(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, 
     (S, 3, Cout, C / 32) as gate_quantize_weights_mx8 writes them, contiguous; wpos (3, Cout, P) bfloat16 contiguous (None with
     P = 0): conv0's position weights, tap-major.  raw: (Q, L, Cout) contiguous, bfloat16 or float32, written in place.
     C % 32 == 0, P % 32 == 0, Cout % 16 == 0."""
-    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or codes.stride(1) != 1 \
-            or scales.stride(1) != 1 or codes.shape[0] != scales.shape[0] or codes.shape[1] < C or scales.shape[1] * 32 < C:
-        raise _lib.DrnError("conv0_mx8: codes (n_rows, >= C) and scales (n_rows, >= C / 32) must be uint8 with unit column stride")
-    if C < 32 or C % 32 or P < 0 or P % 32:
-        raise _lib.DrnError("conv0_mx8: C = %d and P = %d must be multiples of 32 (C at least 32)" % (C, P))
-    if wcodes.dtype != torch.uint8 or wscales.dtype != torch.uint8 or wcodes.dim() != 4 or wscales.dim() != 4 or not wcodes.is_contiguous() \
-            or not wscales.is_contiguous() or wcodes.shape[1] != 3 or wcodes.shape[3] != C \
-            or tuple(wscales.shape) != tuple(wcodes.shape[:3]) + (C // 32,):
-        raise _lib.DrnError("conv0_mx8: wcodes (S, 3, Cout, C) and wscales (S, 3, Cout, C / 32) must be contiguous uint8")
-    S, Cout = int(wcodes.shape[0]), int(wcodes.shape[2])
-    if Cout % 16:
-        raise _lib.DrnError("conv0_mx8: Cout = %d is not a multiple of 16" % Cout)
-    if (pos is None) != (P == 0) or (pos is not None and (pos.dim() != 2 or pos.stride(1) != 1 or pos.dtype != torch.bfloat16
-                                                          or pos.shape[0] != codes.shape[0] or pos.shape[1] < P)):
-        raise _lib.DrnError("conv0_mx8: pos must be (n_rows, >= P) bfloat16 with unit column stride (None with P = 0)")
-    if (wpos is None) != (P == 0) or (wpos is not None and (wpos.dtype != torch.bfloat16 or tuple(wpos.shape) != (3, Cout, P)
-                                                            or not wpos.is_contiguous())):
-        raise _lib.DrnError("conv0_mx8: wpos must be a contiguous (3, %d, %d) bfloat16 tensor (None with P = 0)" % (Cout, P))
-    _need_gpu(codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, raw)
-    Q = int(pq.numel())
-    for name, t, n in (("pq", pq, Q), ("pv", pv, Q), ("vids", vids, int(vids.numel())), ("prop_off", prop_off, int(prop_off.numel()))):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n or n < 1:
-            raise _lib.DrnError("conv0_mx8: %s must be a contiguous 1-d int32 tensor (pq and pv of the same length)" % name)
-    if raw.dim() != 3 or tuple(raw.shape) != (Q, L, Cout) or not raw.is_contiguous() or raw.dtype not in (torch.bfloat16, torch.float32):
-        raise _lib.DrnError("conv0_mx8: raw must be a contiguous (%d, %d, %d) bfloat16 or float32 tensor" % (Q, L, Cout))
-    host = None
-    if pq_host is not None:
-        if pq_host.is_cuda or pq_host.dtype != torch.int32 or not pq_host.is_contiguous() or pq_host.numel() != Q:
-            raise _lib.DrnError("conv0_mx8: pq_host must be a contiguous int32 host tensor of %d entries" % Q)
-        host = ctypes.c_void_p(pq_host.data_ptr())
+    S, Cout, Q, host = _conv0_mx8_operands("conv0_mx8", codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, [("raw", raw)],
+                                           L, C, P, pq_host)
     flops = 2.0 * Q * L * Cout * 3 * (C + P)
     _timed("conv0_mx8", flops, lambda: check(lib().drn_conv0_mx8(
         _p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
         int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(wcodes), _p(wscales), _p(wpos), S, _p(pq), host, _p(pv), _p(vids),
         int(vids.numel()), _p(raw), Cout, int(raw.dtype == torch.float32), Q, L, C, P, Cout, _stream()), "drn_conv0_mx8"))
+
+
+def conv0_mx8_bn(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, pv, vids, ss, gate, out, gated, L, C, P, pq_host=None):
+    """conv0_mx8 -> eval BatchNorm -> ReLU (-> gate) in ONE launch on LDS-staged tiles, without the raw tensor (drn_conv0_mx8_bn): the
+    operands of conv0_mx8; ss (2, Cout) float32 contiguous as bn_eval_scale_shift writes it, or None for the bare convolution; gate
+    (Q, >= Cout) float32 with unit column stride, one row per PAIR as bn_apply_multi takes it, or None; out and gated (None exactly
+    when gate is) (Q, L, Cout) tensors of one dtype, bfloat16 or float32, contiguous or column slices of contiguous wider ones, written
+    in place (nothing past a row's Cout columns is written):
+    out = relu(acc * scale + shift) from the fp32 accumulator, gated = that, unrounded, times the pair's gate row."""
+    if (gate is None) != (gated is None):
+        raise _lib.DrnError("conv0_mx8_bn: gate and gated must come together (a gated output needs a gate)")
+    dests = [("out", out)] + ([("gated", gated)] if gated is not None else [])
+    S, Cout, Q, host = _conv0_mx8_operands("conv0_mx8_bn", codes, scales, pos, prop_off, wcodes, wscales, wpos, pq, pv, vids, dests, L, C,
+                                           P, pq_host, wide=True)
+    if gated is not None and gated.dtype != out.dtype:
+        raise _lib.DrnError("conv0_mx8_bn: out and gated must have one dtype")
+    if ss is not None and (ss.dtype != torch.float32 or tuple(ss.shape) != (2, Cout) or not ss.is_contiguous()):
+        raise _lib.DrnError("conv0_mx8_bn: ss must be a contiguous (2, %d) float32 tensor" % Cout)
+    if gate is not None and (gate.dtype != torch.float32 or gate.dim() != 2 or gate.shape[0] != Q or gate.shape[1] < Cout
+                             or gate.stride(1) != 1):
+        raise _lib.DrnError("conv0_mx8_bn: gate must be (%d, >= %d) float32 with unit column stride" % (Q, Cout))
+    _need_gpu(ss, gate)
+    flops = 2.0 * Q * L * Cout * 3 * (C + P)
+    _timed("conv0_mx8_bn", flops, lambda: check(lib().drn_conv0_mx8_bn(
+        _p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
+        int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(wcodes), _p(wscales), _p(wpos), S, _p(pq), host, _p(pv), _p(vids),
+        int(vids.numel()), _p(ss), _p(gate), gate.stride(0) if gate is not None else 0, _p(out), out.stride(1), _p(gated),
+        gated.stride(1) if gated is not None else 0,
+        int(out.dtype == torch.float32), Q, L, C, P, Cout, _stream()), "drn_conv0_mx8_bn"))
 
 
 def pool_props_lds_rows(B, D, dtype):

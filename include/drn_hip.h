@@ -306,6 +306,20 @@ int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int
                   int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos, int S,
                   const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids, int Vc,
                   void* raw, int ld_raw, int out_f32, int Q, int L, int C, int P, int Cout, void* stream);
+/* drn_conv0_mx8_bn: drn_conv0_mx8 -> eval BatchNorm -> ReLU -> gate in ONE launch, raw never written (Grounder(conv0="mxfp8",
+ * fused=True)).  The same operands, tables, clamps and pq_host refusal, the same sum per output element (a row's value does not depend on
+ * which other pairs share the launch, nor on their order; no split-K, no atomics), computed from LDS-staged tiles of 256 rows of the
+ * flattened (pair, t) output x up to 256 channels -- a tile may hold several pairs and sentences; the grid depends on (Q, L, Cout)
+ * only.  With acc the fp32 accumulator and (sc, sh) = ss[n], ss[Cout + n], the table drn_bn_eval_scale_shift writes:
+ *   v = max(fmaf(acc, sc, sh), 0)          (ss NULL: v = acc, the bare convolution)
+ *   out[(p*L+t)*ld_out + n] = dtype(v);   with gate: gated[(p*L+t)*ld_gated + n] = dtype(v * gate[p*ldg + n])  -- gate (Q, >= Cout)
+ *   fp32, one row per PAIR, multiplied into the unrounded v as drn_bn_apply_multi does; gate and gated come together or not at all.
+ * out / gated bf16, or fp32 with out_f32; elements past Cout in a row are not written.  The other constraints are drn_conv0_mx8's. */
+int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                     int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos, int S,
+                     const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids, int Vc,
+                     const float* ss, const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q,
+                     int L, int C, int P, int Cout, void* stream);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */

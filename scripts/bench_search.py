@@ -33,7 +33,14 @@
            Grounder (drn_gate_gather_packed_q8, then conv0 on bf16 MFMAs), in one process: ms per search (S in {1, 8}, T in {256, 32},
            eager and by graph replay), drn_conv0_mx8 alone beside gather + conv0 GEMM alone at 512 and 64 pairs, the once-per-search
            weights launch alone, the first-hit agreement and evaluate_search recalls of the two modes on random annotations, and the
-           largest ratio of drn_conv0_mx8's error to its derived bound on the random case of tests/test_search_mx8conv_gpu.py."""
+           largest ratio of drn_conv0_mx8's error to its derived bound on the random case of tests/test_search_mx8conv_gpu.py.
+
+  --mx-conv0-fused   instead of the above -> profiles/search_mx8conv_fused_bench.json, by --mx-conv0's protocol on one quantised index:
+           Grounder(conv0="mxfp8", fused=True) (drn_conv0_mx8_bn: conv0 on LDS-staged FP8 tiles with BatchNorm, ReLU and the gate in its
+           epilogue) beside Grounder(conv0="mxfp8") and the default Grounder(fused=True), ms per search (S in {1, 8}, T in {256, 32},
+           eager and by graph replay); the launch alone at 512 and 64 pairs beside its yardsticks (a) drn_conv0_mx8 +
+           bn_eval_scale_shift + bn_apply_multi back to back and (b) the gather + the one-launch conv0 block of the default fused path;
+           the first-hit agreement of the fused and the unfused mode; the error / tolerance ratios of tests/test_search_mx8fused_gpu.py."""
 import argparse
 import json
 import os
@@ -625,6 +632,196 @@ def main_mx_conv0(args):
     print("wrote", out)
 
 
+def bench_mxf_search(model, q, T, S, rounds, window_s=0.3):
+    """conv0="mxfp8" with fused=True (the new launch) beside conv0="mxfp8" unfused and the default fused path, interleaved."""
+    from drn_amd import Grounder
+    tok, qlen = sentences(S, 7)
+    g = {}
+    for mode, kw in (("eager", {}), ("graph", {"graph": True})):
+        g["default_fused_" + mode] = Grounder(model, top_k=10, fused=True, **kw)
+        g["mx_unfused_" + mode] = Grounder(model, top_k=10, conv0="mxfp8", **kw)
+        g["mx_fused_" + mode] = Grounder(model, top_k=10, conv0="mxfp8", fused=True, **kw)
+    variants = {k: (lambda gr=gr: gr.search(tok, qlen, q, per_video=2)) for k, gr in g.items()}
+    hits = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(getattr(hits[a], f), getattr(hits[b], f)) for f in STATE)
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    res = {"T": T, "S": S, "videos": len(q), "pairs_per_step": S * len(q), "top_k": 10, "per_video": 2, "rounds": rounds,
+           "mx_fused_graph_equals_mx_fused_eager": same("mx_fused_graph", "mx_fused_eager"),
+           "mx_fused_hits_equal_mx_unfused": same("mx_fused_eager", "mx_unfused_eager"),
+           "first_hit_same_video_as_mx_unfused": int((hits["mx_fused_eager"].video[:, 0] == hits["mx_unfused_eager"].video[:, 0]).sum()),
+           "first_hit_score_largest_abs_difference_to_mx_unfused":
+               float((hits["mx_fused_eager"].score[:, 0] - hits["mx_unfused_eager"].score[:, 0]).abs().max()),
+           "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_min": min(ts), "ms_per_search_max": max(ts),
+                              "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    v = res["variants"]
+    for mode in ("eager", "graph"):
+        for other in ("mx_unfused_", "default_fused_"):
+            diff = v["mx_fused_" + mode]["ms_per_search_median"] - v[other + mode]["ms_per_search_median"]
+            spread = v[other + mode]["ms_per_search_max"] - v[other + mode]["ms_per_search_min"]
+            res["mx_fused_minus_" + other + mode] = {"ms": diff, "other_max_minus_min_ms": spread, "a_difference": abs(diff) > spread}
+    return res
+
+
+def bench_mxf_kernels(model, q, T, Q, rounds, window_s=0.3):
+    """bench_kernel's protocol, launch-inclusive, interleaved: drn_conv0_mx8_bn alone and behind bn_eval_scale_shift (what
+    functional.conv0_mx8_block launches inside fused_eval()); yardstick (a), the unfused mode's three launches back to back; yardstick
+    (b), the default fused path's gather + bn_eval_scale_shift + one-launch conv0 block (ops.conv_bn_eval); drn_conv0_mx8 alone."""
+    from drn_amd import functional as DF, ops
+    from drn_amd.model.basic_blocks import conv_bn
+    dev = q.codes.device
+    S = Q // NV
+    conv, bn = conv_bn(model.backbone_net.forward_conv0, "bench")
+    Cout = int(conv.weight.shape[0])
+    gate = torch.randn(S, q.Dp, device=dev)
+    pair = torch.arange(Q, dtype=torch.int32, device=dev)
+    pq, pv = torch.div(pair, NV, rounding_mode="floor"), torch.remainder(pair, NV)
+    vids = torch.arange(NV, dtype=torch.int32, device=dev)
+    gate1 = torch.randn(S, Cout, device=dev).index_select(0, pq.long())
+    g0 = torch.empty((Q, T, q.Dp + q.P), dtype=q.dtype, device=dev)
+    raw = torch.empty((Q, T, Cout), dtype=q.dtype, device=dev)
+    outs = [(torch.empty((Q, T, Cout), dtype=q.dtype, device=dev), torch.empty((Q, T, Cout), dtype=q.dtype, device=dev)) for _ in range(2)]
+    ss = torch.empty((2, Cout), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        wq = DF.conv0_mx8_weights(conv.weight, gate, q.D, q.Dp)
+        wp = DF.packed(conv.weight, (0, 2, 1), ops.BF16)
+    scale_shift = lambda: ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
+    level = lambda o: dict(raw=raw, ld_raw=Cout, ss=ss, out=o[0], ld_out=Cout, M=Q * T, L=T, up=None, ld_up=0, gate=gate1, gated=o[1],
+                           ld_gated=Cout)
+    conv0 = lambda o: ops.conv0_mx8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, wq[0], wq[1], wq[2], pq, pv, vids, raw, T, q.Dp, q.P)
+    fused = lambda o: ops.conv0_mx8_bn(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, wq[0], wq[1], wq[2], pq, pv, vids, ss, gate1, o[0],
+                                       o[1], T, q.Dp, q.P)
+    gather = lambda o: ops.gate_gather_packed_q8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, gate, pq, pv, vids, g0, T, q.Dp, q.P, ops.BF16)
+
+    def block(o):
+        desc = ops.gemm_desc(g0, wp, raw, Q * T, Cout, q.Dp + q.P, taps=3, stride=1, pad=1, Lout=T, Lsrc=T, lda=q.Dp + q.P)
+        if not ops.conv_bn_eval([desc], [level(o)], ops.BF16, True):
+            raise SystemExit("bench_search.py: ops.conv_bn_eval does not serve conv0 at these sizes")
+    launch = {"conv0_mx8_bn": fused, "scale_shift_then_conv0_mx8_bn": lambda o: (scale_shift(), fused(o)),
+              "a_conv0_mx8_scale_shift_bn_apply": lambda o: (conv0(o), scale_shift(), ops.bn_apply_multi([level(o)], Cout, ops.BF16, relu=True)),
+              "b_gather_scale_shift_conv_bn_eval": lambda o: (gather(o), scale_shift(), block(o)),
+              "conv0_mx8": conv0}
+
+    def run(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(outs[i & 1])
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    reps = {}
+    with torch.no_grad():
+        for k, fn in launch.items():
+            run(fn, 5)
+            reps[k] = max(10, int(window_s / (run(fn, 10) * 1e-6)))
+        ts = {k: [] for k in launch}
+        for _ in range(rounds):
+            for k, fn in launch.items():
+                ts[k].append(run(fn, reps[k]))
+    flop = 2.0 * Q * T * Cout * 3 * (q.Dp + q.P)
+    res = {"Q": Q, "T": T, "S": S, "C": q.Dp, "P": q.P, "Cout": Cout, "flop": flop,
+           "note": "launch-inclusive, device events around windows of ~0.3 s; out and gated in bf16, a gate row per pair"}
+    for k in launch:
+        us = statistics.median(ts[k])
+        res[k] = {"us_median": us, "us_min": min(ts[k]), "us_max": max(ts[k]), "us_rounds": ts[k], "launches_per_window": reps[k]}
+    for k in ("conv0_mx8_bn", "conv0_mx8"):
+        res[k]["tflops"] = flop / (res[k]["us_median"] * 1e-6) / 1e12
+    a, b, new = res["a_conv0_mx8_scale_shift_bn_apply"], res["b_gather_scale_shift_conv_bn_eval"], res["scale_shift_then_conv0_mx8_bn"]
+    res["new_minus_a_us"] = new["us_median"] - a["us_median"]
+    res["a_max_minus_min_us"] = a["us_max"] - a["us_min"]
+    res["faster_than_a_by_more_than_its_spread"] = a["us_median"] - new["us_median"] > res["a_max_minus_min_us"]
+    res["new_minus_b_us"] = new["us_median"] - b["us_median"]
+    res["faster_than_b_by_more_than_its_spread"] = b["us_median"] - new["us_median"] > b["us_max"] - b["us_min"]
+    return res
+
+
+def bench_mxf_agreement(model, q, T, S=8, nbatches=8):
+    """bench_mx_recall's sentences through the fused and the unfused conv0="mxfp8" mode: how far the two modes' answers are apart."""
+    from drn_amd import Grounder
+    fused, unfused = Grounder(model, top_k=10, conv0="mxfp8", fused=True), Grounder(model, top_k=10, conv0="mxfp8")
+    same_video = same_top10 = 0
+    worst = 0.0
+    for b in range(nbatches):
+        tok, qlen = sentences(S, 100 + b)
+        x, y = fused.search(tok, qlen, q, per_video=2), unfused.search(tok, qlen, q, per_video=2)
+        same_video += int((x.video[:, 0] == y.video[:, 0]).sum())
+        same_top10 += int((x.video == y.video).all(dim=1).sum())
+        worst = max(worst, float((x.score[:, 0] - y.score[:, 0]).abs().max()))
+    return {"T": T, "sentences": S * nbatches, "per_video": 2, "first_hit_same_video_share": same_video / (S * nbatches),
+            "top10_same_videos_in_order_share": same_top10 / (S * nbatches), "first_hit_score_largest_abs_difference": worst,
+            "note": "synthetic weights: this says how far the two modes are apart, nothing about recall on a trained checkpoint"}
+
+
+def mxf_tolerance_ratio():
+    """The random case of tests/test_search_mx8fused_gpu.py (Dp = 384, P = 256, Cout = 64, L = 40, bf16, scale / shift of mixed signs,
+    a gate per pair): the largest |out - want| and |gated - want gate| over their derived tolerances."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_search_mx8conv_gpu import raw_bound
+    from test_search_mx8fused_gpu import epilogue_case, run_bn
+    from drn_amd.index import mx8_conv0_reference
+    case, ss, gate = epilogue_case()
+    out, gated, _ = run_bn(case, 40, torch.bfloat16, ss=ss, gate=gate)
+    ref = mx8_conv0_reference(*case, 40)
+    mag = raw_bound(*case, 40, ref) - 2.0 ** -8 * ref.abs()
+    scale, shift = ss[0].double().cpu(), ss[1].double().cpu()
+    want = torch.relu(ref * scale + shift)
+    tol = scale.abs() * mag + 2.0 ** -8 * want.abs() + 2.0 ** -20 * ((ref * scale).abs() + shift.abs())
+    g1 = gate.double().cpu()[:, None, :]
+    tol_g = g1.abs() * tol * (1 + 2.0 ** -7) + 2.0 ** -8 * (want * g1).abs()
+    return {"Dp": 384, "P": 256, "Cout": 64, "L": 40, "out": "bf16",
+            "tolerance": "|scale| 3 (Dp + P) 2^-23 sum |a b| + 2^-8 |want| + 2^-20 (|ref scale| + |shift|)",
+            "largest_error_over_tolerance_out": float(((out.double().cpu() - want).abs() / tol.clamp_min(1e-30)).max()),
+            "largest_error_over_tolerance_gated": float(((gated.double().cpu() - want * g1).abs() / tol_g.clamp_min(1e-30)).max())}
+
+
+def main_mx_conv0_fused(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex
+    out = args.out or os.path.join(ROOT, "profiles", "search_mx8conv_fused_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, one quantised index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s; min and max of the rounds beside it",
+                      "clock": "host clock around searches ending in a device synchronise; device events for the kernel windows",
+                      "what": "Grounder(conv0=\"mxfp8\", fused=True) beside Grounder(conv0=\"mxfp8\") and Grounder(fused=True) on the same "
+                              "SearchIndex(quantize=\"mxfp8\"); a difference smaller than the other path's own max - min across rounds is "
+                              "no difference"},
+           "tolerance_ratio": mxf_tolerance_ratio(), "search": [], "kernel": [], "agreement": []}
+    print(json.dumps({"tolerance_ratio": res["tolerance_ratio"]}), flush=True)
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        q = SearchIndex.build(model, store, quantize="mxfp8")
+        del store
+        for Q in (512, 64):
+            res["kernel"].append(bench_mxf_kernels(model, q, T, Q, args.rounds))
+            print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        for S in (1, 8):
+            res["search"].append(bench_mxf_search(model, q, T, S, args.rounds))
+            print(json.dumps({"search": res["search"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        res["agreement"].append(bench_mxf_agreement(model, q, T))
+        print(json.dumps({"agreement": res["agreement"][-1]}), flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+        del q
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -634,6 +831,8 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
     ap.add_argument("--quantized", action="store_true", help="measure a SearchIndex built with quantize=\"mxfp8\" beside the plain index")
     ap.add_argument("--mx-conv0", action="store_true", help="measure Grounder(conv0=\"mxfp8\") beside the default path on one quantised index")
+    ap.add_argument("--mx-conv0-fused", action="store_true", help="measure Grounder(conv0=\"mxfp8\", fused=True) beside the unfused mode and "
+                                                                  "the default fused path on one quantised index")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
@@ -645,6 +844,8 @@ def main():
         return main_quantized(args)
     if args.mx_conv0:
         return main_mx_conv0(args)
+    if args.mx_conv0_fused:
+        return main_mx_conv0_fused(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
