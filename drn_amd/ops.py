@@ -1153,12 +1153,13 @@ def head_groups(xs, dxs=None, scales=None):
 
 def _head_calls(calls):
     """calls: list of dicts(groups (HeadGroup array), W, N, C, taps, exp_mode, + bias/out/z (forward) or dout/out/z/dW/dbias/
-    dscale/ws (backward)).  Up to 2 heads share one launch (drn_amd/csrc/heads.hip)."""
+    dscale/ws (backward), optionally accumulate_dx / accumulate_dw (default 0: overwrite)).  Up to 2 heads share one launch
+    (drn_amd/csrc/heads.hip)."""
     arr = (_lib.HeadCall * len(calls))()
     for d, c in zip(arr, calls):
         d.groups = ctypes.cast(c["groups"], ctypes.c_void_p)
         d.ngroups, d.N, d.C, d.taps, d.exp_mode = len(c["groups"]), c["N"], c["C"], c["taps"], int(c["exp_mode"])
-        d.accumulate_dx, d.accumulate_dw = int(c.get("accumulate_dx", 0)), 0
+        d.accumulate_dx, d.accumulate_dw = int(c.get("accumulate_dx", 0)), int(c.get("accumulate_dw", 0))
         d.dscale_stride = c["dscale"].stride(0) if c.get("dscale") is not None and c["dscale"].numel() > 1 else 1
         d.W, d.bias, d.out, d.z = _p(c["W"]), _p(c.get("bias")), _p(c.get("out")), _p(c.get("z"))
         d.dout, d.dW, d.dbias, d.dscale, d.ws = _p(c.get("dout")), _p(c.get("dW")), _p(c.get("dbias")), _p(c.get("dscale")), _p(c.get("ws"))
