@@ -466,33 +466,45 @@ __global__ __launch_bounds__(512) void conv0_mx8_tiled_kernel(const uint8_t* __r
     }
 }
 
+// The argument checks of drn_conv0_mx8_bn and drn_conv0_mx8_bn_tile: one list for both entries, the messages under the caller's name.
+static int conv0_mx8_bn_check(const char* entry, const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos,
+                              int ld_pos, int n_rows, int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes,
+                              const uint8_t* wscales, const void* wpos, int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv,
+                              const int32_t* vids, int Vc, const float* gate, int ldg, const void* out, int ld_out, const void* gated,
+                              int ld_gated, int Q, int L, int C, int P, int Cout) {
+  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && out && (P == 0 || (pos && wpos)),
+                "%s: null pointer", entry);
+  DRN_CHECK_ARG((gate != nullptr) == (gated != nullptr), "%s: gate and gated must come together", entry);
+  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
+                "%s: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", entry, n_rows, pad_row, Nv,
+                S, Vc, Q, L, C, P, Cout);
+  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "%s: C = %d is not a multiple of the block of %d columns", entry, C, MX8_BLOCK);
+  DRN_CHECK_ARG(P % 32 == 0, "%s: P = %d is not a multiple of the 32 columns of a position step", entry, P);
+  DRN_CHECK_ARG(Cout % 16 == 0, "%s: Cout = %d is not a multiple of 16", entry, Cout);
+  DRN_CHECK_ARG((long)Cout * C <= 0x7fffffffL && 3L * Cout * P <= 0x7fffffffL, "%s: a weight plane of %d x %d is beyond 2^31", entry,
+                Cout, C + P);
+  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL - MXT_ROWS && ((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256) <= 0x7fffffffL,
+                "%s: more than 2^31 rows", entry);
+  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_out >= Cout && (!gated || (ld_gated >= Cout && ldg >= Cout)),
+                "%s: a row stride is shorter than its row", entry);
+  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
+                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
+                "%s: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples", entry);
+  if (pq_host)
+    for (int p = 0; p < Q; ++p)
+      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "%s: pair %d reads sentence %d of %d", entry, p, (int)pq_host[p], S);
+  return DRN_OK;
+}
+
 extern "C" int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
                                 int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
                                 int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, const float* ss,
                                 const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q, int L, int C,
                                 int P, int Cout, void* stream) {
   drn_clear_status();
-  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && out && (P == 0 || (pos && wpos)),
-                "drn_conv0_mx8_bn: null pointer");
-  DRN_CHECK_ARG((gate != nullptr) == (gated != nullptr), "drn_conv0_mx8_bn: gate and gated must come together");
-  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
-                "drn_conv0_mx8_bn: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", n_rows, pad_row, Nv,
-                S, Vc, Q, L, C, P, Cout);
-  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "drn_conv0_mx8_bn: C = %d is not a multiple of the block of %d columns", C, MX8_BLOCK);
-  DRN_CHECK_ARG(P % 32 == 0, "drn_conv0_mx8_bn: P = %d is not a multiple of the 32 columns of a position step", P);
-  DRN_CHECK_ARG(Cout % 16 == 0, "drn_conv0_mx8_bn: Cout = %d is not a multiple of 16", Cout);
-  DRN_CHECK_ARG((long)Cout * C <= 0x7fffffffL && 3L * Cout * P <= 0x7fffffffL, "drn_conv0_mx8_bn: a weight plane of %d x %d is beyond 2^31",
-                Cout, C + P);
-  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL - MXT_ROWS && ((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256) <= 0x7fffffffL,
-                "drn_conv0_mx8_bn: more than 2^31 rows");
-  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_out >= Cout && (!gated || (ld_gated >= Cout && ldg >= Cout)),
-                "drn_conv0_mx8_bn: a row stride is shorter than its row");
-  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
-                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
-                "drn_conv0_mx8_bn: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples");
-  if (pq_host)
-    for (int p = 0; p < Q; ++p)
-      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "drn_conv0_mx8_bn: pair %d reads sentence %d of %d", p, (int)pq_host[p], S);
+  if (const int rc = conv0_mx8_bn_check("drn_conv0_mx8_bn", codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes,
+                                        wscales, wpos, S, pq, pq_host, pv, vids, Vc, gate, ldg, out, ld_out, gated, ld_gated, Q, L, C, P, Cout))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)(((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256));
   if (out_f32)
@@ -504,4 +516,318 @@ extern "C" int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_
                                                          Nv, wcodes, wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (bf16_t*)out,
                                                          ld_out, (bf16_t*)gated, ld_gated, Q, L, C, P, Cout);
   return drn_launch_status("drn_conv0_mx8_bn");
+}
+
+// ---------------------------------------------------------------- the same launch on narrow tiles, for grids that do not fill the chip
+// drn_conv0_mx8_bn_tile.  conv0_mx8_tiled_kernel's one tile shape puts cdiv(Q L, 256) x cdiv(Cout, 256) workgroups on the chip, each
+// walking its 3 (C / 128) K steps alone: 64 pairs x T = 32 are 8 workgroups on 256 CUs.  conv0_mx8_narrow_kernel<OUT, ROWS, COLS> is the
+// same computation on ROWS x COLS tiles (128 x 64, 64 x 64), 4 waves: wave w owns rows [16 MI (w % WR), +16 MI) x channels
+// [16 NJ (w / WR), +16 NJ) of the tile.  Everything that defines a value is the wide kernel's: the flattened (pair, t) rows and the row
+// table, the clamped addresses and the zeroing at the LDS write, the swizzle and the operand map, one pass per distinct sentence in the
+// order of first appearance, the tap-outer steps, the position columns after them, the epilogue from the unrounded fp32 value.  An
+// accumulator depends on its own row of A, its own column of B and the order of its K steps alone, and the passes of other sentences
+// add +0: each output element is bit for bit the wide kernel's (tests/test_search_mx8tiles_gpu.py).  No split-K, no atomics.
+// LDS: two stages of (ROWS + COLS) x (128 + 4) bytes + the row table and the sentence list: 52.0 KB at 128 x 64 (two workgroups per
+// CU: <= 256 registers), 34.3 KB at 64 x 64 (three per CU: <= 168 registers; the launch bound asks for that occupancy by ROWS).  The
+// grids a narrow tile is chosen for hold at most three 64 x 64 workgroups per CU, all resident at once, or at most four 128 x 64
+// workgroups per CU in two resident rounds (conv0_mx8_choose); registers beyond that go to a second set of prefetched loads.
+#define MXN_THREADS 256
+template <typename OUT, int ROWS, int COLS>
+__global__ __launch_bounds__(MXN_THREADS, ROWS == 64 ? 3 : 2) void conv0_mx8_narrow_kernel(
+    const uint8_t* __restrict__ codes, int ld_codes, const uint8_t* __restrict__ scales, int ld_scales, const bf16_t* __restrict__ pos,
+    int ld_pos, int n_rows, int pad_row, const int* __restrict__ prop_off, int Nv, const uint8_t* __restrict__ wcodes,
+    const uint8_t* __restrict__ wscales, const bf16_t* __restrict__ wpos, int S, const int* __restrict__ pq, const int* __restrict__ pv,
+    const int* __restrict__ vids, int Vc, const float* __restrict__ ss, const float* __restrict__ gate, int ldg, OUT* __restrict__ out,
+    int ld_out, OUT* __restrict__ gated, int ld_gated, int Q, int L, int C, int P, int Cout) {
+  static_assert(ROWS % 64 == 0 && COLS % 64 == 0 && ROWS + COLS <= MXN_THREADS, "one scale row per thread, whole waves on either side");
+  constexpr int WR = 2, WC = 2, MI = ROWS / WR / 16, NJ = COLS / WC / 16, KA = ROWS / 32, KB = COLS / 32;
+  __shared__ __attribute__((aligned(16))) uint8_t tA[2][ROWS * 128];
+  __shared__ __attribute__((aligned(16))) uint8_t tB[2][COLS * 128];
+  __shared__ unsigned sA[2][ROWS], sB[2][COLS];
+  __shared__ int qs[ROWS];                               // the (clamped) sentences of the tile's pairs; -1 once their pass is done
+  __shared__ i32x4 rinfo[ROWS];                          // per tile row: t, its video's first row and row count, its sentence (-1: past M)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ngroups = (Cout + COLS - 1) / COLS;
+  const int ng = blockIdx.x % ngroups;
+  const int M = Q * L, m0 = (int)(blockIdx.x / ngroups) * ROWS;                // (the entry refuses Q L + 256 > 2^31 - 1)
+  const int p0 = m0 / L, p1 = min((m0 + ROWS - 1) / L, Q - 1), npairs = p1 - p0 + 1;       // (<= ROWS: L >= 1)
+  const int cblocks = C / MX8_BLOCK, ksteps = (C + 127) / 128, nsteps = 3 * ksteps;
+  const int r = lane & 15, kq = lane >> 4;
+
+  if (tid < ROWS) {
+    const int m = m0 + tid, p = min(m / L, Q - 1);
+    const int slot = pv[p];
+    const int vd = (slot >= 0 && slot < Vc) ? vids[slot] : -1;
+    int base = 0, cnt = 0;
+    if (vd >= 0 && vd < Nv) {
+      base = prop_off[vd];
+      cnt = prop_off[vd + 1] - base;
+    }
+    rinfo[tid] = i32x4{m - p * L, base, cnt, m < M ? min(max(pq[p], 0), S - 1) : -1};
+  }
+  for (int i = tid; i < npairs; i += MXN_THREADS) qs[i] = min(max(pq[p0 + i], 0), S - 1);
+  __syncthreads();
+  auto src_of = [&](const i32x4 R, int u) { return (long)min(max(u >= 0 && u < R[2] ? R[1] + u : pad_row, 0), n_rows - 1); };
+  auto live_of = [&](const i32x4 R, int u, int q) { return R[3] == q && u >= 0 && u < L; };
+
+  // staging: thread -> the 16-byte slot (tid & 7) of rows (tid >> 3) + 32 k of A (k < KA) and of B (k < KB); one scale dword of row tid
+  // of A (tid < ROWS) or of row tid - ROWS of B (the next COLS threads): whole waves either way
+  const int srow0 = tid >> 3, sslot = tid & 7;
+  const int dst0 = srow0 * 128 + ((sslot ^ ((srow0 >> 1) & 7)) << 4);          // ((row >> 1) & 7 is the same for rows 32 apart)
+  const bool scaleA = tid < ROWS, scaleB = !scaleA && tid < ROWS + COLS;       // (wave-uniform)
+  const int scrow = scaleA ? tid : min(tid - ROWS, COLS - 1);
+  const int wr = (wave % WR) * 16 * MI, wc = (wave / WR) * 16 * NJ, n0 = ng * COLS + wc;
+
+  f32x4 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int pi = 0; pi < npairs; ++pi) {
+    const int q = qs[pi];
+    if (q < 0) continue;                                 // (uniform: a sentence that had its pass)
+    // fetch: the global loads of a step into one of TWO register sets, nothing consuming them (no wait); stage: mask them and write
+    // them to LDS.  The loads of step s + 2 are issued before the MFMAs of step s, and step s + 1 -- loaded a whole step earlier -- is
+    // written to the other LDS stage after them: a narrow tile has few MFMAs per step to hide a load behind, and the registers to spare.
+    struct Regs {
+      u32x4 ra[KA], rb[KB];
+      unsigned rsb[4], keep;                             // keep: bit k = A row k is live, bit 8 = the scale row is live
+    } set0, set1;
+    auto fetch = [&](int step, Regs& R_) {
+      u32x4(&ra)[KA] = R_.ra;
+      u32x4(&rb)[KB] = R_.rb;
+      unsigned(&rsb)[4] = R_.rsb;
+      unsigned& keep = R_.keep;
+      const int tap = step / ksteps, k0 = (step - tap * ksteps) * 128;
+      const unsigned colc = (unsigned)min(k0 + 16 * sslot, C - 16);
+      const uint8_t* wcp = wcodes + ((long)q * 3 + tap) * Cout * C;            // (uniform)
+      keep = 0;
+      int srow = srow0, scr = scrow;                     // (opaque, as in the wide kernel: offsets made of them are computed here, not kept
+      asm volatile("" : "+v"(srow), "+v"(scr));          //  across the whole K loop)
+#pragma unroll
+      for (int k = 0; k < KA; ++k) {
+        const i32x4 R = rinfo[srow + 32 * k];
+        const int u = R[0] + tap - 1;
+        ra[k] = *(const u32x4*)(codes + src_of(R, u) * ld_codes + colc);
+        keep |= (live_of(R, u, q) ? 1u : 0u) << k;
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k)
+        rb[k] = *(const u32x4*)(wcp + ((unsigned)min(ng * COLS + srow + 32 * k, Cout - 1) * (unsigned)C + colc));
+      {                                                  // (every thread, idle ones too: the number of loads in flight is one
+        const i32x4 R = rinfo[scaleA ? scr : 0];         //  number, so the wait before the LDS writes can leave the newer loads out)
+        const int u = R[0] + tap - 1;
+        keep |= ((!scaleA || live_of(R, u, q)) ? 1u : 0u) << 8;
+        const uint8_t* sp = scaleA ? scales + src_of(R, u) * ld_scales
+                                   : wscales + (((long)q * 3 + tap) * Cout + min(ng * COLS + scr, Cout - 1)) * cblocks;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rsb[g] = sp[min(k0 / MX8_BLOCK + g, cblocks - 1)];
+      }
+    };
+    auto stage = [&](int step, int buf, const Regs& R_) {
+      const u32x4(&ra)[KA] = R_.ra;
+      const u32x4(&rb)[KB] = R_.rb;
+      const unsigned(&rsb)[4] = R_.rsb;
+      const unsigned keep = R_.keep;
+      const int k0 = (step % ksteps) * 128;
+      const bool col_in = k0 + 16 * sslot < C;
+      const u32x4 zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < KA; ++k) *(u32x4*)(&tA[buf][dst0 + 32 * 128 * k]) = (col_in && ((keep >> k) & 1)) ? ra[k] : zero;
+#pragma unroll
+      for (int k = 0; k < KB; ++k) *(u32x4*)(&tB[buf][dst0 + 32 * 128 * k]) = col_in ? rb[k] : zero;
+      if (scaleA || scaleB) {
+        unsigned rs = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rs |= ((((keep >> 8) & 1) && k0 / MX8_BLOCK + g < cblocks) ? rsb[g] : 127u) << (8 * g);
+        (scaleA ? sA[buf] : sB[buf])[scrow] = rs;
+      }
+    };
+
+    // one K step: F takes the loads of step + 2, G holds those of step + 1
+    auto kstep = [&](int step, Regs& F, const Regs& G) {
+      const int buf = step & 1;
+      if (step + 2 < nsteps) fetch(step + 2, F);
+      MXT_FENCE();
+      i32x8 a[MI];
+      int sa[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int row = wr + 16 * i + r, sw = (row >> 1) & 7;
+        const u32x4 lo = *(const u32x4*)(&tA[buf][row * 128 + ((kq ^ sw) << 4)]);
+        const u32x4 hi = *(const u32x4*)(&tA[buf][row * 128 + (((kq + 4) ^ sw) << 4)]);
+        a[i] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        sa[i] = (int)((sA[buf][row] >> (8 * kq)) & 0xffu);
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {                     // (fragments past Cout read clamped rows and are not stored)
+        const int row = wc + 16 * j + r, sw = (row >> 1) & 7;
+        const u32x4 lo = *(const u32x4*)(&tB[buf][row * 128 + ((kq ^ sw) << 4)]);
+        const u32x4 hi = *(const u32x4*)(&tB[buf][row * 128 + (((kq + 4) ^ sw) << 4)]);
+        const i32x8 bw = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        const int sb = (int)((sB[buf][row] >> (8 * kq)) & 0xffu);
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], bw, acc[i][j], 0 /* cbsz: A is e4m3 */, 0 /* blgp: B is e4m3 */, 0,
+                                                                       sa[i], 0, sb);
+#pragma unroll
+        for (int i = 0; i < MI; ++i) asm volatile("" : "+v"(acc[i][j])::"memory");          // (the MFMAs stay before the LDS writes)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (step + 1 < nsteps) stage(step + 1, buf ^ 1, G);
+      __syncthreads();
+    };
+    fetch(0, set0);
+    stage(0, 0, set0);
+    fetch(1, set1);                                      // (nsteps >= 3)
+    __syncthreads();
+    for (int step = 0; step < nsteps; step += 2) {
+      kstep(step, set0, set1);
+      if (step + 1 < nsteps) kstep(step + 1, set1, set0);
+    }
+    // the position columns, fragments from memory
+    if (n0 < Cout) {
+      int rr = r, kk = kq;                               // (opaque, as in fetch)
+      asm volatile("" : "+v"(rr), "+v"(kk));
+      for (int tap = 0; tap < 3; ++tap) {
+        long src[MI];
+        bool live[MI];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const i32x4 R = rinfo[wr + 16 * i + rr];
+          const int u = R[0] + tap - 1;
+          src[i] = src_of(R, u);
+          live[i] = live_of(R, u, q);
+        }
+        for (int j0 = 0; j0 < P; j0 += 32) {
+          bf16x8 a[MI];
+#pragma unroll
+          for (int i = 0; i < MI; ++i) {
+            const bf16x8 v = *(const bf16x8*)(pos + src[i] * ld_pos + j0 + 8 * kk);
+            a[i] = live[i] ? v : bf16x8{};
+          }
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const bf16x8 bw = *(const bf16x8*)(wpos + (unsigned)((tap * Cout + min(n0 + 16 * j + rr, Cout - 1)) * P + j0 + 8 * kk));
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], bw, acc[i][j], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // this sentence is done: strike it from the list (every wave has read qs[pi]: the K loop's barriers lie in between)
+    for (int i = tid; i < npairs; i += MXN_THREADS)
+      if (qs[i] == q) qs[i] = -1;
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int m = m0 + wr + 16 * i + 4 * kq + x;
+      if (m >= M) continue;
+      const float* gp = gated ? gate + (long)(m / L) * ldg : nullptr;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int n = n0 + 16 * j + r;
+        if (n >= Cout) continue;
+        float v = acc[i][j][x];
+        if (ss) v = fmaxf(fmaf(v, ss[n], ss[Cout + n]), 0.f);
+        out[(long)m * ld_out + n] = (OUT)v;
+        if (gated) gated[(long)m * ld_gated + n] = (OUT)(v * gp[n]);
+      }
+    }
+}
+
+// The tile "choose" picks: a function of (Q L, Cout) and the device's CU count alone -- never of pq / pv / vids, so a captured launch
+// replays with other pairs.  W = the wide tile's workgroups, cdiv(Q L, 256) x cdiv(Cout, 256); a wide tile is 16 64 x 64 tiles or 8
+// 128 x 64 tiles at Cout = 256:
+//   16 W <= MXN_SMALL_UPTO_16THS x CUs                   ->  64 x 64  (3/16: its workgroups are resident at once, three per CU)
+//   else 16 W <= MXN_MID_UPTO_16THS x CUs                -> 128 x 64  (8/16: at most two resident rounds of two workgroups per CU)
+//   else                                                 -> 256 x 256 (the wide kernel: a third round of 128 x 64 costs more than it)
+// (the crossovers as measured: DESIGN.md section 3, profiles/search_mx8conv_tiles_bench.json).  No device: wide.
+#define MXN_SMALL_UPTO_16THS 3
+#define MXN_MID_UPTO_16THS 8
+static int conv0_mx8_cus() {                             // (as nt_resident_capacity, gemm_nt_bn.hip)
+  int dev = 0;                                           // A query that fails (a box without a device) answers 0 and takes its OWN error
+  if (hipGetDevice(&dev) != hipSuccess) {                // off the thread's sticky slot; one that succeeds touches nothing, so a pending
+    (void)hipGetLastError();                             // error of earlier work stays for whoever asks for it.
+    return 0;
+  }
+  static int cus[64];
+  if (dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+static void conv0_mx8_choose(long M, int Cout, int* rows, int* cols) {
+  const long W = (M + 255) / 256 * cdiv(Cout, 256), cus = conv0_mx8_cus();
+  if (cus <= 0 || 16 * W > MXN_MID_UPTO_16THS * cus) *rows = 256, *cols = 256;
+  else if (16 * W > MXN_SMALL_UPTO_16THS * cus) *rows = 128, *cols = 64;
+  else *rows = 64, *cols = 64;
+}
+
+extern "C" int drn_conv0_mx8_bn_choose(int Q, int L, int Cout, int* rows, int* cols) {
+  DRN_CHECK_ARG(rows && cols, "drn_conv0_mx8_bn_choose: null pointer");
+  DRN_CHECK_ARG(Q > 0 && L > 0 && Cout > 0 && (long)Q * L <= 0x7fffffffL - MXT_ROWS, "drn_conv0_mx8_bn_choose: bad args (Q %d, L %d, Cout %d)", Q,
+                L, Cout);
+  conv0_mx8_choose((long)Q * L, Cout, rows, cols);       // (a box without a device answers "wide": conv0_mx8_cus)
+  return DRN_OK;
+}
+
+template <typename OUT, int ROWS, int COLS>
+static void launch_conv0_mx8_narrow(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const bf16_t* pos, int ld_pos,
+                                    int n_rows, int pad_row, const int* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales,
+                                    const bf16_t* wpos, int S, const int* pq, const int* pv, const int* vids, int Vc, const float* ss,
+                                    const float* gate, int ldg, OUT* out, int ld_out, OUT* gated, int ld_gated, int Q, int L, int C, int P,
+                                    int Cout, hipStream_t st) {
+  const unsigned grid = (unsigned)(((long)Q * L + ROWS - 1) / ROWS * cdiv(Cout, COLS));
+  conv0_mx8_narrow_kernel<OUT, ROWS, COLS><<<grid, MXN_THREADS, 0, st>>>(codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off,
+                                                                         Nv, wcodes, wscales, wpos, S, pq, pv, vids, Vc, ss, gate, ldg, out, ld_out,
+                                                                         gated, ld_gated, Q, L, C, P, Cout);
+}
+
+extern "C" int drn_conv0_mx8_bn_tile(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos,
+                                     int n_rows, int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales,
+                                     const void* wpos, int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids,
+                                     int Vc, const float* ss, const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated,
+                                     int out_f32, int Q, int L, int C, int P, int Cout, int tile_rows, int tile_cols, void* stream) {
+  const bool choose = tile_rows == 0 && tile_cols == 0;
+  DRN_CHECK_ARG(choose || (tile_rows == 256 && tile_cols == 256) || (tile_rows == 128 && tile_cols == 64) || (tile_rows == 64 && tile_cols == 64),
+                "drn_conv0_mx8_bn_tile: no %d x %d tile (256 x 256, 128 x 64, 64 x 64; 0, 0: choose)", tile_rows, tile_cols);
+  DRN_CHECK_ARG(Q > 0 && L > 0 && Cout > 0 && (long)Q * L <= 0x7fffffffL - MXT_ROWS &&
+                    ((long)Q * L + 63) / 64 * cdiv(Cout, 64) <= 0x7fffffffL,
+                "drn_conv0_mx8_bn_tile: bad args (Q %d, L %d, Cout %d), or more than 2^31 rows or workgroups", Q, L, Cout);
+  if (choose) conv0_mx8_choose((long)Q * L, Cout, &tile_rows, &tile_cols);
+  if (tile_rows == 256)                                  // (the wide tile: the same entry, the same checks)
+    return drn_conv0_mx8_bn(codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales, wpos, S, pq, pq_host,
+                            pv, vids, Vc, ss, gate, ldg, out, ld_out, gated, ld_gated, out_f32, Q, L, C, P, Cout, stream);
+  drn_clear_status();
+  if (const int rc = conv0_mx8_bn_check("drn_conv0_mx8_bn_tile", codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes,
+                                        wscales, wpos, S, pq, pq_host, pv, vids, Vc, gate, ldg, out, ld_out, gated, ld_gated, Q, L, C, P, Cout))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+#define MXN_LAUNCH(OUT, ROWS, COLS)                                                                                                          \
+  launch_conv0_mx8_narrow<OUT, ROWS, COLS>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, \
+                                           wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (OUT*)out, ld_out, (OUT*)gated,     \
+                                           ld_gated, Q, L, C, P, Cout, st)
+  if (tile_rows == 128) {
+    if (out_f32) MXN_LAUNCH(float, 128, 64);
+    else MXN_LAUNCH(bf16_t, 128, 64);
+  } else {
+    if (out_f32) MXN_LAUNCH(float, 64, 64);
+    else MXN_LAUNCH(bf16_t, 64, 64);
+  }
+#undef MXN_LAUNCH
+  return drn_launch_status("drn_conv0_mx8_bn_tile");
 }

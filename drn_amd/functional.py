@@ -865,7 +865,8 @@ def conv0_mx8_weights(weight, gate0, D, Dp, out=None):
 def conv0_mx8_block(index, wq, pair_q, pair_v, vids, L, conv, bn, gate, dt):
     """conv0 -> eval BatchNorm -> ReLU (-> level-1 gate) of Q (sentence, video) pairs straight from a quantised SearchIndex, from the
     index's codes and the gated weights `wq` (conv0_mx8_weights) -> (out, gated), gated None without gate.  Inside fused_eval():
-    bn_eval_scale_shift and ONE ops.conv0_mx8_bn launch that applies the affine map, the ReLU and the gate to its fp32 accumulators.
+    bn_eval_scale_shift and ONE ops.conv0_mx8_bn launch that applies the affine map, the ReLU and the gate to its fp32 accumulators, on
+    the tile ops.conv0_mx8_bn_tile names for (Q L, Cout) (narrow tiles where the grid does not fill the chip; the same bits either way).
     Otherwise ops.conv0_mx8 writes raw (Q, L, Cout), then the unfused eval path's own launches (bn_eval_scale_shift + bn_apply_multi)
     as conv_block runs them."""
     wcodes, wscales, wpos = wq
@@ -876,7 +877,7 @@ def conv0_mx8_block(index, wq, pair_q, pair_v, vids, L, conv, bn, gate, dt):
     if FUSED_EVAL:
         ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
         ops.conv0_mx8_bn(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off, wcodes, wscales, wpos,
-                         pair_q, pair_v, vids, ss, gate, out, gated, L, index.Dp, index.P)
+                         pair_q, pair_v, vids, ss, gate, out, gated, L, index.Dp, index.P, tile="auto")
         return out, gated
     raw = torch.empty((Q, L, Cout), dtype=dt, device=dev)
     ops.conv0_mx8(index.codes, index.scales, index.pos if index.P else None, index.pad_row, index.prop_off, wcodes, wscales, wpos, pair_q,

@@ -774,13 +774,47 @@ def conv0_mx8(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, 
         int(vids.numel()), _p(raw), Cout, int(raw.dtype == torch.float32), Q, L, C, P, Cout, _stream()), "drn_conv0_mx8"))
 
 
-def conv0_mx8_bn(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, pv, vids, ss, gate, out, gated, L, C, P, pq_host=None):
+# The tiles drn_conv0_mx8_bn_tile ships, (rows of the flattened (pair, t) output, channels): the wide one, drn_conv0_mx8_bn's, first.
+CONV0_MX8_WIDE = (256, 256)
+CONV0_MX8_TILES = (CONV0_MX8_WIDE, (128, 64), (64, 64))
+# drn_conv0_mx8_bn_choose's rule (MXN_SMALL_UPTO_16THS / MXN_MID_UPTO_16THS of csrc/qconv.hip; tests/test_search_mx8tiles_cpu.py holds the
+# two together): with W = cdiv(Q L, 256) cdiv(Cout, 256) wide-tile workgroups, 64 x 64 while 16 W <= CONV0_MX8_SMALL_UPTO_16THS x CUs,
+# 128 x 64 while 16 W <= CONV0_MX8_MID_UPTO_16THS x CUs, wide above.
+CONV0_MX8_SMALL_UPTO_16THS = 3
+CONV0_MX8_MID_UPTO_16THS = 8
+
+
+def _conv0_mx8_tile_arg(tile):
+    """tile of conv0_mx8_bn -> None (the wide tile through drn_conv0_mx8_bn), "auto" or a shipped (rows, cols); anything else raises."""
+    if tile is None:
+        return None
+    if isinstance(tile, str):
+        if tile == "auto":
+            return tile
+    elif isinstance(tile, (tuple, list)) and len(tile) == 2 and all(type(v) is int for v in tile) and tuple(tile) in CONV0_MX8_TILES:
+        return tuple(tile)
+    raise _lib.DrnError("conv0_mx8_bn: tile must be None, \"auto\" or one of %s, not %r" % (list(CONV0_MX8_TILES), tile))
+
+
+def conv0_mx8_bn_tile(Q, L, Cout):
+    """(rows, cols) of the tile conv0_mx8_bn(tile="auto") takes for Q pairs of L rows and Cout channels on the current device
+    (drn_conv0_mx8_bn_choose): a function of (Q L, Cout) and the device's compute-unit count alone."""
+    rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().drn_conv0_mx8_bn_choose(int(Q), int(L), int(Cout), ctypes.byref(rows), ctypes.byref(cols)), "drn_conv0_mx8_bn_choose")
+    return int(rows.value), int(cols.value)
+
+
+def conv0_mx8_bn(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, pq, pv, vids, ss, gate, out, gated, L, C, P, pq_host=None,
+                 tile=None):
     """conv0_mx8 -> eval BatchNorm -> ReLU (-> gate) in ONE launch on LDS-staged tiles, without the raw tensor (drn_conv0_mx8_bn): the
     operands of conv0_mx8; ss (2, Cout) float32 contiguous as bn_eval_scale_shift writes it, or None for the bare convolution; gate
     (Q, >= Cout) float32 with unit column stride, one row per PAIR as bn_apply_multi takes it, or None; out and gated (None exactly
     when gate is) (Q, L, Cout) tensors of one dtype, bfloat16 or float32, contiguous or column slices of contiguous wider ones, written
     in place (nothing past a row's Cout columns is written):
-    out = relu(acc * scale + shift) from the fp32 accumulator, gated = that, unrounded, times the pair's gate row."""
+    out = relu(acc * scale + shift) from the fp32 accumulator, gated = that, unrounded, times the pair's gate row.
+    tile: None, the wide 256 x 256 tile through drn_conv0_mx8_bn; "auto", the tile conv0_mx8_bn_tile names for this grid; or one of
+    CONV0_MX8_TILES (drn_conv0_mx8_bn_tile).  Every tile writes bit for bit the same out / gated; the launch tag is conv0_mx8_bn."""
+    tile = _conv0_mx8_tile_arg(tile)
     if (gate is None) != (gated is None):
         raise _lib.DrnError("conv0_mx8_bn: gate and gated must come together (a gated output needs a gate)")
     dests = [("out", out)] + ([("gated", gated)] if gated is not None else [])
@@ -795,12 +829,16 @@ def conv0_mx8_bn(codes, scales, pos, pad_row, prop_off, wcodes, wscales, wpos, p
         raise _lib.DrnError("conv0_mx8_bn: gate must be (%d, >= %d) float32 with unit column stride" % (Q, Cout))
     _need_gpu(ss, gate)
     flops = 2.0 * Q * L * Cout * 3 * (C + P)
-    _timed("conv0_mx8_bn", flops, lambda: check(lib().drn_conv0_mx8_bn(
-        _p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
-        int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(wcodes), _p(wscales), _p(wpos), S, _p(pq), host, _p(pv), _p(vids),
-        int(vids.numel()), _p(ss), _p(gate), gate.stride(0) if gate is not None else 0, _p(out), out.stride(1), _p(gated),
-        gated.stride(1) if gated is not None else 0,
-        int(out.dtype == torch.float32), Q, L, C, P, Cout, _stream()), "drn_conv0_mx8_bn"))
+    args = (_p(codes), codes.stride(0), _p(scales), scales.stride(0), _p(pos), pos.stride(0) if pos is not None else 0, int(codes.shape[0]),
+            int(pad_row), _p(prop_off), int(prop_off.numel()) - 1, _p(wcodes), _p(wscales), _p(wpos), S, _p(pq), host, _p(pv), _p(vids),
+            int(vids.numel()), _p(ss), _p(gate), gate.stride(0) if gate is not None else 0, _p(out), out.stride(1), _p(gated),
+            gated.stride(1) if gated is not None else 0, int(out.dtype == torch.float32), Q, L, C, P, Cout)
+    if tile == "auto":                                   # (the chooser, by its module name: what a test or a benchmark replaces)
+        tile = conv0_mx8_bn_tile(Q, L, Cout)
+    if tile is None:
+        _timed("conv0_mx8_bn", flops, lambda: check(lib().drn_conv0_mx8_bn(*args, _stream()), "drn_conv0_mx8_bn"))
+    else:
+        _timed("conv0_mx8_bn", flops, lambda: check(lib().drn_conv0_mx8_bn_tile(*args, tile[0], tile[1], _stream()), "drn_conv0_mx8_bn_tile"))
 
 
 def pool_props_lds_rows(B, D, dtype):

@@ -320,6 +320,21 @@ int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, 
                      const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids, int Vc,
                      const float* ss, const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q,
                      int L, int C, int P, int Cout, void* stream);
+/* drn_conv0_mx8_bn_tile: drn_conv0_mx8_bn on a tile of tile_rows x tile_cols (rows of the flattened (pair, t) output x channels): 256 x 256
+ * is drn_conv0_mx8_bn itself; 128 x 64 and 64 x 64 put 8 and 16 times as many workgroups on the chip, for grids that do not fill it.  The
+ * same arguments, the same checks, and bit for bit the same out / gated for every tile: an output element sums its own K in the same
+ * fixed order whatever the tile (no split-K, no atomics).  tile_rows = tile_cols = 0: the tile drn_conv0_mx8_bn_choose names.  Any other
+ * shape is refused before the launch. */
+int drn_conv0_mx8_bn_tile(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                          int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
+                          int S, const int32_t* pq, const int32_t* pq_host /*host, may be NULL*/, const int32_t* pv, const int32_t* vids,
+                          int Vc, const float* ss, const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated,
+                          int out_f32, int Q, int L, int C, int P, int Cout, int tile_rows, int tile_cols, void* stream);
+/* drn_conv0_mx8_bn_choose: the tile drn_conv0_mx8_bn_tile(..., 0, 0, ...) takes -> *rows, *cols.  A function of Q * L, Cout and the
+ * current device's compute-unit count alone (never of the pairs: a captured launch replays with other pairs): with W = ceil(Q L / 256) x
+ * ceil(Cout / 256) wide-tile workgroups, 64 x 64 while 16 W <= 3 compute units, 128 x 64 while 16 W <= 8 compute units (W up to half the
+ * compute units), the wide tile above.  Without a device: the wide tile.  A pending HIP error of earlier work is left in place. */
+int drn_conv0_mx8_bn_choose(int Q, int L, int Cout, int* rows, int* cols);
 /* backward of the query gating x = q[:, :, None] * x (model/backbone.py:28-30):
  * dC = (add ? add : 0) + dG * gate[seq] (skipped when dC is NULL); dgate[seq][c] = sum_t dG*act;
  * dsum (optional, [nseq][C]) = sum_t dG * gate[seq]: per-clip column sums of dC's gated term (bias-gradient partials) */

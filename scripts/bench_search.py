@@ -40,7 +40,15 @@
            epilogue) beside Grounder(conv0="mxfp8") and the default Grounder(fused=True), ms per search (S in {1, 8}, T in {256, 32},
            eager and by graph replay); the launch alone at 512 and 64 pairs beside its yardsticks (a) drn_conv0_mx8 +
            bn_eval_scale_shift + bn_apply_multi back to back and (b) the gather + the one-launch conv0 block of the default fused path;
-           the first-hit agreement of the fused and the unfused mode; the error / tolerance ratios of tests/test_search_mx8fused_gpu.py."""
+           the first-hit agreement of the fused and the unfused mode; the error / tolerance ratios of tests/test_search_mx8fused_gpu.py.
+
+  --mx-conv0-tiles   instead of the above -> profiles/search_mx8conv_tiles_bench.json, by the same protocol on one quantised index: the
+           fused launch behind bn_eval_scale_shift on every tile drn_conv0_mx8_bn_tile ships, on the tile the chooser picks ("auto") and
+           on the wide tile through drn_conv0_mx8_bn, beside the default fused path's gather + one-launch conv0 block, at 512 and 64
+           pairs x T in {256, 32}, at the grids between them on either side of the rule's two crossovers (W = 16 ... 56 and 80 ... 255 wide
+           workgroups) and at a T = 32 shortlist step of 8 sentences x 4 candidates (as planned and shuffled); searches by
+           graph replay (S in {1, 8}, T in {256, 32}) with the chooser as shipped, with the chooser held to the wide tile, and on the
+           default Grounder(fused=True).  The chooser's rule rests on these numbers."""
 import argparse
 import json
 import os
@@ -822,6 +830,184 @@ def main_mx_conv0_fused(args):
     print("wrote", out)
 
 
+def bench_mxt_kernels(model, q, T, S, pq, pv, vids, what, rounds, window_s=0.3):
+    """bench_mxf_kernels' protocol on one list of pairs: bn_eval_scale_shift + drn_conv0_mx8_bn_tile on every shipped tile forced, on
+    "auto", on the wide tile through drn_conv0_mx8_bn itself (the kernel before the narrow tiles, in the same process), and the default
+    fused path's gather + bn_eval_scale_shift + one-launch conv0 block."""
+    from drn_amd import functional as DF, ops
+    from drn_amd.model.basic_blocks import conv_bn
+    dev = q.codes.device
+    Q = int(pq.numel())
+    conv, bn = conv_bn(model.backbone_net.forward_conv0, "bench")
+    Cout = int(conv.weight.shape[0])
+    gate = torch.randn(S, q.Dp, device=dev)
+    gate1 = torch.randn(S, Cout, device=dev).index_select(0, pq.long())
+    g0 = torch.empty((Q, T, q.Dp + q.P), dtype=q.dtype, device=dev)
+    raw = torch.empty((Q, T, Cout), dtype=q.dtype, device=dev)
+    outs = [(torch.empty((Q, T, Cout), dtype=q.dtype, device=dev), torch.empty((Q, T, Cout), dtype=q.dtype, device=dev)) for _ in range(2)]
+    ss = torch.empty((2, Cout), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        wq = DF.conv0_mx8_weights(conv.weight, gate, q.D, q.Dp)
+        wp = DF.packed(conv.weight, (0, 2, 1), ops.BF16)
+    scale_shift = lambda: ops.bn_eval_scale_shift(Cout, bn.weight, bn.bias, conv.bias, bn.running_mean, bn.running_var, bn.eps, ss)
+    level = lambda o: dict(raw=raw, ld_raw=Cout, ss=ss, out=o[0], ld_out=Cout, M=Q * T, L=T, up=None, ld_up=0, gate=gate1, gated=o[1],
+                           ld_gated=Cout)
+    fused = lambda o, tile: ops.conv0_mx8_bn(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, wq[0], wq[1], wq[2], pq, pv, vids, ss, gate1,
+                                             o[0], o[1], T, q.Dp, q.P, tile=tile)
+    gather = lambda o: ops.gate_gather_packed_q8(q.codes, q.scales, q.pos, q.pad_row, q.prop_off, gate, pq, pv, vids, g0, T, q.Dp, q.P, ops.BF16)
+
+    def block(o):
+        desc = ops.gemm_desc(g0, wp, raw, Q * T, Cout, q.Dp + q.P, taps=3, stride=1, pad=1, Lout=T, Lsrc=T, lda=q.Dp + q.P)
+        if not ops.conv_bn_eval([desc], [level(o)], ops.BF16, True):
+            raise SystemExit("bench_search.py: ops.conv_bn_eval does not serve conv0 at these sizes")
+    launch = {"wide": lambda o: (scale_shift(), fused(o, None)), "auto": lambda o: (scale_shift(), fused(o, "auto"))}
+    for tile in ops.CONV0_MX8_TILES[1:]:
+        launch["tile_%dx%d" % tile] = lambda o, tile=tile: (scale_shift(), fused(o, tile))
+    launch["default_gather_scale_shift_conv_bn_eval"] = lambda o: (gather(o), scale_shift(), block(o))
+
+    def run(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(outs[i & 1])
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    reps, bits = {}, {}
+    with torch.no_grad():
+        for k, fn in launch.items():
+            run(fn, 5)
+            reps[k] = max(10, int(window_s / (run(fn, 10) * 1e-6)))
+            fn(outs[0])
+            bits[k] = (outs[0][0].clone(), outs[0][1].clone())
+        ts = {k: [] for k in launch}
+        for _ in range(rounds):
+            for k, fn in launch.items():
+                ts[k].append(run(fn, reps[k]))
+    res = {"what": what, "Q": Q, "T": T, "S": S, "C": q.Dp, "P": q.P, "Cout": Cout, "auto_tile": list(ops.conv0_mx8_bn_tile(Q, T, Cout)),
+           "wide_workgroups": -(-Q * T // 256) * -(-Cout // 256),
+           "note": "launch-inclusive, device events around windows of ~0.3 s, each launch behind bn_eval_scale_shift; out and gated in bf16"}
+    for k in launch:
+        res[k] = {"us_median": statistics.median(ts[k]), "us_min": min(ts[k]), "us_max": max(ts[k]), "us_rounds": ts[k],
+                  "launches_per_window": reps[k]}
+        if k != "default_gather_scale_shift_conv_bn_eval":
+            res[k]["bits_equal_wide"] = bool(torch.equal(bits[k][0], bits["wide"][0]) and torch.equal(bits[k][1], bits["wide"][1]))
+    wide = res["wide"]
+    spread = wide["us_max"] - wide["us_min"]
+    res["wide_max_minus_min_us"] = spread
+    for k in launch:
+        if k not in ("wide", "default_gather_scale_shift_conv_bn_eval"):
+            res[k]["faster_than_wide_by_more_than_its_spread"] = wide["us_median"] - res[k]["us_median"] > spread
+            res[k]["slower_than_wide_by_more_than_its_spread"] = res[k]["us_median"] - wide["us_median"] > spread
+    res["auto_minus_default_us"] = res["auto"]["us_median"] - res["default_gather_scale_shift_conv_bn_eval"]["us_median"]
+    return res
+
+
+def bench_mxt_search(model, q, T, S, rounds, window_s=0.3):
+    """Searches by graph replay: conv0="mxfp8", fused=True with the chooser as shipped, the same with the chooser held to the wide tile
+    (captured while ops.conv0_mx8_bn_tile is replaced), and the default fused path."""
+    from drn_amd import Grounder, ops
+    tok, qlen = sentences(S, 7)
+    g = {"default_fused_graph": Grounder(model, top_k=10, fused=True, graph=True),
+         "mx_fused_auto_graph": Grounder(model, top_k=10, conv0="mxfp8", fused=True, graph=True),
+         "mx_fused_wide_graph": Grounder(model, top_k=10, conv0="mxfp8", fused=True, graph=True)}
+    variants = {k: (lambda gr=gr: gr.search(tok, qlen, q, per_video=2)) for k, gr in g.items()}
+    chooser, tiles = ops.conv0_mx8_bn_tile, []
+    ops.conv0_mx8_bn_tile = lambda Q, L, Cout: tiles.append(chooser(Q, L, Cout)) or ops.CONV0_MX8_WIDE
+    try:
+        hits = {"mx_fused_wide_graph": variants["mx_fused_wide_graph"]()}                    # (the capture: the tile is part of it)
+    finally:
+        ops.conv0_mx8_bn_tile = chooser
+    for k in ("default_fused_graph", "mx_fused_auto_graph"):
+        hits[k] = variants[k]()
+    torch.cuda.synchronize()
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    res = {"T": T, "S": S, "videos": len(q), "pairs_per_step": S * len(q), "top_k": 10, "per_video": 2, "rounds": rounds,
+           "auto_tiles": sorted(set(map(tuple, tiles))),
+           "auto_hits_equal_wide_hits": all(torch.equal(getattr(hits["mx_fused_auto_graph"], f), getattr(hits["mx_fused_wide_graph"], f))
+                                            for f in STATE),
+           "variants": {}}
+    for k, ts in times.items():
+        res["variants"][k] = {"ms_per_search_median": statistics.median(ts), "ms_per_search_min": min(ts), "ms_per_search_max": max(ts),
+                              "ms_per_search_rounds": ts, "searches_per_window": reps[k]}
+    v = res["variants"]
+    for other in ("mx_fused_wide_graph", "default_fused_graph"):
+        diff = v["mx_fused_auto_graph"]["ms_per_search_median"] - v[other]["ms_per_search_median"]
+        spread = v[other]["ms_per_search_max"] - v[other]["ms_per_search_min"]
+        res["auto_minus_" + other] = {"ms": diff, "other_max_minus_min_ms": spread, "a_difference": abs(diff) > spread}
+    return res
+
+
+CROSSOVER_PAIRS = {256: (80, 96, 112, 128, 129, 160, 192, 255), 32: (128, 256, 384, 392, 448)}
+
+
+def main_mx_conv0_tiles(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex, ops
+    from drn_amd.grounding import plan_pairs
+    out = args.out or os.path.join(ROOT, "profiles", "search_mx8conv_tiles_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    dev = "cuda:0"
+    res = {"device": torch.cuda.get_device_name(0), "compute_units": torch.cuda.get_device_properties(0).multi_processor_count,
+           "measured_on": "MI355X, one process, one quantised index resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median over rounds of the mean time of a window of ~0.3 s; min and max of the rounds beside it",
+                      "clock": "host clock around searches ending in a device synchronise; device events for the kernel windows",
+                      "what": "drn_conv0_mx8_bn_tile on every shipped tile, on the chosen one and on the wide tile, beside the default fused "
+                              "path, on the same SearchIndex(quantize=\"mxfp8\"); a difference smaller than the wide tile's own max - min "
+                              "across rounds is no difference"},
+           "tiles": [list(t) for t in ops.CONV0_MX8_TILES],
+           "rule": {"W": "cdiv(Q L, 256) x cdiv(Cout, 256), the wide tile's workgroups",
+                    "64x64": "16 W <= %d x compute units" % ops.CONV0_MX8_SMALL_UPTO_16THS,
+                    "128x64": "else 16 W <= %d x compute units" % ops.CONV0_MX8_MID_UPTO_16THS, "wide": "above"},
+           "kernel": [], "search": []}
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, dev)
+        q = SearchIndex.build(model, store, quantize="mxfp8")
+        del store
+        vids = torch.arange(NV, dtype=torch.int32, device=dev)
+        # the four grids of the README, then the grids between them that the rule's two crossovers are read from: W = 80 ... 255 wide
+        # workgroups (T = 256: one per pair) on either side of 128 x 64 | wide, W = 16 ... 56 (T = 32: one per 8 pairs) of 64 x 64 | 128 x 64
+        for Q, what in [(512, "cartesian"), (64, "cartesian")] + [(Q, "cartesian, crossover") for Q in CROSSOVER_PAIRS[T]]:
+            pair = torch.arange(Q, dtype=torch.int32, device=dev)
+            pq, pv = torch.div(pair, NV, rounding_mode="floor"), torch.remainder(pair, NV)
+            res["kernel"].append(bench_mxt_kernels(model, q, T, -(-Q // NV), pq, pv, vids, what, args.rounds))
+            print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        if T == 32:
+            # a shortlist step: 8 sentences x 4 candidates each, one chunk of 32 pairs as plan_pairs emits it (sorted by sentence: a
+            # 256-row tile holds two sentences), and the same pairs shuffled (up to eight sentences in a 256-row tile, two in a 64-row one)
+            gen = torch.Generator().manual_seed(3)
+            lists = [torch.randperm(NV, generator=gen)[:4].tolist() for _ in range(8)]
+            plan = plan_pairs(lists, NV, 32, 32, 4)
+            assert plan.pair_q.shape[0] == 1
+            pq, pv = torch.from_numpy(plan.pair_q[0]).to(dev), torch.from_numpy(plan.pair_v[0]).to(dev)
+            pvids = torch.from_numpy(plan.vids[0]).to(dev)
+            perm = torch.randperm(32, generator=gen).to(dev)
+            for what, a, b in (("shortlist 8 x 4, as planned", pq, pv), ("shortlist 8 x 4, shuffled", pq[perm].contiguous(), pv[perm].contiguous())):
+                res["kernel"].append(bench_mxt_kernels(model, q, T, 8, a, b, pvids, what, args.rounds))
+                print(json.dumps({"kernel": res["kernel"][-1]}), flush=True)
+                json.dump(res, open(out, "w"), indent=1)
+        for S in (1, 8):
+            res["search"].append(bench_mxt_search(model, q, T, S, args.rounds))
+            print(json.dumps({"search": res["search"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+        del q
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -833,6 +1019,8 @@ def main():
     ap.add_argument("--mx-conv0", action="store_true", help="measure Grounder(conv0=\"mxfp8\") beside the default path on one quantised index")
     ap.add_argument("--mx-conv0-fused", action="store_true", help="measure Grounder(conv0=\"mxfp8\", fused=True) beside the unfused mode and "
                                                                   "the default fused path on one quantised index")
+    ap.add_argument("--mx-conv0-tiles", action="store_true", help="measure the narrow tiles of the fused FP8 conv0 and the chooser beside the "
+                                                                  "wide tile and the default fused path on one quantised index")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
@@ -846,6 +1034,8 @@ def main():
         return main_mx_conv0(args)
     if args.mx_conv0_fused:
         return main_mx_conv0_fused(args)
+    if args.mx_conv0_tiles:
+        return main_mx_conv0_tiles(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "search_bench.json")
     from bench_store import build_store
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
