@@ -55,6 +55,68 @@ extern "C" int drn_gate_quantize_weights_mx8(const float* w, int ld_w, const flo
   return drn_launch_status("drn_gate_quantize_weights_mx8");
 }
 
+// ---------------------------------------------------------------- conv0 on the codes: operands, checks
+// The operands of every conv0 entry below, filled once per entry, checked by one function and unpacked by one launch function per
+// kernel family.  drn_conv0_mx8 writes its raw output through out / ld_out and leaves ss, gate and gated null.  (The kernels keep their
+// flat parameter lists and their own bodies.  Both ways of folding the two LDS-staged kernels were built with this struct as the kernel
+// argument and measured: one template on all three tiles was 1 to 2 % slower at 256 x 256, two kernels made of shared device functions
+// 1 to 3 % slower on every tile -- DESIGN.md section 3, profiles/search_mx8conv_onetemplate_bench.json.)
+struct Conv0Mx8Args {
+  const uint8_t *codes, *scales;                         // the index: rows of C codes, C / 32 scale bytes, P position values
+  const bf16_t* pos;
+  const int* prop_off;
+  const uint8_t *wcodes, *wscales;                       // the gated weights [S][3][Cout][C], [..][C / 32], the position weights [3][Cout][P]
+  const bf16_t* wpos;
+  const int *pq, *pv, *vids;
+  const float *ss, *gate;                                // the epilogue of the fused entries
+  void *out, *gated;
+  int ld_codes, ld_scales, ld_pos, n_rows, pad_row, Nv, S, Vc, ldg, ld_out, ld_gated, Q, L, C, P, Cout;
+};
+// (by the parameter names that the three entries share)
+#define CONV0_MX8_ARGS(ss, gate, ldg, out, ld_out, gated, ld_gated)                                                                         \
+  Conv0Mx8Args {                                                                                                                            \
+    codes, scales, (const bf16_t*)pos, prop_off, wcodes, wscales, (const bf16_t*)wpos, pq, pv, vids, ss, gate, out, gated, ld_codes,        \
+        ld_scales, ld_pos, n_rows, pad_row, Nv, S, Vc, ldg, ld_out, ld_gated, Q, L, C, P, Cout                                              \
+  }
+
+// The rows of the widest LDS tile: the fused kernels compute a tile's first row + its rows in int, so Q L stays that far below 2^31.
+#define MXT_ROWS 256
+
+// The argument checks of all three entries, the messages under the caller's name.  fused: the entries with the epilogue, whose
+// kernels index a weight plane in 32 bits and walk tiles of up to MXT_ROWS rows.
+static int conv0_mx8_check(const char* entry, const Conv0Mx8Args& a, const int32_t* pq_host, bool fused) {
+  const int Q = a.Q, L = a.L, C = a.C, P = a.P, Cout = a.Cout;
+  DRN_CHECK_ARG(a.codes && a.scales && a.prop_off && a.wcodes && a.wscales && a.pq && a.pv && a.vids && a.out && (P == 0 || (a.pos && a.wpos)),
+                "%s: null pointer", entry);
+  if (fused) DRN_CHECK_ARG((a.gate != nullptr) == (a.gated != nullptr), "%s: gate and gated must come together", entry);
+  DRN_CHECK_ARG(a.n_rows > 0 && a.pad_row >= 0 && a.pad_row < a.n_rows && a.Nv > 0 && a.S > 0 && a.Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 &&
+                    Cout > 0,
+                "%s: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", entry, a.n_rows, a.pad_row, a.Nv,
+                a.S, a.Vc, Q, L, C, P, Cout);
+  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "%s: C = %d is not a multiple of the block of %d columns", entry, C, MX8_BLOCK);
+  DRN_CHECK_ARG(P % 32 == 0, "%s: P = %d is not a multiple of the 32 columns of a position step", entry, P);
+  DRN_CHECK_ARG(Cout % 16 == 0, "%s: Cout = %d is not a multiple of 16", entry, Cout);
+  if (fused) {
+    DRN_CHECK_ARG((long)Cout * C <= 0x7fffffffL && 3L * Cout * P <= 0x7fffffffL, "%s: a weight plane of %d x %d is beyond 2^31", entry, Cout,
+                  C + P);
+    DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL - MXT_ROWS &&
+                      ((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256) <= 0x7fffffffL,
+                  "%s: more than 2^31 rows", entry);
+  } else {
+    DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL && (long)Q * cdiv(L, 16) * cdiv(Cout, 256) <= 0x7fffffffL, "%s: more than 2^31 rows", entry);
+  }
+  DRN_CHECK_ARG(a.ld_codes >= C && a.ld_scales >= C / MX8_BLOCK && (P == 0 || a.ld_pos >= P) && a.ld_out >= Cout &&
+                    (!a.gated || (a.ld_gated >= Cout && a.ldg >= Cout)),
+                "%s: a row stride is shorter than its row", entry);
+  DRN_CHECK_ARG(a.ld_codes % 16 == 0 && (P == 0 || a.ld_pos % 8 == 0) &&
+                    ((((uintptr_t)a.codes) | ((uintptr_t)a.wcodes) | ((uintptr_t)(P ? a.pos : nullptr)) | ((uintptr_t)(P ? a.wpos : nullptr))) & 15) == 0,
+                "%s: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples", entry);
+  if (pq_host)
+    for (int p = 0; p < Q; ++p)
+      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < a.S, "%s: pair %d reads sentence %d of %d", entry, p, (int)pq_host[p], a.S);
+  return DRN_OK;
+}
+
 // ---------------------------------------------------------------- conv0 on the codes
 // One workgroup = 4 waves = 16 * MI output rows of ONE pair (an M tile never spans two pairs: they may belong to different sentences) x
 // up to 256 output channels, wave w owning channels [64 w, 64 w + 64) as 4 fragments of 16.  No LDS: both operands of
@@ -188,19 +250,19 @@ __global__ __launch_bounds__(256) void conv0_mx8_kernel(const uint8_t* __restric
     }
 }
 
+// The argument list that all three kernels begin with, from the operand struct.
+#define CONV0_MX8_OPERANDS                                                                                                                    \
+  a.codes, a.ld_codes, a.scales, a.ld_scales, a.pos, a.ld_pos, a.n_rows, a.pad_row, a.prop_off, a.Nv, a.wcodes, a.wscales, a.wpos, a.S, a.pq, \
+      a.pv, a.vids, a.Vc
 template <typename OUT>
-static void launch_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const bf16_t* pos, int ld_pos, int n_rows,
-                             int pad_row, const int* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const bf16_t* wpos, int S,
-                             const int* pq, const int* pv, const int* vids, int Vc, OUT* raw, int ld_raw, int Q, int L, int C, int P, int Cout,
-                             hipStream_t st) {
-  const int ngroups = cdiv(Cout, 256);
-#define CONV0_MX8_LAUNCH(MI)                                                                                                          \
-  conv0_mx8_kernel<MI, OUT><<<(unsigned)((long)Q * cdiv(L, 16 * MI) * ngroups), 256, 0, st>>>(                                        \
-      codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales, wpos, S, pq, pv, vids, Vc, raw, \
-      ld_raw, Q, L, C, P, Cout)
+static void launch_conv0_mx8(const Conv0Mx8Args& a, hipStream_t st) {
+  const long per_mtile = (long)a.Q * cdiv(a.Cout, 256);
+#define CONV0_MX8_LAUNCH(MI)                                                                                                             \
+  conv0_mx8_kernel<MI, OUT><<<(unsigned)(per_mtile * cdiv(a.L, 16 * MI)), 256, 0, st>>>(CONV0_MX8_OPERANDS, (OUT*)a.out, a.ld_out, a.Q, a.L, \
+                                                                                         a.C, a.P, a.Cout)
   // rows of one pair per workgroup: as many as the sequence fills, up to 64
-  if (L <= 16) CONV0_MX8_LAUNCH(1);
-  else if (L <= 32) CONV0_MX8_LAUNCH(2);
+  if (a.L <= 16) CONV0_MX8_LAUNCH(1);
+  else if (a.L <= 32) CONV0_MX8_LAUNCH(2);
   else CONV0_MX8_LAUNCH(4);
 #undef CONV0_MX8_LAUNCH
 }
@@ -210,30 +272,10 @@ extern "C" int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* 
                              int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, void* raw,
                              int ld_raw, int out_f32, int Q, int L, int C, int P, int Cout, void* stream) {
   drn_clear_status();
-  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && raw && (P == 0 || (pos && wpos)),
-                "drn_conv0_mx8: null pointer");
-  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
-                "drn_conv0_mx8: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", n_rows, pad_row, Nv, S,
-                Vc, Q, L, C, P, Cout);
-  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "drn_conv0_mx8: C = %d is not a multiple of the block of %d columns", C, MX8_BLOCK);
-  DRN_CHECK_ARG(P % 32 == 0, "drn_conv0_mx8: P = %d is not a multiple of the 32 columns of a position step", P);
-  DRN_CHECK_ARG(Cout % 16 == 0, "drn_conv0_mx8: Cout = %d is not a multiple of 16", Cout);
-  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL && (long)Q * cdiv(L, 16) * cdiv(Cout, 256) <= 0x7fffffffL, "drn_conv0_mx8: more than 2^31 rows");
-  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_raw >= Cout,
-                "drn_conv0_mx8: a row stride is shorter than its row");
-  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
-                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
-                "drn_conv0_mx8: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples");
-  if (pq_host)
-    for (int p = 0; p < Q; ++p)
-      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "drn_conv0_mx8: pair %d reads sentence %d of %d", p, (int)pq_host[p], S);
-  hipStream_t st = (hipStream_t)stream;
-  if (out_f32)
-    launch_conv0_mx8<float>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales,
-                            (const bf16_t*)wpos, S, pq, pv, vids, Vc, (float*)raw, ld_raw, Q, L, C, P, Cout, st);
-  else
-    launch_conv0_mx8<bf16_t>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales,
-                             (const bf16_t*)wpos, S, pq, pv, vids, Vc, (bf16_t*)raw, ld_raw, Q, L, C, P, Cout, st);
+  const Conv0Mx8Args a = CONV0_MX8_ARGS(nullptr, nullptr, 0, raw, ld_raw, nullptr, 0);
+  if (const int rc = conv0_mx8_check("drn_conv0_mx8", a, pq_host, false)) return rc;
+  if (out_f32) launch_conv0_mx8<float>(a, (hipStream_t)stream);
+  else launch_conv0_mx8<bf16_t>(a, (hipStream_t)stream);
   return drn_launch_status("drn_conv0_mx8");
 }
 
@@ -261,7 +303,6 @@ extern "C" int drn_conv0_mx8(const uint8_t* codes, int ld_codes, const uint8_t* 
 // Addresses: clamped exactly as in conv0_mx8_kernel; a masked row is loaded from its clamped address and then zeroed.
 // Epilogue, from the fp32 accumulator: v = relu(fmaf(acc, scale, shift)) with (scale, shift) = ss[n], ss[Cout + n]
 // (bn_eval_scale_shift's table; ss NULL: v = acc), out = OUT(v), gated = OUT(v * gate[pair][n]) from the UNROUNDED v, as bn_apply_kernel.
-#define MXT_ROWS 256
 #define MXT_TILE (MXT_ROWS * 128)
 // The order of the K loop's memory operations IS its schedule (loads of the next step, then per channel fragment two LDS reads and four
 // MFMAs, then the LDS writes of the next step); left alone, the compiler reads all eight B fragments first (64 registers more, which
@@ -464,58 +505,6 @@ __global__ __launch_bounds__(512) void conv0_mx8_tiled_kernel(const uint8_t* __r
         if (gated) gated[(long)m * ld_gated + n] = (OUT)(v * gp[n]);
       }
     }
-}
-
-// The argument checks of drn_conv0_mx8_bn and drn_conv0_mx8_bn_tile: one list for both entries, the messages under the caller's name.
-static int conv0_mx8_bn_check(const char* entry, const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos,
-                              int ld_pos, int n_rows, int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes,
-                              const uint8_t* wscales, const void* wpos, int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv,
-                              const int32_t* vids, int Vc, const float* gate, int ldg, const void* out, int ld_out, const void* gated,
-                              int ld_gated, int Q, int L, int C, int P, int Cout) {
-  DRN_CHECK_ARG(codes && scales && prop_off && wcodes && wscales && pq && pv && vids && out && (P == 0 || (pos && wpos)),
-                "%s: null pointer", entry);
-  DRN_CHECK_ARG((gate != nullptr) == (gated != nullptr), "%s: gate and gated must come together", entry);
-  DRN_CHECK_ARG(n_rows > 0 && pad_row >= 0 && pad_row < n_rows && Nv > 0 && S > 0 && Vc > 0 && Q > 0 && L > 0 && C > 0 && P >= 0 && Cout > 0,
-                "%s: bad args (n_rows %d, pad_row %d, Nv %d, S %d, Vc %d, Q %d, L %d, C %d, P %d, Cout %d)", entry, n_rows, pad_row, Nv,
-                S, Vc, Q, L, C, P, Cout);
-  DRN_CHECK_ARG(C % MX8_BLOCK == 0, "%s: C = %d is not a multiple of the block of %d columns", entry, C, MX8_BLOCK);
-  DRN_CHECK_ARG(P % 32 == 0, "%s: P = %d is not a multiple of the 32 columns of a position step", entry, P);
-  DRN_CHECK_ARG(Cout % 16 == 0, "%s: Cout = %d is not a multiple of 16", entry, Cout);
-  DRN_CHECK_ARG((long)Cout * C <= 0x7fffffffL && 3L * Cout * P <= 0x7fffffffL, "%s: a weight plane of %d x %d is beyond 2^31", entry,
-                Cout, C + P);
-  DRN_CHECK_ARG((long)Q * L <= 0x7fffffffL - MXT_ROWS && ((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256) <= 0x7fffffffL,
-                "%s: more than 2^31 rows", entry);
-  DRN_CHECK_ARG(ld_codes >= C && ld_scales >= C / MX8_BLOCK && (P == 0 || ld_pos >= P) && ld_out >= Cout && (!gated || (ld_gated >= Cout && ldg >= Cout)),
-                "%s: a row stride is shorter than its row", entry);
-  DRN_CHECK_ARG(ld_codes % 16 == 0 && (P == 0 || ld_pos % 8 == 0) &&
-                    ((((uintptr_t)codes) | ((uintptr_t)wcodes) | ((uintptr_t)(P ? pos : nullptr)) | ((uintptr_t)(P ? wpos : nullptr))) & 15) == 0,
-                "%s: codes / wcodes / pos / wpos and their row strides must be 16-byte multiples", entry);
-  if (pq_host)
-    for (int p = 0; p < Q; ++p)
-      DRN_CHECK_ARG(pq_host[p] >= 0 && pq_host[p] < S, "%s: pair %d reads sentence %d of %d", entry, p, (int)pq_host[p], S);
-  return DRN_OK;
-}
-
-extern "C" int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
-                                int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
-                                int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, const float* ss,
-                                const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q, int L, int C,
-                                int P, int Cout, void* stream) {
-  drn_clear_status();
-  if (const int rc = conv0_mx8_bn_check("drn_conv0_mx8_bn", codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes,
-                                        wscales, wpos, S, pq, pq_host, pv, vids, Vc, gate, ldg, out, ld_out, gated, ld_gated, Q, L, C, P, Cout))
-    return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)(((long)Q * L + MXT_ROWS - 1) / MXT_ROWS * cdiv(Cout, 256));
-  if (out_f32)
-    conv0_mx8_tiled_kernel<float><<<grid, 512, 0, st>>>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv,
-                                                        wcodes, wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (float*)out, ld_out,
-                                                        (float*)gated, ld_gated, Q, L, C, P, Cout);
-  else
-    conv0_mx8_tiled_kernel<bf16_t><<<grid, 512, 0, st>>>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off,
-                                                         Nv, wcodes, wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (bf16_t*)out,
-                                                         ld_out, (bf16_t*)gated, ld_gated, Q, L, C, P, Cout);
-  return drn_launch_status("drn_conv0_mx8_bn");
 }
 
 // ---------------------------------------------------------------- the same launch on narrow tiles, for grids that do not fill the chip
@@ -742,6 +731,44 @@ __global__ __launch_bounds__(MXN_THREADS, ROWS == 64 ? 3 : 2) void conv0_mx8_nar
     }
 }
 
+// A shipped tile's launch: its kernel, its thread count, its grid.
+template <typename OUT, int ROWS, int COLS>
+static void launch_conv0_mx8_tile(const Conv0Mx8Args& a, hipStream_t st) {
+  const unsigned grid = (unsigned)(((long)a.Q * a.L + ROWS - 1) / ROWS * cdiv(a.Cout, COLS));
+#define CONV0_MX8_BN_OPERANDS \
+  CONV0_MX8_OPERANDS, a.ss, a.gate, a.ldg, (OUT*)a.out, a.ld_out, (OUT*)a.gated, a.ld_gated, a.Q, a.L, a.C, a.P, a.Cout
+  if constexpr (ROWS == MXT_ROWS) conv0_mx8_tiled_kernel<OUT><<<grid, 512, 0, st>>>(CONV0_MX8_BN_OPERANDS);
+  else conv0_mx8_narrow_kernel<OUT, ROWS, COLS><<<grid, MXN_THREADS, 0, st>>>(CONV0_MX8_BN_OPERANDS);
+#undef CONV0_MX8_BN_OPERANDS
+}
+
+
+// Check, then launch a shipped tile (by its rows: 256 x 256, 128 x 64, 64 x 64), under the name of the entry that the caller is or
+// stands for.
+static int conv0_mx8_bn_run(const char* entry, const Conv0Mx8Args& a, const int32_t* pq_host, int out_f32, int tile_rows, void* stream) {
+  drn_clear_status();
+  if (const int rc = conv0_mx8_check(entry, a, pq_host, true)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (2 * tile_rows + (out_f32 ? 1 : 0)) {
+    case 2 * 256 + 1: launch_conv0_mx8_tile<float, 256, 256>(a, st); break;
+    case 2 * 256: launch_conv0_mx8_tile<bf16_t, 256, 256>(a, st); break;
+    case 2 * 128 + 1: launch_conv0_mx8_tile<float, 128, 64>(a, st); break;
+    case 2 * 128: launch_conv0_mx8_tile<bf16_t, 128, 64>(a, st); break;
+    case 2 * 64 + 1: launch_conv0_mx8_tile<float, 64, 64>(a, st); break;
+    case 2 * 64: launch_conv0_mx8_tile<bf16_t, 64, 64>(a, st); break;
+    default: DRN_CHECK_ARG(false, "%s: no tile of %d rows", entry, tile_rows);
+  }
+  return drn_launch_status(entry);
+}
+
+extern "C" int drn_conv0_mx8_bn(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos, int n_rows,
+                                int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales, const void* wpos,
+                                int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids, int Vc, const float* ss,
+                                const float* gate, int ldg, void* out, int ld_out, void* gated, int ld_gated, int out_f32, int Q, int L, int C,
+                                int P, int Cout, void* stream) {
+  return conv0_mx8_bn_run("drn_conv0_mx8_bn", CONV0_MX8_ARGS(ss, gate, ldg, out, ld_out, gated, ld_gated), pq_host, out_f32, 256, stream);
+}
+
 // The tile "choose" picks: a function of (Q L, Cout) and the device's CU count alone -- never of pq / pv / vids, so a captured launch
 // replays with other pairs.  W = the wide tile's workgroups, cdiv(Q L, 256) x cdiv(Cout, 256); a wide tile is 16 64 x 64 tiles or 8
 // 128 x 64 tiles at Cout = 256:
@@ -785,18 +812,6 @@ extern "C" int drn_conv0_mx8_bn_choose(int Q, int L, int Cout, int* rows, int* c
   return DRN_OK;
 }
 
-template <typename OUT, int ROWS, int COLS>
-static void launch_conv0_mx8_narrow(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const bf16_t* pos, int ld_pos,
-                                    int n_rows, int pad_row, const int* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales,
-                                    const bf16_t* wpos, int S, const int* pq, const int* pv, const int* vids, int Vc, const float* ss,
-                                    const float* gate, int ldg, OUT* out, int ld_out, OUT* gated, int ld_gated, int Q, int L, int C, int P,
-                                    int Cout, hipStream_t st) {
-  const unsigned grid = (unsigned)(((long)Q * L + ROWS - 1) / ROWS * cdiv(Cout, COLS));
-  conv0_mx8_narrow_kernel<OUT, ROWS, COLS><<<grid, MXN_THREADS, 0, st>>>(codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off,
-                                                                         Nv, wcodes, wscales, wpos, S, pq, pv, vids, Vc, ss, gate, ldg, out, ld_out,
-                                                                         gated, ld_gated, Q, L, C, P, Cout);
-}
-
 extern "C" int drn_conv0_mx8_bn_tile(const uint8_t* codes, int ld_codes, const uint8_t* scales, int ld_scales, const void* pos, int ld_pos,
                                      int n_rows, int pad_row, const int32_t* prop_off, int Nv, const uint8_t* wcodes, const uint8_t* wscales,
                                      const void* wpos, int S, const int32_t* pq, const int32_t* pq_host, const int32_t* pv, const int32_t* vids,
@@ -809,25 +824,7 @@ extern "C" int drn_conv0_mx8_bn_tile(const uint8_t* codes, int ld_codes, const u
                     ((long)Q * L + 63) / 64 * cdiv(Cout, 64) <= 0x7fffffffL,
                 "drn_conv0_mx8_bn_tile: bad args (Q %d, L %d, Cout %d), or more than 2^31 rows or workgroups", Q, L, Cout);
   if (choose) conv0_mx8_choose((long)Q * L, Cout, &tile_rows, &tile_cols);
-  if (tile_rows == 256)                                  // (the wide tile: the same entry, the same checks)
-    return drn_conv0_mx8_bn(codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, wscales, wpos, S, pq, pq_host,
-                            pv, vids, Vc, ss, gate, ldg, out, ld_out, gated, ld_gated, out_f32, Q, L, C, P, Cout, stream);
-  drn_clear_status();
-  if (const int rc = conv0_mx8_bn_check("drn_conv0_mx8_bn_tile", codes, ld_codes, scales, ld_scales, pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes,
-                                        wscales, wpos, S, pq, pq_host, pv, vids, Vc, gate, ldg, out, ld_out, gated, ld_gated, Q, L, C, P, Cout))
-    return rc;
-  hipStream_t st = (hipStream_t)stream;
-#define MXN_LAUNCH(OUT, ROWS, COLS)                                                                                                          \
-  launch_conv0_mx8_narrow<OUT, ROWS, COLS>(codes, ld_codes, scales, ld_scales, (const bf16_t*)pos, ld_pos, n_rows, pad_row, prop_off, Nv, wcodes, \
-                                           wscales, (const bf16_t*)wpos, S, pq, pv, vids, Vc, ss, gate, ldg, (OUT*)out, ld_out, (OUT*)gated,     \
-                                           ld_gated, Q, L, C, P, Cout, st)
-  if (tile_rows == 128) {
-    if (out_f32) MXN_LAUNCH(float, 128, 64);
-    else MXN_LAUNCH(bf16_t, 128, 64);
-  } else {
-    if (out_f32) MXN_LAUNCH(float, 64, 64);
-    else MXN_LAUNCH(bf16_t, 64, 64);
-  }
-#undef MXN_LAUNCH
-  return drn_launch_status("drn_conv0_mx8_bn_tile");
+  // (the wide tile: drn_conv0_mx8_bn's launch, under its name)
+  return conv0_mx8_bn_run(tile_rows == 256 ? "drn_conv0_mx8_bn" : "drn_conv0_mx8_bn_tile", CONV0_MX8_ARGS(ss, gate, ldg, out, ld_out, gated, ld_gated),
+                          pq_host, out_f32, tile_rows, stream);
 }

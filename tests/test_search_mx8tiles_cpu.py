@@ -1,6 +1,8 @@
 """drn_conv0_mx8_bn_tile, the host side: the resource notes of every conv0_mx8_narrow_kernel instantiation against the occupancy
 DESIGN.md section 3 claims for its tile, the refusal of a `tile` that is not shipped before the library is reached, the entries in the
-header and the chooser's constants in the source.  tests/test_search_mx8tiles_gpu.py holds the kernels and the search."""
+header, the chooser's constants in the source and the shape of the recorded digests.  tests/test_search_mx8tiles_gpu.py holds the
+kernels and the search."""
+import json
 import os
 import re
 import subprocess
@@ -45,6 +47,27 @@ def test_every_narrow_tile_fits_the_occupancy_it_claims(tmp_path):
             r = table[k]
             assert r["spill"] == 0 and r["scratch"] == 0 and r["vgpr"] + r["agpr"] <= regs, (k, r)
             assert 2 * (rows + cols) * 132 <= lds[k] and per_cu * lds[k] <= LDS_PER_CU, (k, lds[k])
+
+
+def test_the_recorded_digests_cover_the_five_geometries_in_both_modes_and_name_their_commit():
+    """tests/golden/search_mx8_tile_digests.json, which test_every_tile_writes_the_recorded_bits holds the device to: one record for
+    each of that file's GEOMETRIES (by the ids it gives them), each a sha256 of the operands, of the fp32 output and of the bf16 outputs,
+    all different, and the commit whose wide kernel wrote them."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "search_mx8_tile_digests.json")))
+    assert re.fullmatch(r"[0-9a-f]{40}", golden["commit"])
+    gpu = open(os.path.join(ROOT, "tests", "test_search_mx8tiles_gpu.py")).read()
+    ids = []
+    for L, Cout, Dp, P, order in ((12, 16, 64, 0, "sorted"), (70, 272, 160, 32, "interleaved"), (300, 80, 384, 32, "shuffled"),
+                                  (12, 80, 384, 0, "interleaved"), (70, 272, 64, 32, "shuffled")):
+        assert '(%d, %d, %d, %d, %s, "%s")' % (L, Cout, Dp, P, order.upper(), order) in gpu          # (a geometry of that file)
+        ids.append("L%d-Cout%d-Dp%d-P%d-%s" % (L, Cout, Dp, P, order))
+    assert gpu.count(', "sorted")') + gpu.count(', "interleaved")') + gpu.count(', "shuffled")') == len(ids)
+    assert sorted(golden["digests"]) == sorted(ids)
+    seen = set()
+    for rec in golden["digests"].values():
+        assert sorted(rec) == ["bf16", "fp32", "operands"] and all(re.fullmatch(r"[0-9a-f]{64}", v) for v in rec.values()), rec
+        seen.update(rec.values())
+    assert len(seen) == 3 * len(ids)
 
 
 def test_the_wrapper_refuses_a_tile_that_is_not_shipped_and_bad_arguments_under_auto(monkeypatch):

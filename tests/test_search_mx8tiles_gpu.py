@@ -1,8 +1,12 @@
-"""The narrow tiles of the fused FP8 conv0 (drn_conv0_mx8_bn_tile, conv0_mx8_narrow_kernel) on the device: every shipped tile writes
-bit for bit what the wide tile writes -- bare accumulators in fp32 and bf16 through BatchNorm, ReLU and the gate --, EQUALS the float64
+"""The narrow tiles of the fused FP8 conv0 (drn_conv0_mx8_bn_tile, conv0_mx8_narrow_kernel) on the device: every
+shipped tile writes bit for bit what the wide tile writes -- bare accumulators in fp32 and bf16 through BatchNorm, ReLU and the gate --,
+and what the wide tile wrote at the commit that tests/golden/search_mx8_tile_digests.json names, EQUALS the float64
 oracle on exact data, writes nothing outside its columns and does not depend on the order of the pairs; the chooser is a shipped tile, a
 function of the grid alone and the rule DESIGN.md states; and Grounder(conv0="mxfp8", fused=True), which now runs conv0 on the chosen
 tile, returns field for field the hits of the same search with the chooser held to the wide tile."""
+import hashlib
+import json
+import os
 import types
 
 import pytest
@@ -66,6 +70,41 @@ def test_a_narrow_tile_writes_the_wide_tiles_bits(tile, L, Cout, Dp, P, order):
     o, g, _ = run_bn(case, L, BF, ss=ss, gate=gate, tile=tile)
     assert torch.equal(o, wo) and torch.equal(g, wg), tile
     assert 0.05 < float((wo == 0).float().mean()) < 0.95 and not torch.equal(wo, wg)
+
+
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "search_mx8_tile_digests.json")
+
+
+def sha256_of(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.contiguous().cpu().view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+def tile_digests(L, Cout, Dp, P, order, tile):
+    """The operands and the two runs of test_a_narrow_tile_writes_the_wide_tiles_bits on `tile` -> sha256 of the operands, of out (fp32,
+    ss = None) and of out + gated (bf16 through ss and the gate).  Every operand value is drawn from a seeded generator on the host
+    (random_case, epilogue_of) and then moved; pq / pv are integer arithmetic and `permuted` is an indexing."""
+    case = permuted(case_of(Dp, P, Cout, 3 * Dp + P + Cout + L), order)
+    ss, gate = epilogue_of(Cout, L + Cout)
+    index, wcodes, wscales, wpos, pq, pv, vids = case
+    operands = [index.codes, index.scales, index.prop_off, wcodes, wscales, pq, pv, vids, ss, gate] + ([index.pos, wpos] if P else [])
+    out, gated, _ = run_bn(case, L, BF, ss=ss, gate=gate, tile=tile)
+    return {"operands": sha256_of(*operands), "fp32": sha256_of(run_bn(case, L, torch.float32, tile=tile)[0]), "bf16": sha256_of(out, gated)}
+
+
+@pytest.mark.parametrize("L,Cout,Dp,P,order", GEOMETRIES)
+def test_every_tile_writes_the_recorded_bits(request, L, Cout, Dp, P, order):
+    """tests/golden/search_mx8_tile_digests.json: what the wide tile wrote on an MI355X at the commit the file names.  The test
+    above compares the tiles with one another, so a summation order that moved in every tile together -- as it can once the kernels
+    share code -- would pass it; this one would not.  Both entries of the wide tile and every narrow tile, no tolerance."""
+    from drn_amd import ops
+    want = json.load(open(DIGESTS))["digests"][request.node.callspec.id]
+    for tile in (None,) + tuple(ops.CONV0_MX8_TILES):
+        got = tile_digests(L, Cout, Dp, P, order, tile)
+        assert got["operands"] == want["operands"], "the operands are not the recorded ones: the generators, not the kernel"
+        assert got == want, (tile, got, want)
 
 
 # -- 2. the oracle itself, the guards, the order of the pairs --------------------------------------------------------------------------------
