@@ -3,7 +3,8 @@ Regression Network for video grounding.  Host code is Python; all math runs in
 hand-written HIP kernels behind the C-ABI in include/drn_hip.h (libdrn_hip.so).
 """
 __version__ = "0.1.0"
-from .grounding import Grounder, Hits, Moments, group_by_video, search  # noqa: E402,F401
+from .grounding import Grounder, Hits, Moments, group_by_video, plan_candidate_steps, search  # noqa: E402,F401
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
 from .index import SearchIndex  # noqa: E402,F401
 from .search_eval import SearchRecall, evaluate_search, search_batches  # noqa: E402,F401
+from .retrieve import Shortlist, Shortlister, shortlist_reference  # noqa: E402,F401

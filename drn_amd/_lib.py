@@ -20,6 +20,9 @@ MAX_GROUPS = 4
 QD_MAX, QD_COUNTERS = 16, 2048
 LOSS_MAX_BUMPS = 32
 MERGE_MAX_CAND = 2048     # DRN_MERGE_MAX_CAND: K + Vc * kv candidates one drn_merge_moments wavefront stages in LDS
+SHORTLIST_MAX = 128       # DRN_SHORTLIST_MAX: the longest list drn_shortlist_topn returns (a choice, not a measurement)
+SHORTLIST_BLOCK = 256     # videos one workgroup of drn_shortlist_topn's first launch ranks (its workspace is sized by it)
+CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 
 
 class DrnError(RuntimeError):
@@ -171,6 +174,8 @@ SIGNATURES = {
     "drn_merge_moments_ragged": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_search_recall": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "drn_shortlist_topn": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 
 

@@ -12,14 +12,15 @@ each sentence's best moments across the chunks on the device (Hits).
 
 Grounder.search(candidates=) looks for each sentence only in that sentence's own list of videos: plan_pairs cuts the ragged list of
 (sentence, video) pairs into steps of equal shape, the same fronts and trunk run on a step's pairs, and drn_merge_moments_ragged ranks
-them.  Grounder.ground_stored is the one-video-per-sentence case without a ranking: ground() on videos that are already resident."""
+them.  With the candidates as a DEVICE tensor (drn_amd.retrieve.Shortlister's ids) nothing is read on the host: the steps come from
+the shapes alone (plan_candidate_steps) and one drn_plan_candidates launch fills in their videos.  Grounder.ground_stored is the one-video-per-sentence case without a ranking: ground() on videos that are already resident."""
 import collections
 
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import DrnError
+from ._lib import CANDIDATES_MAX, DrnError
 
 
 class Moments(object):
@@ -153,6 +154,79 @@ def _plan(key, S, pairs, slots, cap):
         plan.pair_q[c, :q.size], plan.pair_v[c, :q.size], plan.pair_video[c, :q.size] = q[order], slot.reshape(-1)[order], v[order]
         plan.pair_off[c, 1:] = np.cumsum(np.bincount(q, minlength=S))
     return plan
+
+
+CandidateSteps = collections.namedtuple("CandidateSteps", "Sc Nc pairs pair_q pair_v pair_off first")
+CandidateSteps.__doc__ = """The static half of a search over device candidates (plan_candidate_steps): Sc sentences x Nc columns per step,
+`pairs` pair slots per step, and int32 arrays with a leading step axis: pair_q (steps, pairs) the pair's sentence (0 for padding),
+pair_v (steps, pairs) = arange(pairs) (one video slot per pair), pair_off (steps, S + 1), first (steps, 1) = 1 for step 0 only."""
+
+
+def plan_candidate_steps(S, N, pairs=None, cap=None):
+    """The steps of a search over a (S, N) table of candidates as a function of the SHAPES alone -- nothing in it depends on the data, so
+    the table is never walked on the host -> CandidateSteps.  cap: the pairs of one sentence a ranking step holds,
+    (MERGE_MAX_CAND - top_k) // per_video (default: no limit).  pairs: pair slots per step, default min(SEARCH_PAIR_BUDGET, S * N).
+    Nc = min(N, cap, pairs) columns and Sc = min(S, pairs // Nc) sentences per step; steps run sentence block outer, column block
+    inner: step sb * ceil(N / Nc) + cb, and its pair i = sl * Nc + jl is sentence sb * Sc + sl, column cb * Nc + jl.  pair_off gives
+    sentence s of the step's block the pairs [(s - sb * Sc) * Nc, + Nc) and every other sentence an empty range; pairs at or past
+    pair_off[S] are padding (pair_q 0).  Which of a step's pairs name a video is the data's half: plan_candidates_reference /
+    ops.plan_candidates write -1 for the others, and the ranking skips those.  Pure numpy."""
+    S, N = int(S), int(N)
+    if S < 1 or N < 1:
+        raise DrnError("plan_candidate_steps: S and N must be at least 1 (got %d, %d)" % (S, N))
+    pairs = min(Grounder.SEARCH_PAIR_BUDGET, S * N) if pairs is None else int(pairs)
+    cap = N if cap is None else int(cap)
+    if pairs < 1 or cap < 1:
+        raise DrnError("plan_candidate_steps: pairs and cap must be at least 1 (got %d, %d)" % (pairs, cap))
+    Nc = min(N, cap, pairs)
+    Sc = min(S, pairs // Nc)
+    nsb, ncb = -(-S // Sc), -(-N // Nc)
+    steps = nsb * ncb
+    i = np.arange(pairs)
+    sb = np.repeat(np.arange(nsb), ncb)
+    sent = sb[:, None] * Sc + (i // Nc)[None, :]
+    pair_q = np.where((i[None, :] < Sc * Nc) & (sent < S), sent, 0).astype(np.int32)
+    held = np.clip(np.arange(S + 1)[None, :] - sb[:, None] * Sc, 0, np.minimum(Sc, S - sb * Sc)[:, None])
+    first = (np.arange(steps) == 0).astype(np.int32).reshape(steps, 1)
+    return CandidateSteps(Sc, Nc, pairs, pair_q, np.tile(i.astype(np.int32), (steps, 1)), (held * Nc).astype(np.int32), first)
+
+
+def plan_candidates_reference(C, num_videos, S, N, pairs=None, cap=None):
+    """THE DEFINITION of ops.plan_candidates' table, in numpy: C (S, N) integers -> pair_video (steps, pairs) int32 for the steps of
+    plan_candidate_steps(S, N, pairs, cap).  The pair of (sentence s, column j) gets C[s, j] when that is a position in
+    [0, num_videos) and no earlier column of row s holds the same position -- the WHOLE row, not only the step's columns -- and -1
+    otherwise; pairs of sentences or columns past S or N and pairs past Sc * Nc get -1."""
+    C = np.asarray(C).astype(np.int64).reshape(int(S), int(N))
+    plan = plan_candidate_steps(S, N, pairs, cap)
+    Sc, Nc = plan.Sc, plan.Nc
+    ncb = -(-int(N) // Nc)
+    table = np.full(plan.pair_q.shape, -1, dtype=np.int32)
+    for s in range(int(S)):
+        seen = set()
+        for j in range(int(N)):
+            v = int(C[s, j])
+            if 0 <= v < int(num_videos) and v not in seen:
+                seen.add(v)
+                table[(s // Sc) * ncb + j // Nc, (s % Sc) * Nc + j % Nc] = v
+    return table
+
+
+def check_device_candidates(C, S, store, chunk=None):
+    """The refusals of search(candidates= a device tensor) that depend on the tensor, the store and S, before any launch and without
+    reading the tensor: a SearchIndex, int32, (S, N) with 1 <= N <= CANDIDATES_MAX -- 1024, a CHOICE, not a measurement:
+    ops.plan_candidates holds one row in 4 KiB of LDS to drop its repeats."""
+    from .index import SearchIndex
+    if not isinstance(store, SearchIndex):
+        raise DrnError("Grounder.search: device candidates need a SearchIndex: on a FeatureStore every (sentence, video) pair would "
+                       "pool and project its own video -- build an index (SearchIndex.build) or pass host lists")
+    if chunk is not None:
+        raise DrnError("Grounder.search: chunk= does not apply to device candidates (every pair has a video slot of its own)")
+    if S < 1:
+        raise DrnError("Grounder.search: no sentences")
+    if C.dtype != torch.int32:
+        raise DrnError("Grounder.search: device candidates must be int32, not %s" % C.dtype)
+    if C.dim() != 2 or int(C.shape[0]) != S or not 1 <= int(C.shape[1]) <= CANDIDATES_MAX:
+        raise DrnError("Grounder.search: device candidates must be (%d, N) with 1 <= N <= %d, not %s" % (S, CANDIDATES_MAX, tuple(C.shape)))
 
 
 class _GroundGraph(object):
@@ -343,7 +417,17 @@ class Grounder(object):
         the largest count among all candidate videos.  All steps' arrays and first-chunk words go up in one copy; a step runs the same
         front on its pairs (pair_q, pair_v instead of p // Vc, p % Vc), select_moments and drn_merge_moments_ragged.  The Hits of
         candidates=[all videos] * S are those of the search without candidates.  graph=True: one more signature,
-        ("pairs", store, S, pairs, chunk, T, per_video, top_k): other lists that cut to the same shape replay the same graph."""
+        ("pairs", store, S, pairs, chunk, T, per_video, top_k): other lists that cut to the same shape replay the same graph.
+        candidates as a DEVICE tensor: a CUDA int32 tensor (S, N), 1 <= N <= CANDIDATES_MAX (1024, a choice), e.g.
+        drn_amd.Shortlister.shortlist(...).ids -- row s is sentence s's set of store positions, an entry < 0 or >= len(store) is no
+        candidate, a position repeated in a row counts once (the first occurrence).  The tensor is NEVER read on the host: the steps
+        are plan_candidate_steps(S, N, pairs, cap) -- shapes alone, one pinned upload -- one ops.plan_candidates launch per search
+        writes their pair_video rows, and each step runs the body above with one video slot per pair (chunk= does not apply).  Needs
+        a SearchIndex (plain or quantised; a FeatureStore raises before any launch: every pair would pool and project its own
+        video).  T defaults to index.T, because nothing can be read back to find a smaller one: pass T= when the shortlisted videos
+        are known to be short.  The Hits are those of the same rows passed as host lists at the same T.  graph=True: one more
+        signature, ("cands", store, S, N, pairs, T, per_video, top_k, conv0); the plan launch sits outside the captured body and the
+        step's row is copied into its static buffer on the device."""
         from ._lib import MERGE_MAX_CAND
         from .index import SearchIndex
         if candidates is not None and videos is not None:
@@ -360,6 +444,8 @@ class Grounder(object):
         if indexed:
             store.check(model, "Grounder.search")
         model.check_conv0(self.conv0, store, "Grounder.search")
+        if torch.is_tensor(candidates) and candidates.is_cuda:
+            return self._search_device_candidates(query_tokens, query_length, store, K, kv, candidates, chunk, pairs, T, resident.device)
         if candidates is not None:
             return self._search_pairs(query_tokens, query_length, store, K, kv, candidates, chunk, pairs, T, resident.device)
         ids = np.arange(len(store), dtype=np.int32) if videos is None else store.ids_of(videos).numpy()
@@ -523,6 +609,54 @@ class Grounder(object):
             self._conv0_weights(store, gates, out=ent.inputs[7 + ng:])
         for c in range(C):
             ent.inputs[0].copy_(rows[c])
+            ent.graph.replay()
+        return Hits(*[t.clone() for t in ent.out])
+
+    def _search_device_candidates(self, query_tokens, query_length, store, K, kv, C, chunk, pairs, T, dev):
+        """search(candidates= a device tensor) after the refusals every form shares.  C is never read on the host: the steps are
+        plan_candidate_steps' (shapes alone, ONE pinned upload), ONE ops.plan_candidates launch writes every step's pair_video row from
+        C, and each step is _search_pairs' body with vids = that row and one slot per pair."""
+        from ._lib import MERGE_MAX_CAND
+        S = int(query_tokens.shape[0])
+        check_device_candidates(C, S, store, chunk)
+        N = int(C.shape[1])
+        cap = (MERGE_MAX_CAND - K) // kv
+        if cap < 1:
+            raise DrnError("Grounder.search: top_k + per_video = %d exceeds the %d candidates one ranking step holds" % (K + kv, MERGE_MAX_CAND))
+        if pairs is not None and int(pairs) < 1:
+            raise DrnError("Grounder.search: pairs must be at least 1 (got %d)" % int(pairs))
+        plan = plan_candidate_steps(S, N, pairs, cap)
+        pairs, steps = plan.pairs, int(plan.pair_q.shape[0])
+        T = int(store.T) if T is None else int(T)
+        rows, split = self._upload_plan((plan.pair_q, plan.pair_v, plan.pair_off), plan.first, dev)
+        table = ops.plan_candidates(C.contiguous(), len(store), plan.Sc, plan.Nc, pairs, steps,
+                                    torch.empty((steps, pairs), dtype=torch.int32, device=dev))
+        gates = [g.contiguous() for g in self.model.encode_query(query_tokens, query_length)]
+        ng, mx = len(gates), self.conv0 is not None
+
+        def body(row, pvideo, seg, score, video, level, rank, n, *g):
+            pq, pv, poff, flag = split(row)
+            mom = self._pair_front(kv, store, T, pvideo, pq, pv, g[:ng], g[ng:])
+            return ops.merge_moments_ragged(mom, pvideo, poff, len(store), (seg, score, video, level, rank, n), flag)
+
+        ent = None
+        if self.graph:
+            sig = ("cands", store, S, N, pairs, T, kv, K, self.conv0)
+            ent, fresh = self._entry(sig, body, dev, lambda: [rows[0].clone(), table[0].clone()] + list(ops.merge_state(S, K, dev))
+                                     + [g.clone() for g in gates] + self._conv0_weights(store, gates))
+        if ent is None:
+            state = ops.merge_state(S, K, dev)
+            wq = tuple(self._conv0_weights(store, gates))
+            for c in range(steps):
+                body(rows[c], table[c], *(state + tuple(gates) + wq))
+            return Hits(*state)
+        for dst, src in zip(ent.inputs[8:], gates):
+            dst.copy_(src)
+        if mx and not fresh:
+            self._conv0_weights(store, gates, out=ent.inputs[8 + ng:])
+        for c in range(steps):
+            ent.inputs[0].copy_(rows[c])
+            ent.inputs[1].copy_(table[c])
             ent.graph.replay()
         return Hits(*[t.clone() for t in ent.out])
 

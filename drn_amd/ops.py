@@ -1488,6 +1488,53 @@ def search_recall(hits, gt_video, gt, ious):
     return out
 
 
+def shortlist_ws_keys(V, S, n):
+    """The 8-byte keys of workspace drn_shortlist_topn needs: S * ceil(V / SHORTLIST_BLOCK) * min(n, SHORTLIST_BLOCK)."""
+    return int(S) * (-(-int(V) // _lib.SHORTLIST_BLOCK)) * min(int(n), _lib.SHORTLIST_BLOCK)
+
+
+def shortlist_topn(emb, queries, n, ws, ids, scores, counts):
+    """Each sentence's best n rows of `emb` (V, E) by dot product with its row of `queries` (S, E), both contiguous and of one dtype
+    (float32 / bfloat16), into ids (S, n) int32, scores (S, n) float32 and counts (S,) int32, all written in place
+    (drn_shortlist_topn; drn_amd.retrieve.shortlist_reference is the definition: finite scores only, score descending then position
+    ascending, -1 / 0 past the list).  ws: an int64 tensor of at least shortlist_ws_keys(V, S, n) elements.  Two launches on the
+    current stream behind one entry (one tag, shortlist_topn); no host synchronisation."""
+    _need_gpu(emb, queries, ws, ids, scores, counts)
+    n = int(n)
+    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
+            or emb.shape[1] != queries.shape[1]:
+        raise _lib.DrnError("shortlist_topn: emb (V, E) and queries (S, E) must be contiguous and of one dtype and width")
+    V, E = (int(x) for x in emb.shape)
+    S = int(queries.shape[0])
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("shortlist_topn: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
+    for name, t, dt, shape in (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)),
+                               ("counts", counts, torch.int32, (S,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("shortlist_topn: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < shortlist_ws_keys(V, S, n):
+        raise _lib.DrnError("shortlist_topn: ws must be a contiguous int64 tensor of at least %d elements" % shortlist_ws_keys(V, S, n))
+    _timed("shortlist_topn", 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn(
+        _p(emb), _p(queries), V, E, S, n, dtype_code(emb), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts),
+        _stream()), "drn_shortlist_topn"))
+    return ids, scores, counts
+
+
+def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
+    """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
+    drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch
+    (tag plan_candidates); cand is not read on the host."""
+    _need_gpu(cand, table)
+    if cand.dim() != 2 or cand.dtype != torch.int32 or not cand.is_contiguous():
+        raise _lib.DrnError("plan_candidates: cand must be a contiguous (S, N) int32 tensor")
+    if table.dtype != torch.int32 or tuple(table.shape) != (int(steps), int(pairs)) or not table.is_contiguous():
+        raise _lib.DrnError("plan_candidates: table must be a contiguous (%d, %d) int32 tensor" % (int(steps), int(pairs)))
+    S, N = (int(x) for x in cand.shape)
+    _timed("plan_candidates", 0, lambda: check(lib().drn_plan_candidates(
+        _p(cand), S, N, int(num_videos), int(Sc), int(Nc), int(pairs), int(steps), _p(table), _stream()), "drn_plan_candidates"))
+    return table
+
+
 # ---------------------------------------------------------------------------------------------
 # query-encoder glue (drn_amd/csrc/qenc.hip)
 # ---------------------------------------------------------------------------------------------

@@ -49,7 +49,8 @@ def evaluate_search(grounder, batches, store, ious=(0.5, 0.7), topks=(1, 10, 100
     start and end as fractions of that video; tensors on the host or on the device (search_batches adapts a loader).  store: the
     FeatureStore or SearchIndex to search.  Every batch runs grounder.search(..., top_k=max(topks), per_video=per_video, **search_kw)
     -- search_kw: chunk, T, pairs, videos -- and one drn_search_recall launch on its Hits.  candidates: None, or a callable
-    (names, query_tokens, query_length) -> what search(candidates=) accepts, called once per batch (a retriever's shortlist).
+    (names, query_tokens, query_length) -> what search(candidates=) accepts, called once per batch (a retriever's shortlist; a device tensor such as
+    Shortlister.shortlist(...).ids goes through untouched, so the pass has no synchronise per batch).
     A batch's names are resolved against store.index on the host before anything of that batch is launched; the ground truth goes
     up through pinned non-blocking copies; the tables are concatenated and copied ONCE, after the last batch.  Works with
     Grounder(graph=True): search()'s graph is the body, the recall launch sits outside it.  -> SearchRecall; no batches: n = 0 and

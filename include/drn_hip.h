@@ -645,6 +645,27 @@ int drn_merge_moments_ragged(const float* seg, const float* score, const int32_t
  * sentence, no host synchronisation. */
 int drn_search_recall(const float* seg, const int32_t* video, const int32_t* n, const int32_t* gt_video, const void* gt, int gt_is_f64,
                       const double* ious /*device*/, int S, int K, int I, int32_t* first_hit, void* stream);
+/* The first stage of a two-stage search (drn_amd/csrc/retrieve.hip): each of S sentences' best n videos of an embedding table, by
+ * dot product.  emb [V][E] and queries [S][E], contiguous, both float32 or both bfloat16 (dtype), 16-byte aligned.
+ * score[s][v] = sum_e queries[s][e] * emb[v][e], accumulated in fp32 on MFMAs in ONE fixed order per score: its bits do not depend on
+ * V, S, n or how the grid cuts the table.  Sentence s lists the videos whose score is finite, ordered by score descending, then
+ * position ascending -- a total order -- cut to n: ids [S][n], scores [S][n], counts [S] = the list's length; past it ids = -1 and
+ * scores = 0.  1 <= n <= DRN_SHORTLIST_MAX (a choice, not a measurement: two lists of that many 8-byte keys are the 2 KiB one merging
+ * wavefront sorts in LDS).  ws: ws_keys >= S * ceil(V / 256) * min(n, 256) 8-byte keys of workspace, 8-byte aligned, written by the
+ * first of the two launches (each workgroup ranks 256 videos for 16 sentences) and read by the second (one wavefront per sentence
+ * merges its lists).  No atomics, no host synchronisation. */
+#define DRN_SHORTLIST_MAX 128
+int drn_shortlist_topn(const void* emb, const void* queries, int V, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids,
+                       float* scores, int32_t* counts, void* stream);
+/* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
+ * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
+ * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the
+ * pair_video rows drn_merge_moments_ragged reads: step sb * ceil(N / Nc) + cb holds the sentences [sb * Sc, + Sc) and the columns
+ * [cb * Nc, + Nc), its pair sl * Nc + jl is (sentence sb * Sc + sl, column cb * Nc + jl) and gets that entry's position, or -1 for no
+ * candidate, a sentence or column past S or N, or a pair at or past Sc * Nc.  1 <= Sc <= S, 1 <= Nc <= N, Sc * Nc <= pairs and
+ * steps == ceil(S / Sc) * ceil(N / Nc), refused otherwise.  Every element of the table is written; one launch, nothing read back. */
+#define DRN_CANDIDATES_MAX 1024
+int drn_plan_candidates(const int32_t* cand, int S, int N, int Nv, int Sc, int Nc, int pairs, int steps, int32_t* table, void* stream);
 
 /* ---- query-encoder glue (drn_amd/csrc/qenc.hip; model/language_module.py:17-63), all fp32 ----------------------
  * Word embedding lookup written time-major (L, B, E) and its dense gradient (row padding_idx stays zero). */

@@ -48,7 +48,17 @@
            pairs x T in {256, 32}, at the grids between them on either side of the rule's two crossovers (W = 16 ... 56 and 80 ... 255 wide
            workgroups) and at a T = 32 shortlist step of 8 sentences x 4 candidates (as planned and shuffled); searches by
            graph replay (S in {1, 8}, T in {256, 32}) with the chooser as shipped, with the chooser held to the wide tile, and on the
-           default Grounder(fused=True).  The chooser's rule rests on these numbers."""
+           default Grounder(fused=True).  The chooser's rule rests on these numbers.
+
+  --device-candidates   instead of the above -> profiles/search_device_candidates_bench.json, by the same protocol (64 videos x 120 x
+           4096, bf16, T in {256, 32}, S = 8, median [min, max] of 5 interleaved rounds): (a) a two-stage search -- Shortlister.shortlist
+           then Grounder.search(candidates=) -- with the shortlist's ids passed as the device tensor, beside the only way the parent of
+           this feature has: the same shortlist read back with .tolist() and passed as host lists to the same kind of Grounder (N in
+           {4, 16}, a plain and a quantised index, eager and by graph replay); (b) the shortlist launch alone (V = 64 and a synthetic
+           65,536 x 512 bf16 table, S in {1, 8, 64}, n in {16, 128}) beside torch.matmul + torch.topk on the same tensors and beside
+           the time to read the table once at the chip's bandwidth; (c) the plan launch alone at S * N = 32 and 512; the largest
+           error / tolerance ratio of tests/test_shortlist_gpu.py's random case.  Random embeddings: nothing here says anything about
+           recall."""
 import argparse
 import json
 import os
@@ -1008,6 +1018,166 @@ def main_mx_conv0_tiles(args):
     print("wrote", out)
 
 
+HBM_PEAK_BYTES_PER_S, HBM_COPY_BYTES_PER_S = 8.0e12, 6.29e12          # MI355X: the spec and what a float4 copy reaches
+
+
+def event_window(launch, rounds, window_s=0.2):
+    """Launch-inclusive us per call: back-to-back calls issued from Python on one stream, device events around each window."""
+    def run(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    run(5)
+    reps = max(10, min(2000, int(window_s / (run(10) * 1e-6))))
+    return [run(reps) for _ in range(rounds)], reps
+
+
+def spread(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts), "rounds": ts}
+
+
+def verdict(new, base):
+    """new against base, both lists of rounds: a difference inside the baseline's own max - min is NO DIFFERENCE."""
+    d = statistics.median(new) - statistics.median(base)
+    if abs(d) <= max(base) - min(base):
+        return "NO DIFFERENCE"
+    return "SLOWER" if d > 0 else "faster"
+
+
+def bench_two_stage(model, where, name, T, S, N, rounds, window_s=0.2):
+    """(a): shortlist + search with the ids as a device tensor beside the same shortlist read back and passed as host lists."""
+    from drn_amd import Grounder, Shortlister
+    tok, qlen = sentences(S, 7)
+    g = torch.Generator().manual_seed(N)
+    sl = Shortlister(torch.randn(NV, 512, generator=g).to("cuda:0", torch.bfloat16).contiguous(), names=where.names)
+    qe = torch.randn(S, 512, generator=g).to("cuda:0", torch.bfloat16).contiguous()
+    gr = {k: Grounder(model, top_k=10, graph=k.endswith("graph")) for k in ("host_eager", "device_eager", "host_graph", "device_graph")}
+
+    def host(grounder):
+        short = sl.shortlist(qe, N)
+        lists = [row[:k] for row, k in zip(short.ids.tolist(), short.n.tolist())]          # (the read-back: the search's only synchronise)
+        return grounder.search(tok, qlen, where, per_video=2, candidates=lists)
+
+    def device(grounder):
+        return grounder.search(tok, qlen, where, per_video=2, candidates=sl.shortlist(qe, N).ids)
+    variants = {k: (lambda k=k: (host if k.startswith("host") else device)(gr[k])) for k in gr}
+    hits = {k: fn() for k, fn in variants.items()}
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(getattr(hits[a], f), getattr(hits[b], f)) for f in STATE)
+    reps = {}
+    for k, fn in variants.items():
+        window(fn, 3)
+        reps[k] = max(5, int(window_s * 1e3 / window(fn, 5)))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(window(fn, reps[k]))
+    res = {"resident": name, "T": T, "index_T": int(where.T), "S": S, "videos": NV, "candidates_per_sentence": N, "pairs": S * N,
+           "top_k": 10, "per_video": 2, "rounds": rounds, "graph_captures": {k: gr[k].captures for k in gr if k.endswith("graph")},
+           "device_equals_host": {"eager": same("device_eager", "host_eager"), "graph": same("device_graph", "host_graph")},
+           "variants": {k: dict(spread(ts), unit="ms per shortlist + search", searches_per_window=reps[k]) for k, ts in times.items()}}
+    res["device_against_host"] = {m: {"ratio_of_medians": statistics.median(times["device_" + m]) / statistics.median(times["host_" + m]),
+                                      "verdict": verdict(times["device_" + m], times["host_" + m])} for m in ("eager", "graph")}
+    return res
+
+
+def bench_shortlist_launch(V, S, n, rounds):
+    """(b): drn_shortlist_topn alone beside torch.matmul + torch.topk on the same tensors (bf16 scores there, fp32 here) and beside the
+    time to read the table once."""
+    from drn_amd import Shortlist, Shortlister
+    g = torch.Generator(device="cuda:0").manual_seed(V + S)
+    emb = torch.randn(V, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    sl = Shortlister(emb)
+    out = Shortlist(*sl.shortlist(q, n))
+    k = min(n, V)
+    ours, reps = event_window(lambda: sl.shortlist(q, n, out=out), rounds)
+    theirs, _ = event_window(lambda: torch.topk(torch.matmul(q, emb.t()), k, dim=1), rounds)
+    table = emb.numel() * emb.element_size()
+    tiles, blocks, m = -(-S // 16), -(-V // 256), min(n, 256)
+    res = {"V": V, "E": 512, "S": S, "n": n, "dtype": "bf16", "launches_per_window": reps, "table_bytes": table,
+           "table_reads": tiles, "workspace_bytes_written_and_read": S * blocks * m * 8,
+           "shortlist_us": spread(ours), "matmul_topk_us": spread(theirs),
+           "table_once_us_at_8.0TB/s": table / HBM_PEAK_BYTES_PER_S * 1e6, "table_once_us_at_6.29TB/s": table / HBM_COPY_BYTES_PER_S * 1e6,
+           "shortlist_over_matmul_topk": statistics.median(ours) / statistics.median(theirs),
+           "shortlist_against_matmul_topk": verdict(ours, theirs),
+           "shortlist_over_table_floor_6.29TB/s": statistics.median(ours) / (tiles * table / HBM_COPY_BYTES_PER_S * 1e6),
+           "note": "launch-inclusive, both launches of the shortlist; the floor counts the table once per 16 sentences and nothing else"
+                   + ("; 64 KB: the table lives in cache, the floor is not an HBM time" if V <= 64 else "")}
+    del sl, emb
+    return res
+
+
+def bench_plan_launch(S, N, rounds):
+    """(c): drn_plan_candidates alone."""
+    from drn_amd import ops, plan_candidate_steps
+    C = torch.randint(-2, NV, (S, N), dtype=torch.int32, device="cuda:0")
+    plan = plan_candidate_steps(S, N, None, 1019)                      # cap of top_k = 10, per_video = 2
+    steps = plan.pair_q.shape[0]
+    table = torch.empty((steps, plan.pairs), dtype=torch.int32, device="cuda:0")
+    ts, reps = event_window(lambda: ops.plan_candidates(C, NV, plan.Sc, plan.Nc, plan.pairs, steps, table), rounds)
+    return {"S": S, "N": N, "pairs": plan.pairs, "steps": steps, "launches_per_window": reps, "plan_us": spread(ts)}
+
+
+def shortlist_tolerance_ratio():
+    """tests/test_shortlist_gpu.py's random case (E = 512, V = 300, S = 5, n = 16, bf16): the largest |returned score - float64 score|
+    over tol = E * 2^-23 * sum |q * emb|."""
+    from drn_amd import Shortlister
+    g = torch.Generator().manual_seed(4)
+    emb = torch.randn(300, 512, generator=g).to("cuda:0", torch.bfloat16).contiguous()
+    q = torch.randn(5, 512, generator=g).to("cuda:0", torch.bfloat16).contiguous()
+    got = Shortlister(emb).shortlist(q, 16)
+    ref = q.double() @ emb.double().t()
+    tol = 512 * 2.0 ** -23 * (q.double().abs() @ emb.double().abs().t())
+    ids = got.ids.long()
+    return float(((got.scores.double() - torch.gather(ref, 1, ids)).abs() / torch.gather(tol, 1, ids)).max())
+
+
+def main_device_candidates(args):
+    from bench_store import build_store
+    from drn_amd import SearchIndex
+    out = args.out or os.path.join(ROOT, "profiles", "search_device_candidates_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, indexes resident",
+           "store": {"videos": NV, "rows_per_video": 120, "dim": D, "dtype": "bf16"},
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "host clock around shortlist + search ending in a device synchronise; device events for the launch windows",
+                      "baseline": "the same shortlist read back with .tolist() and passed as host lists: the only way before device "
+                                  "candidates existed.  A difference inside the baseline's own max - min is NO DIFFERENCE",
+                      "what_this_does_not_say": "synthetic weights and random embeddings: nothing here says anything about recall"},
+           "tolerance_ratio": shortlist_tolerance_ratio(), "two_stage": [], "shortlist_launch": [], "plan_launch": []}
+    for V in (NV, 65536):
+        for S in (1, 8, 64):
+            for n in (16, 128):
+                res["shortlist_launch"].append(bench_shortlist_launch(V, S, n, args.rounds))
+                print(json.dumps({"shortlist_launch": res["shortlist_launch"][-1]}), flush=True)
+    torch.cuda.empty_cache()
+    for S, N in ((8, 4), (8, 64)):
+        res["plan_launch"].append(bench_plan_launch(S, N, args.rounds))
+        print(json.dumps({"plan_launch": res["plan_launch"][-1]}), flush=True)
+    json.dump(res, open(out, "w"), indent=1)
+    model = make_model()
+    for T in (256, 32):
+        store = build_store(T, torch.bfloat16, "cuda:0")
+        for name, kw in (("index", {}), ("index_mxfp8", {"quantize": "mxfp8"})):
+            index = SearchIndex.build(model, store, **kw)
+            for N in (4, 16):
+                res["two_stage"].append(bench_two_stage(model, index, name, T, 8, N, args.rounds))
+                print(json.dumps({"two_stage": res["two_stage"][-1]}), flush=True)
+                json.dump(res, open(out, "w"), indent=1)
+            del index
+        del store
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -1021,9 +1191,13 @@ def main():
                                                                   "the default fused path on one quantised index")
     ap.add_argument("--mx-conv0-tiles", action="store_true", help="measure the narrow tiles of the fused FP8 conv0 and the chooser beside the "
                                                                   "wide tile and the default fused path on one quantised index")
+    ap.add_argument("--device-candidates", action="store_true", help="measure Shortlister.shortlist + Grounder.search(candidates= a device "
+                                                                     "tensor) beside the shortlist read back as host lists")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.device_candidates:
+        return main_device_candidates(args)
     if args.shortlist:
         return main_shortlist(args)
     if args.evaluate:
