@@ -22,6 +22,7 @@ LOSS_MAX_BUMPS = 32
 MERGE_MAX_CAND = 2048     # DRN_MERGE_MAX_CAND: K + Vc * kv candidates one drn_merge_moments wavefront stages in LDS
 SHORTLIST_MAX = 128       # DRN_SHORTLIST_MAX: the longest list drn_shortlist_topn returns (a choice, not a measurement)
 SHORTLIST_BLOCK = 256     # videos one workgroup of drn_shortlist_topn's first launch ranks (its workspace is sized by it)
+SHORTLIST_SEG_BLOCK = 256  # videos of one block of drn_shortlist_segments_topn's plan at most, and rows of one pass (SG_BLOCK)
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 
 
@@ -175,6 +176,8 @@ SIGNATURES = {
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_search_recall": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "drn_shortlist_topn": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_segments_topn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

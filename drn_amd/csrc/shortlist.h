@@ -1,0 +1,72 @@
+// What the two shortlist translation units share (retrieve.hip: one vector per video; retrieve_seg.hip: a ragged run of segment vectors
+// per video): the 64-bit candidate key, the bitonic sort, the fragment loaders and the MFMA step of one (sentence, row) score, and the
+// host-side launch of the merging kernel, which lives in retrieve.hip and serves both.
+#pragma once
+#include "common.h"
+
+typedef unsigned long long sl_key_t;
+
+// the score as an unsigned word that orders as the float does (-0 folded into +0); a finite score's word is never 0
+__device__ __forceinline__ unsigned sl_word(float score) {
+  const unsigned b = __float_as_uint(score + 0.f);                              // (-0 + 0 = +0)
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ sl_key_t sl_key(float score, int v) {
+  if (!isfinite(score)) return 0ull;
+  return ((sl_key_t)sl_word(score) << 32) | (sl_key_t)(~(unsigned)v);
+}
+__device__ __forceinline__ float sl_score(sl_key_t k) {
+  const unsigned o = (unsigned)(k >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+__device__ __forceinline__ int sl_video(sl_key_t k) { return (int)~(unsigned)k; }
+
+// Bitonic sort, descending, of ROWS rows of LEN keys each by NT threads (LEN a power of two).
+template <int LEN, int NT>
+__device__ __forceinline__ void sl_sort_desc(sl_key_t* keys, const int rows, const int tid) {
+  const int total = rows * (LEN / 2);
+  for (int k = 2; k <= LEN; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = tid; p < total; p += NT) {
+        const int row = p / (LEN / 2), t = p - row * (LEN / 2);
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        sl_key_t* r = keys + row * LEN;
+        const sl_key_t a = r[i], b = r[l];
+        const bool desc = (i & k) == 0;
+        if (desc ? a < b : a > b) { r[i] = b; r[l] = a; }
+      }
+      __syncthreads();
+    }
+}
+
+// 8 bf16 / 4 fp32 of `row` from column c0: one 16-byte load, or (the tail, a row that is not 16-byte aligned) element by element
+// with zeros past E
+__device__ __forceinline__ bf16x8 sl_frag(const bf16_t* row, const int c0) { return *reinterpret_cast<const bf16x8*>(row + c0); }
+__device__ __forceinline__ f32x4 sl_frag(const float* row, const int c0) { return *reinterpret_cast<const f32x4*>(row + c0); }
+__device__ __forceinline__ bf16x8 sl_frag_tail(const bf16_t* row, const int c0, const int E) {
+  bf16x8 f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = c0 + j < E ? row[c0 + j] : (bf16_t)0.f;
+  return f;
+}
+__device__ __forceinline__ f32x4 sl_frag_tail(const float* row, const int c0, const int E) {
+  f32x4 f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) f[j] = c0 + j < E ? row[c0 + j] : 0.f;
+  return f;
+}
+__device__ __forceinline__ f32x4 sl_mfma(const bf16x8 a, const bf16x8 b, f32x4 acc) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 sl_mfma(const f32x4 a, const f32x4 b, f32x4 acc) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
+  return acc;
+}
+template <typename T> struct SlStep;
+template <> struct SlStep<bf16_t> { static constexpr int COLS = 32, PER_LANE = 8; };
+template <> struct SlStep<float> { static constexpr int COLS = 16, PER_LANE = 4; };
+
+// shortlist_merge_kernel (retrieve.hip) on `stream`: sentence s merges its nblocks sorted lists of m keys, ws[s][block][0..m), into
+// ids, scores [S][n] and counts [S].  Not part of the C ABI.
+void sl_launch_merge(const sl_key_t* ws, int S, int n, int m, int nblocks, int32_t* ids, float* scores, int32_t* counts, hipStream_t stream);

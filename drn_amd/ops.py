@@ -1520,6 +1520,46 @@ def shortlist_topn(emb, queries, n, ws, ids, scores, counts):
     return ids, scores, counts
 
 
+def shortlist_segments_ws_keys(nblocks, S, n):
+    """The 8-byte keys of workspace drn_shortlist_segments_topn needs: K + ceil(K / 2), K = S * nblocks * min(n, SHORTLIST_SEG_BLOCK)."""
+    K = int(S) * int(nblocks) * min(int(n), _lib.SHORTLIST_SEG_BLOCK)
+    return K + (K + 1) // 2
+
+
+def shortlist_segments_topn(emb, queries, offsets, blk_vid, vid_blk, n, ws, ids, scores, counts, rows):
+    """Each sentence's best n videos of a RAGGED table by their best row: emb (R, E) and queries (S, E), contiguous and of one dtype
+    (float32 / bfloat16); offsets (V + 1,), blk_vid (nblocks + 1,) and vid_blk (V,) int32 on the device (the rows of each video and the
+    block plan, drn_amd.retrieve.plan_segment_blocks) -> ids, scores (S, n), counts (S,) and rows (S, n) int32, all written in place
+    (drn_shortlist_segments_topn; drn_amd.retrieve.segment_shortlist_reference is the definition).  ws: an int64 tensor of at least
+    shortlist_segments_ws_keys(nblocks, S, n) elements.  Three launches on the current stream behind one entry (one tag,
+    shortlist_segments_topn); the tables are not read on the host and nothing is synchronised."""
+    _need_gpu(emb, queries, offsets, blk_vid, vid_blk, ws, ids, scores, counts, rows)
+    n = int(n)
+    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
+            or emb.shape[1] != queries.shape[1]:
+        raise _lib.DrnError("shortlist_segments_topn: emb (R, E) and queries (S, E) must be contiguous and of one dtype and width")
+    R, E = (int(x) for x in emb.shape)
+    S = int(queries.shape[0])
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("shortlist_segments_topn: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
+    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
+        raise _lib.DrnError("shortlist_segments_topn: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1")
+    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
+    for name, t, dt, shape in (("offsets", offsets, torch.int32, (V + 1,)), ("blk_vid", blk_vid, torch.int32, (nblocks + 1,)),
+                               ("vid_blk", vid_blk, torch.int32, (V,)), ("ids", ids, torch.int32, (S, n)),
+                               ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)),
+                               ("rows", rows, torch.int32, (S, n))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("shortlist_segments_topn: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    need = shortlist_segments_ws_keys(nblocks, S, n)
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < need:
+        raise _lib.DrnError("shortlist_segments_topn: ws must be a contiguous int64 tensor of at least %d elements" % need)
+    _timed("shortlist_segments_topn", 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn(
+        _p(emb), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), R, V, nblocks, E, S, n, dtype_code(emb), _p(ws),
+        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn"))
+    return ids, scores, counts, rows
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -5,13 +5,19 @@ queries come from any dual encoder.  What it supplies is the ranking -- under a 
 ascending), so that equal scores fall the same way in every run and every build, which torch.topk does not promise -- and a result
 that never leaves the device: Shortlist.ids is what Grounder.search(candidates=) takes as a device tensor.
 
-shortlist_reference is the definition, in plain torch; Shortlister.shortlist is drn_shortlist_topn (csrc/retrieve.hip)."""
+shortlist_reference is the definition, in plain torch; Shortlister.shortlist is drn_shortlist_topn (csrc/retrieve.hip).
+
+A dual encoder hands out one embedding per clip, shot or window rather than one per video.  Shortlister(offsets=) takes such a RAGGED
+table -- R segment rows, video v owning the rows offsets[v] .. offsets[v + 1] - 1, the FeatureStore's seg_off layout -- scores a video
+by its BEST segment and lists distinct videos, with the winning segment beside each: segment_shortlist_reference is that definition,
+drn_shortlist_segments_topn (csrc/retrieve_seg.hip) the launch, plan_segment_blocks its host-side block plan."""
 import collections
 
+import numpy as np
 import torch
 
 from . import ops
-from ._lib import SHORTLIST_MAX, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from ._lib import SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
 Shortlist.__doc__ = """ids (S, n) int32 store positions, best first, -1 past the list; scores (S, n) float32, 0 past the list; n (S,) int32 the
@@ -40,12 +46,121 @@ def shortlist_reference(embeddings, queries, n):
     return Shortlist(ids, scores, count.to(torch.int32))
 
 
-class Shortlister(object):
-    """Shortlister(embeddings, names=None): a (V, E) table of video embeddings, row v belonging to store position v -- a contiguous
-    CUDA tensor, bfloat16 or float32, V >= 1 and E >= 1, kept by reference.  Non-finite embeddings are refused here (ONE
-    synchronise, once).  names: kept when given; check(store) raises unless they are the store's, before any launch."""
+SegmentShortlist = collections.namedtuple("SegmentShortlist", "ids scores n rows")
+SegmentShortlist.__doc__ = """ids, scores, n as in Shortlist (a video's score is its best segment's); rows (S, n) int32: the lowest segment number of
+the video (table row - offsets[video]) that reaches that score, -1 past the list.  All on the device."""
 
-    def __init__(self, embeddings, names=None):
+SegmentPlan = collections.namedtuple("SegmentPlan", "blk_vid vid_blk")
+SegmentPlan.__doc__ = """blk_vid (nblocks + 1,) int32: block b holds the videos blk_vid[b] .. blk_vid[b + 1] - 1; vid_blk (V,) int32: a video's block.
+numpy arrays."""
+
+SEGMENT_ROW_TARGET = 256  # rows a block of the plan aims at: a CHOICE (one pass of the ranking workgroup), not a measurement
+
+
+def check_segment_offsets(offsets, R, names=None):
+    """offsets (a sequence, a numpy array or a HOST tensor) for a table of R rows -> an int64 numpy array of V + 1 entries; raises
+    unless they are integers, start at 0, never decrease, end at R, V >= 1 and 1 <= R < 2^31, and names (when given) has V entries."""
+    R = int(R)
+    if torch.is_tensor(offsets):
+        if offsets.is_floating_point() or offsets.is_complex() or offsets.dtype == torch.bool:
+            raise DrnError("Shortlister: the offsets must be integers, not %s" % offsets.dtype)
+        offsets = offsets.detach().cpu().numpy()
+    try:
+        off = np.asarray(offsets)
+    except Exception:
+        raise DrnError("Shortlister: the offsets must be a sequence of V + 1 integers")
+    if off.dtype.kind not in "iu":
+        raise DrnError("Shortlister: the offsets must be integers, not %s" % off.dtype)
+    if off.ndim != 1 or off.shape[0] < 2:
+        raise DrnError("Shortlister: the offsets must be V + 1 integers with V >= 1, not %s" % (tuple(off.shape),))
+    if not 1 <= R < 2 ** 31:
+        raise DrnError("Shortlister: R = %d rows outside [1, 2^31)" % R)
+    off = off.astype(np.int64)
+    if int(off[0]) != 0 or int(off[-1]) != R:
+        raise DrnError("Shortlister: the offsets must start at 0 and end at R = %d, not run from %d to %d" % (R, int(off[0]), int(off[-1])))
+    if bool((np.diff(off) < 0).any()):
+        raise DrnError("Shortlister: the offsets decrease at video %d" % int(np.argmax(np.diff(off) < 0)))
+    if names is not None and len(names) != off.shape[0] - 1:
+        raise DrnError("Shortlister: %d names for %d videos (the offsets have V + 1 entries)" % (len(names), off.shape[0] - 1))
+    return off
+
+
+def plan_segment_blocks(offsets, max_videos=SHORTLIST_SEG_BLOCK, row_target=SEGMENT_ROW_TARGET):
+    """The block plan of a segmented shortlist, from host offsets (V + 1 non-decreasing integers) -> SegmentPlan.  The videos are walked
+    in order; a block is closed when the next video would bring it over max_videos videos or over row_target rows, and a single video
+    larger than row_target is a block of its own.  Every video lies whole inside exactly one block, so the merge never sees a video
+    twice; max_videos may not exceed what one ranking workgroup sorts (SHORTLIST_SEG_BLOCK)."""
+    if not 1 <= int(max_videos) <= SHORTLIST_SEG_BLOCK or int(row_target) < 1:
+        raise DrnError("plan_segment_blocks: max_videos = %d outside [1, %d] or row_target = %d below 1"
+                       % (int(max_videos), SHORTLIST_SEG_BLOCK, int(row_target)))
+    lens = np.diff(np.asarray(offsets, dtype=np.int64)).tolist()
+    starts, videos, rows = [0], 0, 0
+    for v, length in enumerate(lens):
+        if videos and (videos + 1 > max_videos or rows + length > row_target):
+            starts.append(v)
+            videos = rows = 0
+        videos, rows = videos + 1, rows + length
+    starts.append(len(lens))
+    blk_vid = np.asarray(starts, dtype=np.int32)
+    vid_blk = np.repeat(np.arange(len(starts) - 1, dtype=np.int32), np.diff(blk_vid))
+    return SegmentPlan(blk_vid, vid_blk)
+
+
+def segment_shortlist_reference(embeddings, offsets, queries, n):
+    """THE DEFINITION of a segmented shortlist, in float64 (usable on the CPU).  embeddings (R, E), queries (S, E); offsets: V + 1
+    non-decreasing integers from 0 to R, video v owning the rows offsets[v] .. offsets[v + 1] - 1, row r being segment r - offsets[v]
+    of its video.  score[s, v] = the maximum over v's rows of sum_e queries[s, e] * embeddings[r, e] (a NaN among them makes it NaN);
+    rows[s, v] = the lowest segment number that reaches it.  Sentence s lists the videos that own a row and whose score is finite,
+    ordered by higher score, then lower position, cut to n.  Past the list ids = -1, scores = 0 and rows = -1; n[s] is its length (a NaN
+    query row lists nothing).  -> SegmentShortlist on the inputs' device, scores rounded to float32."""
+    n = int(n)
+    emb, q = embeddings.double(), queries.double()
+    dev = emb.device
+    R, S = int(emb.shape[0]), int(q.shape[0])
+    off = torch.as_tensor(check_segment_offsets(offsets, R), device=dev)
+    V = int(off.shape[0]) - 1
+    lens = off[1:] - off[:-1]
+    video = torch.repeat_interleave(torch.arange(V, device=dev), lens)             # (R,) the video of a row
+    segment = torch.arange(R, device=dev) - off[video]
+    index = video[None, :].expand(S, R)
+    dot = q @ emb.t()                                                               # (S, R)
+    nan = torch.isnan(dot)
+    clean = torch.where(nan, torch.full_like(dot, float("-inf")), dot)
+    score = torch.full((S, V), float("-inf"), dtype=torch.float64, device=dev).scatter_reduce(1, index, clean, "amax", include_self=True)
+    any_nan = torch.zeros((S, V), dtype=torch.float64, device=dev).scatter_add(1, index, nan.double()) > 0
+    score = torch.where(any_nan, torch.full_like(score, float("nan")), score)
+    reaches = clean == torch.gather(score, 1, index)
+    rows = torch.full((S, V), R, dtype=torch.int64, device=dev).scatter_reduce(
+        1, index, torch.where(reaches, segment[None, :].expand(S, R), torch.full_like(index, R)), "amin", include_self=True)
+    finite = torch.isfinite(score) & (lens > 0)[None, :]
+    key = torch.where(finite, score, torch.full_like(score, float("-inf")))
+    # a stable sort by descending score keeps equal scores in position order
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    count = finite.sum(dim=1).clamp(max=n)
+    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    scores = torch.zeros((S, n), dtype=torch.float32, device=dev)
+    segs = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    m = min(n, V)
+    listed = torch.arange(m, device=dev)[None, :] < count[:, None]
+    ids[:, :m] = torch.where(listed, order[:, :m].to(torch.int32), ids[:, :m])
+    scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
+    segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order[:, :m]).to(torch.int32), segs[:, :m])
+    return SegmentShortlist(ids, scores, count.to(torch.int32), segs)
+
+
+class Shortlister(object):
+    """Shortlister(embeddings, names=None, offsets=None): a (V, E) table of video embeddings, row v belonging to store position v -- a
+    contiguous CUDA tensor, bfloat16 or float32, V >= 1 and E >= 1, kept by reference.  Non-finite embeddings are refused here (ONE
+    synchronise, once).  names: kept when given; check(store) raises unless they are the store's, before any launch.
+
+    offsets (a sequence, a numpy array or a tensor on any device) makes the table RAGGED: (R, E) segment embeddings, video v -- store
+    position v -- owning the rows offsets[v] .. offsets[v + 1] - 1, V + 1 non-decreasing integers from 0 to R with V >= 1 and
+    1 <= R < 2^31 (a video may own no row: it is never listed).  They are checked on the host here, in the same one synchronise as the
+    embeddings, and the block plan (plan_segment_blocks) is made and put on the device once.  len() is V and names has V entries;
+    shortlist() scores a video by its best segment and returns a SegmentShortlist.  Beside a FeatureStore, whose windows are such
+    runs, the intended use is Shortlister(window_embeddings, names=store.names, offsets=store.seg_off)."""
+
+    def __init__(self, embeddings, names=None, offsets=None):
         if not torch.is_tensor(embeddings) or not embeddings.is_cuda:
             raise DrnError("Shortlister: the embeddings must be a tensor on the GPU; there is no CPU fallback")
         if embeddings.dtype not in (torch.bfloat16, torch.float32):
@@ -54,15 +169,41 @@ class Shortlister(object):
             raise DrnError("Shortlister: the embeddings must be a contiguous (V, E) tensor with V >= 1 and E >= 1, not %s"
                            % (tuple(embeddings.shape),))
         self.names = None if names is None else list(names)
-        if self.names is not None and len(self.names) != int(embeddings.shape[0]):
-            raise DrnError("Shortlister: %d names for %d embeddings" % (len(self.names), int(embeddings.shape[0])))
-        if not bool(torch.isfinite(embeddings).all()):
-            raise DrnError("Shortlister: the embeddings hold values that are not finite")
+        self._seg = None
+        if offsets is not None:
+            self._init_segments(embeddings, offsets)
+        else:
+            if self.names is not None and len(self.names) != int(embeddings.shape[0]):
+                raise DrnError("Shortlister: %d names for %d embeddings" % (len(self.names), int(embeddings.shape[0])))
+            if not bool(torch.isfinite(embeddings).all()):
+                raise DrnError("Shortlister: the embeddings hold values that are not finite")
         self.embeddings = embeddings
         self._ws = {}
 
+    def _init_segments(self, embeddings, offsets):
+        """The ragged table's checks and its device tables.  Offsets that live on the device come to the host in the one transfer
+        that brings the embeddings' finiteness."""
+        dev, R = embeddings.device, int(embeddings.shape[0])
+        finite = torch.isfinite(embeddings).all()
+        if torch.is_tensor(offsets) and offsets.is_cuda:
+            if offsets.is_floating_point() or offsets.is_complex() or offsets.dtype == torch.bool:
+                raise DrnError("Shortlister: the offsets must be integers, not %s" % offsets.dtype)
+            if offsets.dim() != 1:
+                raise DrnError("Shortlister: the offsets must be V + 1 integers with V >= 1, not %s" % (tuple(offsets.shape),))
+            both = torch.cat([offsets.to(device=dev, dtype=torch.int64), finite.to(torch.int64).reshape(1)]).cpu()
+            offsets, finite = both[:-1], bool(both[-1])
+        off = check_segment_offsets(offsets, R, self.names)
+        if not bool(finite):
+            raise DrnError("Shortlister: the embeddings hold values that are not finite")
+        plan = plan_segment_blocks(off)
+        put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        self.plan = plan
+        self._seg = (put(off), put(plan.blk_vid), put(plan.vid_blk))
+        self.offsets = self._seg[0]
+
     def __len__(self):
-        return int(self.embeddings.shape[0])
+        seg = getattr(self, "_seg", None)
+        return int(self.embeddings.shape[0]) if seg is None else int(seg[0].shape[0]) - 1
 
     def check(self, store):
         """Raises unless this table's names are the store's (a FeatureStore or a SearchIndex), position by position."""
@@ -85,7 +226,15 @@ class Shortlister(object):
             raise DrnError("Shortlister.shortlist: the queries must be on the GPU; there is no CPU fallback")
         S = int(queries.shape[0])
         if out is not None:
-            for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
+            if getattr(self, "_seg", None) is None:
+                fields, dtypes, shapes = Shortlist._fields, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))
+            else:
+                fields, dtypes = SegmentShortlist._fields, (torch.int32, torch.float32, torch.int32, torch.int32)
+                shapes = ((S, n), (S, n), (S,), (S, n))
+                if len(out) != 4:
+                    raise DrnError("Shortlister.shortlist: out must hold the four buffers of a SegmentShortlist (ids, scores, n, rows), "
+                                   "not %d" % len(out))
+            for name, t, dt, shape in zip(fields, out, dtypes, shapes):
                 if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
                     raise DrnError("Shortlister.shortlist: out.%s must be a contiguous %s %s tensor on the GPU" % (name, shape, dt))
         return S, n
@@ -95,13 +244,26 @@ class Shortlister(object):
         on the device.  out: a Shortlist (or 3-tuple) of buffers written in place, every element, and returned.  Runs on the current
         stream without a host synchronisation and can be captured in a graph (the workspace is kept per (S, n): warm the shape once
         before capturing).  Scores are accumulated in fp32 in an order that is fixed per (sentence, video): the same bits whatever
-        V, S or n."""
+        V, S or n.
+
+        On a ragged table (offsets=) -> SegmentShortlist (segment_shortlist_reference defines it): distinct videos by their best
+        segment, with the winning segment in rows; out takes the four buffers.  A row's score has the same bits whatever the offsets,
+        and with one row per video the scores are the plain table's."""
         S, n = self._check(queries, n, out)
         dev = self.embeddings.device
+        seg = getattr(self, "_seg", None)
         if out is None:
             out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
                    torch.empty((S,), dtype=torch.int32, device=dev))
+            if seg is not None:
+                out += (torch.empty((S, n), dtype=torch.int32, device=dev),)
         ws = self._ws.get((S, n))
+        if seg is not None:
+            if ws is None:
+                keys = ops.shortlist_segments_ws_keys(int(seg[1].shape[0]) - 1, S, n)
+                ws = self._ws[(S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
+            ops.shortlist_segments_topn(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
+            return SegmentShortlist(*out)
         if ws is None:
             ws = self._ws[(S, n)] = torch.empty(ops.shortlist_ws_keys(len(self), S, n), dtype=torch.int64, device=dev)
         ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)

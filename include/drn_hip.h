@@ -657,6 +657,20 @@ int drn_search_recall(const float* seg, const int32_t* video, const int32_t* n, 
 #define DRN_SHORTLIST_MAX 128
 int drn_shortlist_topn(const void* emb, const void* queries, int V, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids,
                        float* scores, int32_t* counts, void* stream);
+/* The shortlist over a RAGGED table (drn_amd/csrc/retrieve_seg.hip): emb [R][E] holds segment embeddings, video v owns the rows
+ * offsets[v] .. offsets[v + 1] - 1 (offsets [V + 1] int32 on the device, non-decreasing from 0 to R; a video may own no row).
+ * score[s][v] = the maximum over v's rows of drn_shortlist_topn's score of that row -- the same MFMA chain per (sentence, row), so a
+ * row's bits depend on the row and the query alone, and with one row per video the scores are drn_shortlist_topn's.  Sentence s lists
+ * the videos that own a row and whose score is finite, under the same total order, cut to n; rows [S][n] = the lowest segment number
+ * (row - offsets[v]) that reaches the video's score, -1 past the list.  blk_vid [nblocks + 1] and vid_blk [V], int32 on the device,
+ * are the caller's block plan: block b holds the videos blk_vid[b] .. blk_vid[b + 1] - 1, at most 256, blk_vid[0] = 0 and
+ * blk_vid[nblocks] = V, and vid_blk[v] is v's block.  The three tables are NOT read on the host; every index taken from them is
+ * clamped, so a bad table gives a wrong list and no access outside the buffers.  ws: ws_keys >= K + ceil(K / 2) 8-byte keys, K = S *
+ * nblocks * min(n, 256) (each block's lists, then their winning segments as int32).  Three launches (rank the blocks, the merge of
+ * drn_shortlist_topn, look the segments up); no atomics, no host synchronisation. */
+int drn_shortlist_segments_topn(const void* emb, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
+                                const int32_t* vid_blk, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys,
+                                int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

@@ -58,7 +58,16 @@
            65,536 x 512 bf16 table, S in {1, 8, 64}, n in {16, 128}) beside torch.matmul + torch.topk on the same tensors and beside
            the time to read the table once at the chip's bandwidth; (c) the plan launch alone at S * N = 32 and 512; the largest
            error / tolerance ratio of tests/test_shortlist_gpu.py's random case.  Random embeddings: nothing here says anything about
-           recall."""
+           recall.
+
+  --segment-shortlist   instead of the above -> profiles/search_segment_shortlist_bench.json: Shortlister(offsets=).shortlist alone
+           (drn_shortlist_segments_topn, all three launches) on R = 65,536 rows x 512 in bf16 laid out as 65,536 videos x 1 row, 4,096 x
+           16 and 546 x 120 (the last video takes 136 rows, to make R), S in {1, 8, 64}, n in {16, 128}, launch-inclusive us, median
+           [min, max] of 5 interleaved rounds, beside (a) the plain shortlist kernel on the same R rows as R videos and (b)
+           torch.matmul + scatter_reduce_(amax) + torch.topk, with the read floor (R * E * 2 bytes per 16 sentences at 6.29 TB/s) beside
+           every figure; the derived condition that the 16-row and 120-row layouts take no longer than the 1-row layout by more than
+           its max - min, shape by shape; the largest error / tolerance ratio of tests/test_segment_shortlist_gpu.py's random case.
+           Random embeddings: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1178,6 +1187,118 @@ def main_device_candidates(args):
     print("wrote", out)
 
 
+SEGMENT_LAYOUTS = (("65536x1", [1] * 65536), ("4096x16", [16] * 4096), ("546x120", [120] * 545 + [136]))     # R = 65,536 each: the
+# bench store's 546 videos of 120 rows come to 65,520, so its last video takes the 16 rows that remain
+
+
+def interleaved_windows(variants, rounds, window_s=0.2):
+    """{name: launch} -> ({name: [us per call, one per round]}, {name: calls per window}): launch-inclusive, device events around windows
+    of back-to-back calls, the variants taking turns inside every round."""
+    def run(launch, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+    reps = {}
+    for k, launch in variants.items():
+        run(launch, 5)
+        reps[k] = max(10, min(2000, int(window_s / (run(launch, 10) * 1e-6))))
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, launch in variants.items():
+            times[k].append(run(launch, reps[k]))
+    return times, reps
+
+
+def bench_segment_shortlist(name, lens, emb, S, n, rounds):
+    """drn_shortlist_segments_topn on R = 65,536 rows cut into videos by `lens`, beside (a) the plain kernel of the parent on the same R
+    rows as R videos and (b) what a caller can do without the feature: torch.matmul, a segmented amax, torch.topk."""
+    import numpy as np
+    from drn_amd import SegmentShortlist, Shortlist, Shortlister
+    R, V = int(emb.shape[0]), len(lens)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    assert off[-1] == R
+    g = torch.Generator(device="cuda:0").manual_seed(S + n)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    seg, plain = Shortlister(emb, offsets=off), Shortlister(emb)
+    out_seg, out_plain = SegmentShortlist(*seg.shortlist(q, n)), Shortlist(*plain.shortlist(q, n))
+    index = torch.repeat_interleave(torch.arange(V, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(S, R).contiguous()
+    best = torch.empty((S, V), dtype=torch.bfloat16, device="cuda:0")
+
+    def torch_way():
+        best.fill_(float("-inf"))
+        best.scatter_reduce_(1, index, torch.matmul(q, emb.t()), "amax")
+        return torch.topk(best, min(n, V), dim=1)
+    times, reps = interleaved_windows({"segments": lambda: seg.shortlist(q, n, out=out_seg), "plain_rows": lambda: plain.shortlist(q, n, out=out_plain),
+                                       "torch": torch_way}, rounds)
+    table, tiles = emb.numel() * emb.element_size(), -(-S // 16)
+    med = {k: statistics.median(ts) for k, ts in times.items()}
+    return {"layout": name, "R": R, "V": V, "E": 512, "S": S, "n": n, "dtype": "bf16", "blocks": int(seg.plan.blk_vid.shape[0]) - 1,
+            "launches_per_window": reps, "table_bytes": table, "table_reads": tiles,
+            "segments_us": spread(times["segments"]), "plain_rows_us": spread(times["plain_rows"]), "matmul_amax_topk_us": spread(times["torch"]),
+            "read_floor_us_at_6.29TB/s": tiles * table / HBM_COPY_BYTES_PER_S * 1e6, "table_once_us_at_8.0TB/s": table / HBM_PEAK_BYTES_PER_S * 1e6,
+            "segments_over_plain_rows": med["segments"] / med["plain_rows"], "segments_against_plain_rows": verdict(times["segments"], times["plain_rows"]),
+            "segments_over_matmul_amax_topk": med["segments"] / med["torch"], "segments_against_matmul_amax_topk": verdict(times["segments"], times["torch"]),
+            "segments_over_read_floor": med["segments"] / (tiles * table / HBM_COPY_BYTES_PER_S * 1e6),
+            "note": "launch-inclusive, all three launches of the segmented shortlist; plain_rows ranks the same R rows as R videos (another "
+                    "answer: rows, not videos); torch scores in bf16, here fp32; the floor counts the table once per 16 sentences and nothing else"}
+
+
+def segment_tolerance_ratio():
+    """tests/test_segment_shortlist_gpu.py's random case (E = 512, run lengths 1, 3, 0, 17 twenty times, then 300 and 2; S = 5, n = 16,
+    bf16): the largest |returned score - the video's float64 maximum| over tol = the largest E * 2^-23 * sum |q * emb_r| of its rows."""
+    import numpy as np
+    from drn_amd import Shortlister
+    lens = [1, 3, 0, 17] * 20 + [300, 2]
+    g = torch.Generator().manual_seed(4)
+    emb = torch.randn(sum(lens), 512, generator=g).to("cuda:0", torch.bfloat16).contiguous()
+    q = torch.randn(17, 512, generator=g).to("cuda:0", torch.bfloat16)[:5].contiguous()
+    got = Shortlister(emb, offsets=np.concatenate([[0], np.cumsum(lens)])).shortlist(q, 16)
+    video = torch.repeat_interleave(torch.arange(len(lens), device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(5, -1)
+    ref = torch.full((5, len(lens)), float("-inf"), dtype=torch.float64, device="cuda:0").scatter_reduce(1, video, q.double() @ emb.double().t(), "amax")
+    tol = torch.zeros_like(ref).scatter_reduce(1, video, 512 * 2.0 ** -23 * (q.double().abs() @ emb.double().abs().t()), "amax")
+    ids = got.ids.long()
+    return float(((got.scores.double() - torch.gather(ref, 1, ids)).abs() / torch.gather(tol, 1, ids)).max())
+
+
+def main_segment_shortlist(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_segment_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "plain_rows: the parent's drn_shortlist_topn on the same R rows, in the same process, its code unchanged; "
+                                   "matmul_amax_topk: torch.matmul, scatter_reduce_(amax) over the videos' rows, torch.topk.  A difference "
+                                   "inside the baseline's own max - min is NO DIFFERENCE",
+                      "condition": "derived, not measured: at the same R the 16-row and 120-row layouts score the same rows with the same MFMAs "
+                                   "and sort fewer keys than the 1-row layout, so neither may take longer than it by more than ITS max - min",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall"},
+           "tolerance_ratio": segment_tolerance_ratio(), "segment_shortlist": [], "condition": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for n in (16, 128):
+            rows = {}
+            for name, lens in SEGMENT_LAYOUTS:
+                rows[name] = bench_segment_shortlist(name, lens, emb, S, n, args.rounds)
+                res["segment_shortlist"].append(rows[name])
+                print(json.dumps({"segment_shortlist": rows[name]}), flush=True)
+            base = rows["65536x1"]["segments_us"]
+            for name in ("4096x16", "546x120"):
+                over = rows[name]["segments_us"]["median"] - base["median"]
+                res["condition"].append({"S": S, "n": n, "layout": name, "median_minus_1row_median_us": over,
+                                         "1row_max_minus_min_us": base["max"] - base["min"], "holds": over <= base["max"] - base["min"]})
+                print(json.dumps({"condition": res["condition"][-1]}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -1193,9 +1314,13 @@ def main():
                                                                   "wide tile and the default fused path on one quantised index")
     ap.add_argument("--device-candidates", action="store_true", help="measure Shortlister.shortlist + Grounder.search(candidates= a device "
                                                                      "tensor) beside the shortlist read back as host lists")
+    ap.add_argument("--segment-shortlist", action="store_true", help="measure Shortlister(offsets=).shortlist on 65,536 rows in three layouts "
+                                                                     "beside the plain kernel on the same rows and matmul + amax + topk")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.segment_shortlist:
+        return main_segment_shortlist(args)
     if args.device_candidates:
         return main_device_candidates(args)
     if args.shortlist:
