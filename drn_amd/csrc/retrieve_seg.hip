@@ -170,6 +170,12 @@ __global__ __launch_bounds__(256) void shortlist_segment_rows_kernel(const sl_ke
   rows[idx] = row;
 }
 
+// (declared in shortlist.h: retrieve_q8.hip's lists are looked up by the same kernel; not part of the C ABI)
+void sl_launch_segment_rows(const sl_key_t* ws, const int* wsr, const int32_t* vid_blk, const int32_t* ids, int V, int S, int n, int m,
+                            int nblocks, int32_t* rows, hipStream_t stream) {
+  shortlist_segment_rows_kernel<<<cdiv(S * n, 256), 256, 0, stream>>>(ws, wsr, vid_blk, ids, V, S * n, n, m, nblocks, rows);
+}
+
 extern "C" int drn_shortlist_segments_topn(const void* emb, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
                                            const int32_t* vid_blk, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws,
                                            int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream) {
@@ -199,7 +205,6 @@ extern "C" int drn_shortlist_segments_topn(const void* emb, const void* queries,
     shortlist_segments_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)emb, (const float*)queries, offsets, blk_vid, R, V,
                                                                             E, S, m, nblocks, lists_k, lists_r);
   sl_launch_merge(lists_k, S, n, m, nblocks, ids, scores, counts, (hipStream_t)stream);
-  shortlist_segment_rows_kernel<<<cdiv(S * n, 256), 256, 0, (hipStream_t)stream>>>(lists_k, lists_r, vid_blk, ids, V, S * n, n, m, nblocks,
-                                                                                  rows);
+  sl_launch_segment_rows(lists_k, lists_r, vid_blk, ids, V, S, n, m, nblocks, rows, (hipStream_t)stream);
   return drn_launch_status("drn_shortlist_segments_topn");
 }

@@ -1,8 +1,10 @@
 // What the two shortlist translation units share (retrieve.hip: one vector per video; retrieve_seg.hip: a ragged run of segment vectors
 // per video): the 64-bit candidate key, the bitonic sort, the fragment loaders and the MFMA step of one (sentence, row) score, and the
-// host-side launch of the merging kernel, which lives in retrieve.hip and serves both.
+// host-side launch of the merging kernel, which lives in retrieve.hip and serves both.  retrieve_q8.hip ranks the same two tables kept in
+// block-scaled FP8: its table operand is sl_frag_q8 below, everything after the scores is what is declared here.
 #pragma once
 #include "common.h"
+#include "mx8.h"
 
 typedef unsigned long long sl_key_t;
 
@@ -63,6 +65,28 @@ __device__ __forceinline__ f32x4 sl_mfma(const f32x4 a, const f32x4 b, f32x4 acc
   for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
   return acc;
 }
+// The table operand of a block-scaled FP8 table (drn_amd/index.py mx8_quantize is the format): the PER_LANE code bytes of `codes` from
+// column c0, as loaded, and -- with their block's scale byte -- the fragment sl_frag would load from the dequantised row.  code -> fp32
+// by v_cvt_pk_f32_fp8 (OCP on gfx950), times 2^(scale - 127) (the scale byte placed in the fp32 exponent field), then -> bf16 for a
+// bf16 chain: every step is exact (four significant bits; the format keeps every value zero or a normal number), the statements of
+// gate_gather_packed_q8_kernel (qindex.hip).  c0 is a multiple of PER_LANE, which divides 32: a lane's columns lie inside one block.
+__device__ __forceinline__ u32x2 sl_codes_q8(const uint8_t* codes, const int c0, bf16_t) { return *reinterpret_cast<const u32x2*>(codes + c0); }
+__device__ __forceinline__ unsigned sl_codes_q8(const uint8_t* codes, const int c0, float) { return *reinterpret_cast<const unsigned*>(codes + c0); }
+__device__ __forceinline__ bf16x8 sl_frag_q8(const u32x2 w, const unsigned scale) {
+  const float sc = __uint_as_float(scale << 23);
+  bf16x8 f;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
+    f[4 * j] = (bf16_t)(lo[0] * sc); f[4 * j + 1] = (bf16_t)(lo[1] * sc); f[4 * j + 2] = (bf16_t)(hi[0] * sc); f[4 * j + 3] = (bf16_t)(hi[1] * sc);
+  }
+  return f;
+}
+__device__ __forceinline__ f32x4 sl_frag_q8(const unsigned w, const unsigned scale) {
+  const float sc = __uint_as_float(scale << 23);
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  return f32x4{lo[0] * sc, lo[1] * sc, hi[0] * sc, hi[1] * sc};
+}
 template <typename T> struct SlStep;
 template <> struct SlStep<bf16_t> { static constexpr int COLS = 32, PER_LANE = 8; };
 template <> struct SlStep<float> { static constexpr int COLS = 16, PER_LANE = 4; };
@@ -70,3 +94,7 @@ template <> struct SlStep<float> { static constexpr int COLS = 16, PER_LANE = 4;
 // shortlist_merge_kernel (retrieve.hip) on `stream`: sentence s merges its nblocks sorted lists of m keys, ws[s][block][0..m), into
 // ids, scores [S][n] and counts [S].  Not part of the C ABI.
 void sl_launch_merge(const sl_key_t* ws, int S, int n, int m, int nblocks, int32_t* ids, float* scores, int32_t* counts, hipStream_t stream);
+// shortlist_segment_rows_kernel (retrieve_seg.hip) on `stream`: the winning segment of each listed (sentence, place), looked up in the
+// lists ws / wsr of the video's block, into rows [S][n].  Not part of the C ABI.
+void sl_launch_segment_rows(const sl_key_t* ws, const int* wsr, const int32_t* vid_blk, const int32_t* ids, int V, int S, int n, int m,
+                            int nblocks, int32_t* rows, hipStream_t stream);

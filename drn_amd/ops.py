@@ -1560,6 +1560,69 @@ def shortlist_segments_topn(emb, queries, offsets, blk_vid, vid_blk, n, ws, ids,
     return ids, scores, counts, rows
 
 
+def _q8_table(what, codes, scales, queries):
+    """The checks a block-scaled FP8 table shares between the two quantised shortlists -> (rows, E)."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or not codes.is_contiguous() \
+            or not scales.is_contiguous() or codes.shape[1] % 32 or tuple(scales.shape) != (int(codes.shape[0]), int(codes.shape[1]) // 32):
+        raise _lib.DrnError("%s: codes (rows, E) and scales (rows, E / 32) must be contiguous uint8 tensors with E a multiple of 32" % what)
+    if queries.dim() != 2 or not queries.is_contiguous() or queries.dtype not in (torch.float32, torch.bfloat16) \
+            or queries.shape[1] != codes.shape[1]:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, %d) float32 / bfloat16 tensor" % (what, int(codes.shape[1])))
+    return int(codes.shape[0]), int(codes.shape[1])
+
+
+def shortlist_topn_q8(codes, scales, queries, n, ws, ids, scores, counts):
+    """shortlist_topn over a table kept in block-scaled FP8: codes (V, E) and scales (V, E / 32) uint8 as quantize_rows_mx8 writes them,
+    E % 32 == 0; queries (S, E) float32 / bfloat16, whose dtype chooses the MFMA chain (drn_shortlist_topn_q8).  The result is bit for
+    bit shortlist_topn over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype); ws, ids, scores and counts as there.  Two
+    launches on the current stream behind one entry (one tag, shortlist_topn_q8); no host synchronisation."""
+    _need_gpu(codes, scales, queries, ws, ids, scores, counts)
+    n = int(n)
+    V, E = _q8_table("shortlist_topn_q8", codes, scales, queries)
+    S = int(queries.shape[0])
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("shortlist_topn_q8: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
+    for name, t, dt, shape in (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)),
+                               ("counts", counts, torch.int32, (S,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("shortlist_topn_q8: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < shortlist_ws_keys(V, S, n):
+        raise _lib.DrnError("shortlist_topn_q8: ws must be a contiguous int64 tensor of at least %d elements" % shortlist_ws_keys(V, S, n))
+    _timed("shortlist_topn_q8", 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_q8(
+        _p(codes), _p(scales), _p(queries), V, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores),
+        _p(counts), _stream()), "drn_shortlist_topn_q8"))
+    return ids, scores, counts
+
+
+def shortlist_segments_topn_q8(codes, scales, queries, offsets, blk_vid, vid_blk, n, ws, ids, scores, counts, rows):
+    """shortlist_segments_topn over a ragged table kept in block-scaled FP8: codes (R, E) and scales (R, E / 32) uint8, E % 32 == 0;
+    queries (S, E) float32 / bfloat16, whose dtype chooses the MFMA chain (drn_shortlist_segments_topn_q8).  The result is bit for bit
+    shortlist_segments_topn over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype); every other argument as there.  Three
+    launches on the current stream behind one entry (one tag, shortlist_segments_topn_q8); nothing is read on the host."""
+    _need_gpu(codes, scales, queries, offsets, blk_vid, vid_blk, ws, ids, scores, counts, rows)
+    n = int(n)
+    R, E = _q8_table("shortlist_segments_topn_q8", codes, scales, queries)
+    S = int(queries.shape[0])
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("shortlist_segments_topn_q8: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
+    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
+        raise _lib.DrnError("shortlist_segments_topn_q8: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1")
+    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
+    for name, t, dt, shape in (("offsets", offsets, torch.int32, (V + 1,)), ("blk_vid", blk_vid, torch.int32, (nblocks + 1,)),
+                               ("vid_blk", vid_blk, torch.int32, (V,)), ("ids", ids, torch.int32, (S, n)),
+                               ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)),
+                               ("rows", rows, torch.int32, (S, n))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("shortlist_segments_topn_q8: %s must be a contiguous %s %s tensor" % (name, shape, dt))
+    need = shortlist_segments_ws_keys(nblocks, S, n)
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < need:
+        raise _lib.DrnError("shortlist_segments_topn_q8: ws must be a contiguous int64 tensor of at least %d elements" % need)
+    _timed("shortlist_segments_topn_q8", 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_q8(
+        _p(codes), _p(scales), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), R, V, nblocks, E, S, n, dtype_code(queries), _p(ws),
+        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn_q8"))
+    return ids, scores, counts, rows
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -10,7 +10,14 @@ shortlist_reference is the definition, in plain torch; Shortlister.shortlist is 
 A dual encoder hands out one embedding per clip, shot or window rather than one per video.  Shortlister(offsets=) takes such a RAGGED
 table -- R segment rows, video v owning the rows offsets[v] .. offsets[v + 1] - 1, the FeatureStore's seg_off layout -- scores a video
 by its BEST segment and lists distinct videos, with the winning segment beside each: segment_shortlist_reference is that definition,
-drn_shortlist_segments_topn (csrc/retrieve_seg.hip) the launch, plan_segment_blocks its host-side block plan."""
+drn_shortlist_segments_topn (csrc/retrieve_seg.hip) the launch, plan_segment_blocks its host-side block plan.
+
+Shortlister(quantize="mxfp8") and Shortlister.from_mx8 keep either table in block-scaled FP8 (the index's MX layout, drn_amd.index.mx8_quantize:
+E + E / 32 bytes a row instead of 2 E or 4 E) and rank it with drn_shortlist_topn_q8 / drn_shortlist_segments_topn_q8
+(csrc/retrieve_q8.hip).  A dequantised value is exact in bfloat16 and float32, so no new definition is needed: the quantised shortlist IS
+shortlist_reference(mx8_dequantize(codes, scales), queries, n) -- with offsets, segment_shortlist_reference of the same dequantised
+table -- and the kernels answer bit for bit like shortlister.dequantized(), a plain Shortlister over those rows.  Quantising the table
+is lossy against the ORIGINAL embeddings (|dq - x| <= max(|x| / 16, 2^e / 1024) per element); the ranking of what the table holds is not."""
 import collections
 
 import numpy as np
@@ -18,6 +25,7 @@ import torch
 
 from . import ops
 from ._lib import SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
 Shortlist.__doc__ = """ids (S, n) int32 store positions, best first, -1 past the list; scores (S, n) float32, 0 past the list; n (S,) int32 the
@@ -148,8 +156,22 @@ def segment_shortlist_reference(embeddings, offsets, queries, n):
     return SegmentShortlist(ids, scores, count.to(torch.int32), segs)
 
 
+def quantized_score_bound(embeddings, scales, queries):
+    """How far a quantised table's score may lie from the float64 score of the ORIGINAL table -> (S, rows) float64.  embeddings (rows,
+    E) is the table before quantising and scales (rows, E / 32) the scale bytes mx8_quantize gave it.  The format rounds an element to
+    within max(|x| / 16, 2^e / 1024) of itself (e4m3fn keeps four significant bits of a normal code, and its subnormal codes are 2^-9
+    apart; e = scale - 127), so |q . dq - q . x| <= sum_e |q_e| * max(|x_e| / 16, 2^e_block / 1024); the fp32 accumulation of E products
+    adds at most E * 2^-23 * sum_e |q_e * x_e| (tests/test_shortlist_gpu.py derives that term).  A best-segment score moves by no more
+    than the largest bound among the video's rows."""
+    x, q = embeddings.double(), queries.double()
+    rows, E = (int(v) for v in x.shape)
+    ulp = torch.ldexp(torch.ones((), dtype=torch.float64, device=x.device), scales.to(x.device).to(torch.int32) - 127 - 10)
+    per = torch.maximum(x.abs() / 16, ulp.repeat_interleave(MX8_BLOCK, dim=1))
+    return q.abs() @ per.t() + E * 2.0 ** -23 * (q.abs() @ x.abs().t())
+
+
 class Shortlister(object):
-    """Shortlister(embeddings, names=None, offsets=None): a (V, E) table of video embeddings, row v belonging to store position v -- a
+    """Shortlister(embeddings, names=None, offsets=None, quantize=None): a (V, E) table of video embeddings, row v belonging to store position v -- a
     contiguous CUDA tensor, bfloat16 or float32, V >= 1 and E >= 1, kept by reference.  Non-finite embeddings are refused here (ONE
     synchronise, once).  names: kept when given; check(store) raises unless they are the store's, before any launch.
 
@@ -158,9 +180,24 @@ class Shortlister(object):
     1 <= R < 2^31 (a video may own no row: it is never listed).  They are checked on the host here, in the same one synchronise as the
     embeddings, and the block plan (plan_segment_blocks) is made and put on the device once.  len() is V and names has V entries;
     shortlist() scores a video by its best segment and returns a SegmentShortlist.  Beside a FeatureStore, whose windows are such
-    runs, the intended use is Shortlister(window_embeddings, names=store.names, offsets=store.seg_off)."""
+    runs, the intended use is Shortlister(window_embeddings, names=store.names, offsets=store.seg_off).
 
-    def __init__(self, embeddings, names=None, offsets=None):
+    quantize="mxfp8" keeps the table -- plain or ragged -- in block-scaled FP8 instead: codes (rows, E) uint8 and scales (rows, E / 32)
+    uint8, byte for byte drn_amd.index.mx8_quantize of the embeddings (written by ops.quantize_rows_mx8), E + E / 32 bytes a row.  E must
+    be a multiple of 32.  Every check above is made as without it, in the same one synchronise, and NO reference to `embeddings` is
+    kept: the caller may drop the wide table.  Shortlister.from_mx8 takes tables quantised elsewhere.  shortlist() then returns, bit for
+    bit, what dequantized() -- a plain Shortlister over mx8_dequantize(codes, scales, dtype) -- returns; against the ORIGINAL embeddings
+    the table is lossy (the format's bound per element), and what that does to recall this module does not say.
+
+    Attributes a caller may rely on: quantize (None or "mxfp8"); dtype (of the table's values and of the queries shortlist() takes) and
+    E; embeddings (the table, None on a quantised object); codes and scales (None on a plain one); names; offsets and plan on a ragged
+    table; nbytes, the bytes of the table held (= bytes_of(rows, E, dtype, quantize))."""
+
+    quantize = codes = scales = _dtype = None     # (what a plain table has; also for an object made without the constructor)
+
+    def __init__(self, embeddings, names=None, offsets=None, quantize=None):
+        if quantize not in QUANTIZE:
+            raise DrnError("Shortlister: quantize must be one of %s, not %r" % (QUANTIZE, quantize))
         if not torch.is_tensor(embeddings) or not embeddings.is_cuda:
             raise DrnError("Shortlister: the embeddings must be a tensor on the GPU; there is no CPU fallback")
         if embeddings.dtype not in (torch.bfloat16, torch.float32):
@@ -168,23 +205,79 @@ class Shortlister(object):
         if embeddings.dim() != 2 or embeddings.shape[0] < 1 or embeddings.shape[1] < 1 or not embeddings.is_contiguous():
             raise DrnError("Shortlister: the embeddings must be a contiguous (V, E) tensor with V >= 1 and E >= 1, not %s"
                            % (tuple(embeddings.shape),))
+        rows, E = (int(x) for x in embeddings.shape)
+        if quantize is not None and E % MX8_BLOCK:
+            raise DrnError("Shortlister: quantize=%r needs E to be a multiple of %d (one scale per %d columns, and the kernels have no "
+                           "tail), not E = %d" % (quantize, MX8_BLOCK, MX8_BLOCK, E))
+        self._init_table(rows, embeddings.device, names, offsets, lambda: torch.isfinite(embeddings).all(),
+                         "the embeddings hold values that are not finite")
+        if quantize is None:
+            self.embeddings = embeddings
+            return
+        self.embeddings, self.quantize, self._dtype = None, quantize, embeddings.dtype
+        self.codes = torch.empty((rows, E), dtype=torch.uint8, device=embeddings.device)
+        self.scales = torch.empty((rows, E // MX8_BLOCK), dtype=torch.uint8, device=embeddings.device)
+        step = max(1, (1 << 30) // E)             # (a launch quantises at most 2^30 elements: one launch up to 2 M rows of 512)
+        for a in range(0, rows, step):
+            ops.quantize_rows_mx8(embeddings[a:a + step], self.codes[a:a + step], self.scales[a:a + step])
+
+    @classmethod
+    def from_mx8(cls, codes, scales, dtype, names=None, offsets=None):
+        """A quantised Shortlister on tables the caller quantised: codes (rows, E) and scales (rows, E / 32), contiguous uint8 CUDA
+        tensors, E % 32 == 0, kept by reference -- ops.quantize_rows_mx8(x_chunk, codes[a:b], scales[a:b]) fills row slices, so the wide
+        table never has to exist.  dtype (torch.bfloat16 or torch.float32) is that of the queries and fixes which MFMA chain scores.
+        Raises unless the tables are the format's: no code an e4m3fn NaN (0x7f / 0xff), every scale byte in [17, 254] (2^-110 .. 2^127,
+        the range mx8_quantize writes: below it a value could be subnormal, which is not exact in bfloat16) and every dequantised value
+        finite in dtype -- checked in row chunks, without materialising the dequantised table, in the ONE synchronise that also
+        serves the offsets.  names and offsets as in the constructor."""
+        if not torch.is_tensor(codes) or not torch.is_tensor(scales) or not codes.is_cuda or not scales.is_cuda:
+            raise DrnError("Shortlister.from_mx8: codes and scales must be tensors on the GPU; there is no CPU fallback")
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+            raise DrnError("Shortlister.from_mx8: codes and scales must be uint8, not %s and %s" % (codes.dtype, scales.dtype))
+        if codes.dim() != 2 or codes.shape[0] < 1 or codes.shape[1] < 1 or not codes.is_contiguous():
+            raise DrnError("Shortlister.from_mx8: codes must be a contiguous (V, E) tensor with V >= 1 and E >= 1, not %s" % (tuple(codes.shape),))
+        rows, E = (int(x) for x in codes.shape)
+        if E % MX8_BLOCK:
+            raise DrnError("Shortlister.from_mx8: E must be a multiple of %d (one scale per %d columns, and the kernels have no tail), "
+                           "not E = %d" % (MX8_BLOCK, MX8_BLOCK, E))
+        if tuple(scales.shape) != (rows, E // MX8_BLOCK) or not scales.is_contiguous():
+            raise DrnError("Shortlister.from_mx8: scales must be a contiguous (%d, %d) tensor beside codes %s, not %s"
+                           % (rows, E // MX8_BLOCK, tuple(codes.shape), tuple(scales.shape)))
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise DrnError("Shortlister.from_mx8: dtype (of the queries) must be bfloat16 or float32, not %s" % (dtype,))
+
+        def sound():
+            ok = (scales >= MX8_EMIN + 127).all() & (scales <= 254).all()
+            step = max(1, (1 << 22) // E)         # (a chunk's dequantised rows and the table look-up's indices: 4 M elements)
+            for a in range(0, rows, step):
+                c = codes[a:a + step]
+                ok = ok & ((c & 0x7f) != 0x7f).all() & torch.isfinite(mx8_dequantize(c, scales[a:a + step], dtype)).all()
+            return ok
+        self = cls.__new__(cls)
+        self._init_table(rows, codes.device, names, offsets, sound,
+                         "the tables are not block-scaled FP8 with finite values (a NaN code 0x7f / 0xff, a scale byte outside "
+                         "[17, 254], or a value that is not finite in %s)" % (dtype,))
+        self.embeddings, self.quantize, self._dtype, self.codes, self.scales = None, "mxfp8", dtype, codes, scales
+        return self
+
+    def _init_table(self, rows, dev, names, offsets, sound, unsound):
+        """What every way of building shares: names, offsets and the block plan, and the ONE synchronise that brings sound() -- a
+        device boolean, launched here after the host-side refusals -- to the host."""
         self.names = None if names is None else list(names)
         self._seg = None
-        if offsets is not None:
-            self._init_segments(embeddings, offsets)
-        else:
-            if self.names is not None and len(self.names) != int(embeddings.shape[0]):
-                raise DrnError("Shortlister: %d names for %d embeddings" % (len(self.names), int(embeddings.shape[0])))
-            if not bool(torch.isfinite(embeddings).all()):
-                raise DrnError("Shortlister: the embeddings hold values that are not finite")
-        self.embeddings = embeddings
         self._ws = {}
+        if offsets is not None:
+            self._init_segments(rows, dev, offsets, sound, unsound)
+        else:
+            if self.names is not None and len(self.names) != rows:
+                raise DrnError("Shortlister: %d names for %d embeddings" % (len(self.names), rows))
+            if not bool(sound()):
+                raise DrnError("Shortlister: " + unsound)
 
-    def _init_segments(self, embeddings, offsets):
+    def _init_segments(self, R, dev, offsets, sound, unsound):
         """The ragged table's checks and its device tables.  Offsets that live on the device come to the host in the one transfer
-        that brings the embeddings' finiteness."""
-        dev, R = embeddings.device, int(embeddings.shape[0])
-        finite = torch.isfinite(embeddings).all()
+        that brings the table's soundness (its finiteness)."""
+        finite = sound()
         if torch.is_tensor(offsets) and offsets.is_cuda:
             if offsets.is_floating_point() or offsets.is_complex() or offsets.dtype == torch.bool:
                 raise DrnError("Shortlister: the offsets must be integers, not %s" % offsets.dtype)
@@ -194,16 +287,57 @@ class Shortlister(object):
             offsets, finite = both[:-1], bool(both[-1])
         off = check_segment_offsets(offsets, R, self.names)
         if not bool(finite):
-            raise DrnError("Shortlister: the embeddings hold values that are not finite")
+            raise DrnError("Shortlister: " + unsound)
         plan = plan_segment_blocks(off)
         put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         self.plan = plan
         self._seg = (put(off), put(plan.blk_vid), put(plan.vid_blk))
         self.offsets = self._seg[0]
 
+    def _table(self):
+        """The tensor that has the table's rows, columns and device: the embeddings, or the codes of a quantised table."""
+        return self.embeddings if self.quantize is None else self.codes
+
+    @property
+    def dtype(self):
+        """The dtype of the table's values and of the queries shortlist() takes."""
+        return self.embeddings.dtype if self.quantize is None else self._dtype
+
+    @property
+    def E(self):
+        return int(self._table().shape[1])
+
+    @staticmethod
+    def bytes_of(rows, E, dtype, quantize=None):
+        """The bytes of a table of `rows` rows of E columns: rows * E * itemsize(dtype) as given, rows * (E + E / 32) with
+        quantize="mxfp8" whatever the dtype (528 against 1024 in bfloat16 and 2048 in float32 at E = 512)."""
+        rows, E = int(rows), int(E)
+        if quantize not in QUANTIZE:
+            raise DrnError("Shortlister.bytes_of: quantize must be one of %s, not %r" % (QUANTIZE, quantize))
+        if quantize is None:
+            return rows * E * torch.empty((), dtype=dtype).element_size()
+        if E % MX8_BLOCK:
+            raise DrnError("Shortlister.bytes_of: quantize=%r needs E to be a multiple of %d, not E = %d" % (quantize, MX8_BLOCK, E))
+        return rows * (E + E // MX8_BLOCK)
+
+    @property
+    def nbytes(self):
+        """The bytes of the table this object holds (the offsets, the plan and the workspaces are not counted)."""
+        if self.quantize is None:
+            return self.embeddings.numel() * self.embeddings.element_size()
+        return self.codes.numel() + self.scales.numel()
+
+    def dequantized(self):
+        """A plain Shortlister over mx8_dequantize(codes, scales, dtype) with the same names and offsets: what the quantised table
+        really holds, and the oracle shortlist() answers bit for bit like.  (On a plain table: itself.)"""
+        if self.quantize is None:
+            return self
+        seg = getattr(self, "_seg", None)
+        return Shortlister(mx8_dequantize(self.codes, self.scales, self._dtype), names=self.names, offsets=None if seg is None else seg[0])
+
     def __len__(self):
         seg = getattr(self, "_seg", None)
-        return int(self.embeddings.shape[0]) if seg is None else int(seg[0].shape[0]) - 1
+        return int(self._table().shape[0]) if seg is None else int(seg[0].shape[0]) - 1
 
     def check(self, store):
         """Raises unless this table's names are the store's (a FeatureStore or a SearchIndex), position by position."""
@@ -212,13 +346,13 @@ class Shortlister(object):
 
     def _check(self, queries, n, out):
         """shortlist's refusals, before the library is reached -> (S, n)."""
-        emb = self.embeddings
+        E, dtype = self.E, self.dtype
         if not torch.is_tensor(queries):
             raise DrnError("Shortlister.shortlist: the queries must be a tensor")
-        if queries.dim() != 2 or queries.shape[0] < 1 or queries.shape[1] != emb.shape[1]:
-            raise DrnError("Shortlister.shortlist: the queries must be (S, %d), not %s" % (int(emb.shape[1]), tuple(queries.shape)))
-        if queries.dtype != emb.dtype:
-            raise DrnError("Shortlister.shortlist: the queries are %s, the table is %s" % (queries.dtype, emb.dtype))
+        if queries.dim() != 2 or queries.shape[0] < 1 or queries.shape[1] != E:
+            raise DrnError("Shortlister.shortlist: the queries must be (S, %d), not %s" % (E, tuple(queries.shape)))
+        if queries.dtype != dtype:
+            raise DrnError("Shortlister.shortlist: the queries are %s, the table is %s" % (queries.dtype, dtype))
         n = int(n)
         if not 1 <= n <= SHORTLIST_MAX:
             raise DrnError("Shortlister.shortlist: n = %d outside [1, %d]" % (n, SHORTLIST_MAX))
@@ -248,9 +382,15 @@ class Shortlister(object):
 
         On a ragged table (offsets=) -> SegmentShortlist (segment_shortlist_reference defines it): distinct videos by their best
         segment, with the winning segment in rows; out takes the four buffers.  A row's score has the same bits whatever the offsets,
-        and with one row per video the scores are the plain table's."""
+        and with one row per video the scores are the plain table's.
+
+        On a quantised table (quantize="mxfp8", from_mx8) the queries have the recorded dtype and the definition is
+        shortlist_reference(mx8_dequantize(codes, scales), queries, n) -- with offsets, segment_shortlist_reference of the same
+        dequantised table: the result types, the order, the padding, rows, out= and graph capture are unchanged, and every field is
+        bit for bit what dequantized().shortlist(queries, n) gives."""
         S, n = self._check(queries, n, out)
-        dev = self.embeddings.device
+        dev = self._table().device
+        q8 = self.quantize is not None
         seg = getattr(self, "_seg", None)
         if out is None:
             out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
@@ -262,9 +402,15 @@ class Shortlister(object):
             if ws is None:
                 keys = ops.shortlist_segments_ws_keys(int(seg[1].shape[0]) - 1, S, n)
                 ws = self._ws[(S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
-            ops.shortlist_segments_topn(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
+            if q8:
+                ops.shortlist_segments_topn_q8(self.codes, self.scales, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
+            else:
+                ops.shortlist_segments_topn(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
             return SegmentShortlist(*out)
         if ws is None:
             ws = self._ws[(S, n)] = torch.empty(ops.shortlist_ws_keys(len(self), S, n), dtype=torch.int64, device=dev)
-        ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)
+        if q8:
+            ops.shortlist_topn_q8(self.codes, self.scales, queries.contiguous(), n, ws, *out)
+        else:
+            ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)
         return Shortlist(*out)

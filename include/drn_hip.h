@@ -671,6 +671,20 @@ int drn_shortlist_topn(const void* emb, const void* queries, int V, int E, int S
 int drn_shortlist_segments_topn(const void* emb, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
                                 const int32_t* vid_blk, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys,
                                 int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
+/* drn_shortlist_topn and drn_shortlist_segments_topn over a table kept in block-scaled FP8 (drn_amd/csrc/retrieve_q8.hip): codes
+ * [V or R][E] uint8 (OCP e4m3fn) and scales [V or R][E / 32] uint8 (e8m0, one power-of-two scale per 32 columns), contiguous, as
+ * drn_quantize_rows_mx8 writes them, codes 16-byte aligned; E % 32 == 0, refused otherwise (there is no tail).  dtype is that of the
+ * QUERIES (float32 or bfloat16) and chooses the MFMA chain.  A table value is float(code) * 2^(scale - 127), exact in both dtypes,
+ * built in registers from 8 (bfloat16) or 4 (float32) code bytes and the scale byte of their block; the K-steps, their order and the
+ * MFMAs per (sentence, row) are the plain entries', so the lists are BIT FOR BIT those of the plain entry over the dequantised table.
+ * The table is not checked here: a NaN code (0x7f / 0xff) or a scale byte of 255 makes scores that are not finite and are not listed.
+ * Everything else -- the order, the padding, the workspace and its size, the block plan, the clamps, the launches (two and three) -- is
+ * the plain twin's. */
+int drn_shortlist_topn_q8(const uint8_t* codes, const uint8_t* scales, const void* queries, int V, int E, int S, int n, int dtype, void* ws,
+                          int ws_keys, int32_t* ids, float* scores, int32_t* counts, void* stream);
+int drn_shortlist_segments_topn_q8(const uint8_t* codes, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                   const int32_t* blk_vid, const int32_t* vid_blk, int R, int V, int nblocks, int E, int S, int n, int dtype,
+                                   void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

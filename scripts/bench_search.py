@@ -67,7 +67,16 @@
            torch.matmul + scatter_reduce_(amax) + torch.topk, with the read floor (R * E * 2 bytes per 16 sentences at 6.29 TB/s) beside
            every figure; the derived condition that the 16-row and 120-row layouts take no longer than the 1-row layout by more than
            its max - min, shape by shape; the largest error / tolerance ratio of tests/test_segment_shortlist_gpu.py's random case.
-           Random embeddings: nothing here says anything about recall."""
+           Random embeddings: nothing here says anything about recall.
+
+  --quantized-shortlist  instead of the above -> profiles/search_q8_shortlist_bench.json: Shortlister(quantize="mxfp8").shortlist
+           (drn_shortlist_topn_q8 on 65,536 videos x 1 row, drn_shortlist_segments_topn_q8 on 4,096 x 16 and 546 x 120; R = 65,536 rows
+           x 512, bf16 queries, S in {1, 8, 64}, n in {16, 128}, launch-inclusive us, median [min, max] of 5 interleaved rounds) beside
+           the plain table over the SAME dequantised rows ranked by the plain kernels in the same process, with each table's read
+           floor; the bytes of both tables (asserted equal to Shortlister.bytes_of); the time to quantise the table; whether the two
+           answers are the same bits; the tolerance_ratio of tests/test_q8_shortlist_gpu.py's lossy case; and, on the random table, the
+           share of sentences whose first video and whose n-list agree with those of the ORIGINAL unquantised table.  Random
+           embeddings: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1299,10 +1308,109 @@ def main_segment_shortlist(args):
     print("wrote", out)
 
 
+def bench_q8_shortlist(name, lens, emb, S, n, rounds):
+    """Shortlister(quantize="mxfp8") on R = 65,536 rows (one row per video: the plain entry; otherwise the segmented one) beside the
+    plain table over the SAME dequantised rows, in one process, and the agreement of its lists with those of the ORIGINAL table."""
+    import numpy as np
+    from drn_amd import Shortlister
+    R, V = int(emb.shape[0]), len(lens)
+    off = None if V == R else np.concatenate([[0], np.cumsum(lens)])
+    g = torch.Generator(device="cuda:0").manual_seed(S + n)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    quant = Shortlister(emb, offsets=off, quantize="mxfp8")
+    plain = quant.dequantized()
+    assert quant.nbytes == Shortlister.bytes_of(R, 512, torch.bfloat16, "mxfp8") and plain.nbytes == Shortlister.bytes_of(R, 512, torch.bfloat16)
+    out_q, out_p = quant.shortlist(q, n), plain.shortlist(q, n)
+    times, reps = interleaved_windows({"quantized": lambda: quant.shortlist(q, n, out=out_q), "plain": lambda: plain.shortlist(q, n, out=out_p)},
+                                      rounds)
+    same = all(torch.equal(a, b) for a, b in zip(out_q, out_p))
+    orig = Shortlister(emb, offsets=off).shortlist(q, n)
+    first = float((orig.ids[:, 0] == out_q.ids[:, 0]).double().mean())
+    lists = float((orig.ids == out_q.ids).all(dim=1).double().mean())
+    common = float((orig.ids[:, :, None] == out_q.ids[:, None, :]).any(dim=2).double().mean())      # (every list here is full: n <= V)
+    tiles = -(-S // 16)
+    med = {k: statistics.median(ts) for k, ts in times.items()}
+    return {"layout": name, "entry": "drn_shortlist_topn_q8" if off is None else "drn_shortlist_segments_topn_q8", "R": R, "V": V, "E": 512,
+            "S": S, "n": n, "dtype": "bf16", "launches_per_window": reps, "quantized_table_bytes": quant.nbytes, "plain_table_bytes": plain.nbytes,
+            "table_reads": tiles, "quantized_us": spread(times["quantized"]), "plain_us": spread(times["plain"]),
+            "quantized_read_floor_us_at_6.29TB/s": tiles * quant.nbytes / HBM_COPY_BYTES_PER_S * 1e6,
+            "plain_read_floor_us_at_6.29TB/s": tiles * plain.nbytes / HBM_COPY_BYTES_PER_S * 1e6,
+            "quantized_over_plain": med["quantized"] / med["plain"], "quantized_against_plain": verdict(times["quantized"], times["plain"]),
+            "equals_plain_over_dequantised_rows_bit_for_bit": same,
+            "against_the_original_table": {"share_of_sentences_with_the_same_first_video": first, "share_of_sentences_with_the_same_n_list": lists,
+                                           "mean_share_of_the_n_list_in_both": common},
+            "note": "launch-inclusive, every launch of the entry; plain ranks mx8_dequantize of the same codes; the agreement is on RANDOM "
+                    "embeddings against the table before quantising and says nothing about recall"}
+
+
+def q8_tolerance_ratio():
+    """tests/test_q8_shortlist_gpu.py's lossy case (E = 512, bf16, blocks of 32 columns scaled by 2^-3 .. 2^3, run lengths 1, 3, 0, 17
+    twenty times, then 300 and 2; S = 5, n = 16 and 128, the rows as videos and as runs): the largest |quantised score - float64 score
+    of the table BEFORE quantising| over drn_amd.retrieve.quantized_score_bound."""
+    import numpy as np
+    from drn_amd import Shortlister
+    from drn_amd.retrieve import quantized_score_bound
+    lens = [1, 3, 0, 17] * 20 + [300, 2]
+    R = sum(lens)
+    g = torch.Generator().manual_seed(4 + 1000 * R + 512)
+    emb = torch.randn(R, 512, generator=g) * torch.exp2(torch.randint(-3, 4, (R, 16), generator=g).float()).repeat_interleave(32, dim=1)
+    q = torch.randn(17, 512, generator=g)
+    emb, q = emb.to("cuda:0", torch.bfloat16).contiguous(), q.to("cuda:0", torch.bfloat16)[:5].contiguous()
+    video = torch.repeat_interleave(torch.arange(len(lens), device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(5, -1)
+    worst = 0.0
+    for off in (None, np.concatenate([[0], np.cumsum(lens)])):
+        sl = Shortlister(emb, offsets=off, quantize="mxfp8")
+        ref, tol = q.double() @ emb.double().t(), quantized_score_bound(emb, sl.scales, q)
+        if off is not None:
+            ref = torch.full((5, len(lens)), float("-inf"), dtype=torch.float64, device="cuda:0").scatter_reduce(1, video, ref, "amax")
+            tol = torch.zeros_like(ref).scatter_reduce(1, video, tol, "amax")
+        for n in (16, 128):
+            got = sl.shortlist(q, n)
+            ids = got.ids.clamp(min=0).long()
+            ratio = (got.scores.double() - torch.gather(ref, 1, ids)).abs() / torch.gather(tol, 1, ids)
+            worst = max(worst, float(ratio[got.ids >= 0].max()))
+    return worst
+
+
+def main_q8_shortlist(args):
+    from drn_amd import Shortlister, ops
+    out = args.out or os.path.join(ROOT, "profiles", "search_q8_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    codes = torch.empty((65536, 512), dtype=torch.uint8, device="cuda:0")
+    scales = torch.empty((65536, 16), dtype=torch.uint8, device="cuda:0")
+    quantize_us, reps = event_window(lambda: ops.quantize_rows_mx8(emb, codes, scales), args.rounds)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, both tables resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baseline": "plain: Shortlister over mx8_dequantize of the SAME codes and scales (bf16), the plain kernels, their code "
+                                  "unchanged, in the same process.  A difference inside the plain table's own max - min is NO DIFFERENCE",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall"},
+           "table": {"rows": 65536, "E": 512, "dtype": "bf16",
+                     "quantized_bytes": Shortlister.bytes_of(65536, 512, torch.bfloat16, "mxfp8"), "plain_bytes": Shortlister.bytes_of(65536, 512, torch.bfloat16),
+                     "float32_bytes": Shortlister.bytes_of(65536, 512, torch.float32),
+                     "bytes_per_row": {"quantized": Shortlister.bytes_of(1, 512, torch.bfloat16, "mxfp8"), "bf16": 1024, "fp32": 2048},
+                     "quantize_us": dict(spread(quantize_us), launches_per_window=reps, what="ops.quantize_rows_mx8 of the whole table, one launch")},
+           "tolerance_ratio": q8_tolerance_ratio(), "q8_shortlist": []}
+    del codes, scales
+    for S in (1, 8, 64):
+        for n in (16, 128):
+            for name, lens in SEGMENT_LAYOUTS:
+                row = bench_q8_shortlist(name, lens, emb, S, n, args.rounds)
+                res["q8_shortlist"].append(row)
+                print(json.dumps({"q8_shortlist": row}), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
-                                            "search_q8_bench.json with --quantized)")
+                                            "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1316,9 +1424,13 @@ def main():
                                                                      "tensor) beside the shortlist read back as host lists")
     ap.add_argument("--segment-shortlist", action="store_true", help="measure Shortlister(offsets=).shortlist on 65,536 rows in three layouts "
                                                                      "beside the plain kernel on the same rows and matmul + amax + topk")
+    ap.add_argument("--quantized-shortlist", action="store_true", help="measure Shortlister(quantize=\"mxfp8\").shortlist on 65,536 rows in three "
+                                                                       "layouts beside the plain table over the same dequantised rows")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.quantized_shortlist:
+        return main_q8_shortlist(args)
     if args.segment_shortlist:
         return main_segment_shortlist(args)
     if args.device_candidates:
