@@ -26,40 +26,7 @@
 #define SQ_BLOCK 256        // = SL_BLOCK (retrieve.hip) = SG_BLOCK (retrieve_seg.hip) = _lib.SHORTLIST_BLOCK = _lib.SHORTLIST_SEG_BLOCK
 #define SQ_LD (SQ_BLOCK + 1)
 
-// acc[j] += q[16 sentences] x the dequantised rows crow[j] / srow[j] (j = 0..3) over NB scale blocks from column c: every load of their
-// NB * 32 / COLS steps is issued before the first conversion, then the steps run in ascending order
-template <typename T, int NB>
-__device__ __forceinline__ void sq_blocks(const T* qrow, const uint8_t* const (&crow)[4], const uint8_t* const (&srow)[4], const int c,
-                                          const int g, f32x4 (&acc)[4]) {
-  constexpr int COLS = SlStep<T>::COLS, PER_LANE = SlStep<T>::PER_LANE, STEPS = NB * MX8_BLOCK / COLS;
-  decltype(sl_frag(qrow, 0)) a[STEPS];
-  decltype(sl_codes_q8(crow[0], 0, T())) w[STEPS][4];
-  unsigned sb[NB][4];
-#pragma unroll
-  for (int u = 0; u < NB; ++u)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sb[u][j] = srow[j][c / MX8_BLOCK + u];
-#pragma unroll
-  for (int k = 0; k < STEPS; ++k) {
-    const int c0 = c + k * COLS + g * PER_LANE;
-    a[k] = sl_frag(qrow, c0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[k][j] = sl_codes_q8(crow[j], c0, T());
-  }
-#pragma unroll
-  for (int k = 0; k < STEPS; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a[k], sl_frag_q8(w[k][j], sb[k * COLS / MX8_BLOCK][j]), acc[j]);
-}
-
-// all K-steps of E in ascending order, NB blocks at a time
-template <typename T, int NB>
-__device__ __forceinline__ void sq_scores(const T* qrow, const uint8_t* const (&crow)[4], const uint8_t* const (&srow)[4], const int E,
-                                          const int g, f32x4 (&acc)[4]) {
-  int c = 0;
-  for (; c + NB * MX8_BLOCK <= E; c += NB * MX8_BLOCK) sq_blocks<T, NB>(qrow, crow, srow, c, g, acc);
-  if (NB > 1 && c < E) sq_blocks<T, 1>(qrow, crow, srow, c, g, acc);      // (an odd number of blocks)
-}
+// (sq_blocks / sq_scores, the scores of a tile from codes and scale bytes: shortlist.h, shared with retrieve_allow.hip)
 
 template <typename T>
 __global__ __launch_bounds__(256) void shortlist_block_q8_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales,

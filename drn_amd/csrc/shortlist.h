@@ -1,7 +1,8 @@
 // What the two shortlist translation units share (retrieve.hip: one vector per video; retrieve_seg.hip: a ragged run of segment vectors
 // per video): the 64-bit candidate key, the bitonic sort, the fragment loaders and the MFMA step of one (sentence, row) score, and the
 // host-side launch of the merging kernel, which lives in retrieve.hip and serves both.  retrieve_q8.hip ranks the same two tables kept in
-// block-scaled FP8: its table operand is sl_frag_q8 below, everything after the scores is what is declared here.
+// block-scaled FP8: its table operand is sl_frag_q8 below, everything after the scores is what is declared here.  retrieve_allow.hip
+// ranks all four under an allow mask: the plain chain, and the FP8 chain sq_scores below, which it shares with retrieve_q8.hip.
 #pragma once
 #include "common.h"
 #include "mx8.h"
@@ -90,6 +91,41 @@ __device__ __forceinline__ f32x4 sl_frag_q8(const unsigned w, const unsigned sca
 template <typename T> struct SlStep;
 template <> struct SlStep<bf16_t> { static constexpr int COLS = 32, PER_LANE = 8; };
 template <> struct SlStep<float> { static constexpr int COLS = 16, PER_LANE = 4; };
+
+// acc[j] += q[16 sentences] x the dequantised rows crow[j] / srow[j] (j = 0..3) over NB scale blocks from column c: every load of their
+// NB * 32 / COLS steps is issued before the first conversion, then the steps run in ascending order
+template <typename T, int NB>
+__device__ __forceinline__ void sq_blocks(const T* qrow, const uint8_t* const (&crow)[4], const uint8_t* const (&srow)[4], const int c,
+                                          const int g, f32x4 (&acc)[4]) {
+  constexpr int COLS = SlStep<T>::COLS, PER_LANE = SlStep<T>::PER_LANE, STEPS = NB * MX8_BLOCK / COLS;
+  decltype(sl_frag(qrow, 0)) a[STEPS];
+  decltype(sl_codes_q8(crow[0], 0, T())) w[STEPS][4];
+  unsigned sb[NB][4];
+#pragma unroll
+  for (int u = 0; u < NB; ++u)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sb[u][j] = srow[j][c / MX8_BLOCK + u];
+#pragma unroll
+  for (int k = 0; k < STEPS; ++k) {
+    const int c0 = c + k * COLS + g * PER_LANE;
+    a[k] = sl_frag(qrow, c0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[k][j] = sl_codes_q8(crow[j], c0, T());
+  }
+#pragma unroll
+  for (int k = 0; k < STEPS; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a[k], sl_frag_q8(w[k][j], sb[k * COLS / MX8_BLOCK][j]), acc[j]);
+}
+
+// all K-steps of E in ascending order, NB blocks at a time
+template <typename T, int NB>
+__device__ __forceinline__ void sq_scores(const T* qrow, const uint8_t* const (&crow)[4], const uint8_t* const (&srow)[4], const int E,
+                                          const int g, f32x4 (&acc)[4]) {
+  int c = 0;
+  for (; c + NB * MX8_BLOCK <= E; c += NB * MX8_BLOCK) sq_blocks<T, NB>(qrow, crow, srow, c, g, acc);
+  if (NB > 1 && c < E) sq_blocks<T, 1>(qrow, crow, srow, c, g, acc);      // (an odd number of blocks)
+}
 
 // shortlist_merge_kernel (retrieve.hip) on `stream`: sentence s merges its nblocks sorted lists of m keys, ws[s][block][0..m), into
 // ids, scores [S][n] and counts [S].  Not part of the C ABI.

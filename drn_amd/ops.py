@@ -1623,6 +1623,144 @@ def shortlist_segments_topn_q8(codes, scales, queries, offsets, blk_vid, vid_blk
     return ids, scores, counts, rows
 
 
+def allow_words(V):
+    """The int32 words of one row of a packed allow mask over V videos: ceil(V / 32)."""
+    return -(-int(V) // 32)
+
+
+def pack_allow(mask, words):
+    """mask (V,) or (S, V) bool on the device -> words (W,) or (S, W) int32, W = allow_words(V), written in place, every word: bit
+    v & 31 of word v >> 5 = mask[..., v], zero bits past V (drn_pack_allow; drn_amd.retrieve.pack_allow_reference is the definition).
+    One launch (tag pack_allow); the mask is not read on the host."""
+    _need_gpu(mask, words)
+    if mask.dtype != torch.bool or mask.dim() not in (1, 2) or mask.shape[-1] < 1 or mask.shape[0] < 1 or not mask.is_contiguous():
+        raise _lib.DrnError("pack_allow: the mask must be a contiguous bool tensor (V,) or (S, V) with V >= 1 and S >= 1, not %s %s"
+                            % (mask.dtype, tuple(mask.shape)))
+    V = int(mask.shape[-1])
+    shape = tuple(mask.shape[:-1]) + (allow_words(V),)
+    if words.dtype != torch.int32 or tuple(words.shape) != shape or not words.is_contiguous():
+        raise _lib.DrnError("pack_allow: words must be a contiguous %s torch.int32 tensor" % (shape,))
+    S = 1 if mask.dim() == 1 else int(mask.shape[0])
+    _timed("pack_allow", 0.0, lambda: check(lib().drn_pack_allow(_p(mask), S, V, _p(words), _stream()), "drn_pack_allow"))
+    return words
+
+
+def _allow_stride(what, allow, V, S):
+    """The checks of a packed mask for V videos and S sentences -> allow_stride: 0 for a shared mask (W,), W for one (S, W)."""
+    W = allow_words(V)
+    if allow.dtype != torch.int32 or not allow.is_contiguous() or tuple(allow.shape) not in ((W,), (S, W)):
+        raise _lib.DrnError("%s: allow must be a contiguous torch.int32 tensor (%d,) or (%d, %d) -- ceil(V / 32) packed words a row "
+                            "(drn_amd.retrieve.pack_allow makes them) -- not %s %s" % (what, W, S, W, allow.dtype, tuple(allow.shape)))
+    return 0 if allow.dim() == 1 else W
+
+
+def _shortlist_buffers(what, S, n, need, ws, ids, scores, counts, rows=None):
+    """The checks the shortlist wrappers share: n, the output buffers and the workspace."""
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("%s: n = %d outside [1, %d]" % (what, n, _lib.SHORTLIST_MAX))
+    outs = (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)))
+    if rows is not None:
+        outs += (("rows", rows, torch.int32, (S, n)),)
+    for name, t, dt, shape in outs:
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous %s %s tensor" % (what, name, shape, dt))
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < need:
+        raise _lib.DrnError("%s: ws must be a contiguous int64 tensor of at least %d elements" % (what, need))
+
+
+def _segment_tables(what, offsets, blk_vid, vid_blk):
+    """The checks of a ragged table's device tables -> (V, nblocks)."""
+    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
+        raise _lib.DrnError("%s: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1" % what)
+    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
+    for name, t, shape in (("offsets", offsets, (V + 1,)), ("blk_vid", blk_vid, (nblocks + 1,)), ("vid_blk", vid_blk, (V,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous %s torch.int32 tensor" % (what, name, shape))
+    return V, nblocks
+
+
+def _plain_table(what, emb, queries):
+    """The checks a plain table shares between the two masked shortlists -> (rows, E)."""
+    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
+            or emb.shape[1] != queries.shape[1]:
+        raise _lib.DrnError("%s: emb (rows, E) and queries (S, E) must be contiguous and of one dtype and width" % what)
+    return int(emb.shape[0]), int(emb.shape[1])
+
+
+def shortlist_topn_allow(emb, queries, allow, n, ws, ids, scores, counts):
+    """shortlist_topn over the videos a packed mask allows: allow (W,) -- one mask for every sentence -- or (S, W) int32 on the device,
+    W = allow_words(V), bit v & 31 of word v >> 5 set = video v may be listed, bits past V ignored (drn_shortlist_topn_allow;
+    drn_amd.retrieve.shortlist_reference(..., allow=) is the definition).  A listed score has shortlist_topn's bits; every other argument
+    as there.  Two launches behind one entry (one tag, shortlist_topn_allow); the mask is not read on the host."""
+    what = "shortlist_topn_allow"
+    _need_gpu(emb, queries, allow, ws, ids, scores, counts)
+    n = int(n)
+    V, E = _plain_table(what, emb, queries)
+    S = int(queries.shape[0])
+    _shortlist_buffers(what, S, n, shortlist_ws_keys(V, S, n), ws, ids, scores, counts)
+    stride = _allow_stride(what, allow, V, S)
+    _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_allow(
+        _p(emb), _p(queries), _p(allow), stride, V, E, S, n, dtype_code(emb), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores),
+        _p(counts), _stream()), "drn_shortlist_topn_allow"))
+    return ids, scores, counts
+
+
+def shortlist_segments_topn_allow(emb, queries, offsets, blk_vid, vid_blk, allow, n, ws, ids, scores, counts, rows):
+    """shortlist_segments_topn over the VIDEOS a packed mask allows (not rows): allow (W,) or (S, W) int32, W = allow_words(V), as in
+    shortlist_topn_allow (drn_shortlist_segments_topn_allow; drn_amd.retrieve.segment_shortlist_reference(..., allow=) is the
+    definition).  Every other argument as in shortlist_segments_topn.  Three launches behind one entry (one tag,
+    shortlist_segments_topn_allow); nothing is read on the host."""
+    what = "shortlist_segments_topn_allow"
+    _need_gpu(emb, queries, offsets, blk_vid, vid_blk, allow, ws, ids, scores, counts, rows)
+    n = int(n)
+    R, E = _plain_table(what, emb, queries)
+    S = int(queries.shape[0])
+    V, nblocks = _segment_tables(what, offsets, blk_vid, vid_blk)
+    _shortlist_buffers(what, S, n, shortlist_segments_ws_keys(nblocks, S, n), ws, ids, scores, counts, rows)
+    stride = _allow_stride(what, allow, V, S)
+    _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_allow(
+        _p(emb), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), _p(allow), stride, R, V, nblocks, E, S, n, dtype_code(emb), _p(ws),
+        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn_allow"))
+    return ids, scores, counts, rows
+
+
+def shortlist_topn_q8_allow(codes, scales, queries, allow, n, ws, ids, scores, counts):
+    """shortlist_topn_q8 over the videos a packed mask allows: allow as in shortlist_topn_allow (drn_shortlist_topn_q8_allow).  The
+    result is bit for bit shortlist_topn_allow over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype).  Two launches behind one
+    entry (one tag, shortlist_topn_q8_allow); the mask is not read on the host."""
+    what = "shortlist_topn_q8_allow"
+    _need_gpu(codes, scales, queries, allow, ws, ids, scores, counts)
+    n = int(n)
+    V, E = _q8_table(what, codes, scales, queries)
+    S = int(queries.shape[0])
+    _shortlist_buffers(what, S, n, shortlist_ws_keys(V, S, n), ws, ids, scores, counts)
+    stride = _allow_stride(what, allow, V, S)
+    _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_q8_allow(
+        _p(codes), _p(scales), _p(queries), _p(allow), stride, V, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)),
+        _p(ids), _p(scores), _p(counts), _stream()), "drn_shortlist_topn_q8_allow"))
+    return ids, scores, counts
+
+
+def shortlist_segments_topn_q8_allow(codes, scales, queries, offsets, blk_vid, vid_blk, allow, n, ws, ids, scores, counts, rows):
+    """shortlist_segments_topn_q8 over the VIDEOS a packed mask allows: allow as in shortlist_topn_allow
+    (drn_shortlist_segments_topn_q8_allow).  The result is bit for bit shortlist_segments_topn_allow over
+    drn_amd.index.mx8_dequantize(codes, scales, queries.dtype).  Three launches behind one entry (one tag,
+    shortlist_segments_topn_q8_allow); nothing is read on the host."""
+    what = "shortlist_segments_topn_q8_allow"
+    _need_gpu(codes, scales, queries, offsets, blk_vid, vid_blk, allow, ws, ids, scores, counts, rows)
+    n = int(n)
+    R, E = _q8_table(what, codes, scales, queries)
+    S = int(queries.shape[0])
+    V, nblocks = _segment_tables(what, offsets, blk_vid, vid_blk)
+    _shortlist_buffers(what, S, n, shortlist_segments_ws_keys(nblocks, S, n), ws, ids, scores, counts, rows)
+    stride = _allow_stride(what, allow, V, S)
+    _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_q8_allow(
+        _p(codes), _p(scales), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), _p(allow), stride, R, V, nblocks, E, S, n,
+        dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()),
+        "drn_shortlist_segments_topn_q8_allow"))
+    return ids, scores, counts, rows
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

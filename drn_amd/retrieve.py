@@ -17,8 +17,15 @@ E + E / 32 bytes a row instead of 2 E or 4 E) and rank it with drn_shortlist_top
 (csrc/retrieve_q8.hip).  A dequantised value is exact in bfloat16 and float32, so no new definition is needed: the quantised shortlist IS
 shortlist_reference(mx8_dequantize(codes, scales), queries, n) -- with offsets, segment_shortlist_reference of the same dequantised
 table -- and the kernels answer bit for bit like shortlister.dequantized(), a plain Shortlister over those rows.  Quantising the table
-is lossy against the ORIGINAL embeddings (|dq - x| <= max(|x| / 16, 2^e / 1024) per element); the ranking of what the table holds is not."""
+is lossy against the ORIGINAL embeddings (|dq - x| <= max(|x| / 16, 2^e / 1024) per element); the ranking of what the table holds is not.
+
+shortlist(allow=) FILTERS any of the four tables on the device: a packed mask -- ceil(V / 32) int32 words, one row for all sentences or
+one per sentence, made by pack_allow from a bool tensor or by Shortlister.allow_of from host names or positions -- says which videos a
+sentence may list (a metadata filter, deleted videos, per-user visibility).  A video whose bit is clear is no candidate, exactly like
+one whose score is not finite: shortlist_reference(..., allow=) and segment_shortlist_reference(..., allow=) are the definition, the
+four *_allow entries (csrc/retrieve_allow.hip) the launches, and a listed score has the bits the unfiltered shortlist gives it."""
 import collections
+import numbers
 
 import numpy as np
 import torch
@@ -32,15 +39,26 @@ Shortlist.__doc__ = """ids (S, n) int32 store positions, best first, -1 past the
 length of each sentence's list.  All on the device."""
 
 
-def shortlist_reference(embeddings, queries, n):
+def _allowed(allow, S, V, device):
+    """A reference's allow= -> a bool tensor that broadcasts against (S, V): (V,) is shared by all sentences, (S, V) has a row each."""
+    if not torch.is_tensor(allow) or allow.dtype != torch.bool or tuple(allow.shape) not in ((V,), (S, V)):
+        raise DrnError("allow must be a bool tensor (%d,) or (%d, %d): one entry per video, shared or per sentence" % (V, S, V))
+    return allow.to(device)
+
+
+def shortlist_reference(embeddings, queries, n, allow=None):
     """THE DEFINITION of a shortlist, in float64 (usable on the CPU): score[s, v] = sum_e queries[s, e] * embeddings[v, e]; sentence s
     lists the videos whose score is finite, ordered by higher score, then lower position, cut to n.  Past the list ids = -1 and
-    scores = 0; n[s] is its length (a NaN query row lists nothing).  -> Shortlist on the inputs' device, scores rounded to float32."""
+    scores = 0; n[s] is its length (a NaN query row lists nothing).  allow: a bool tensor (V,), shared by all sentences, or (S, V), one
+    row per sentence: a video with allow == False is no candidate for that sentence, exactly like one whose score is not finite (its
+    score, NaN or the best, changes nothing for the others).  -> Shortlist on the inputs' device, scores rounded to float32."""
     n = int(n)
     emb, q = embeddings.double(), queries.double()
     V, S = int(emb.shape[0]), int(q.shape[0])
     score = q @ emb.t()
     finite = torch.isfinite(score)
+    if allow is not None:
+        finite = finite & _allowed(allow, S, V, emb.device)
     key = torch.where(finite, score, torch.full_like(score, float("-inf")))
     # a stable sort by descending score keeps equal scores in position order
     order = torch.sort(key, dim=1, descending=True, stable=True).indices
@@ -114,13 +132,14 @@ def plan_segment_blocks(offsets, max_videos=SHORTLIST_SEG_BLOCK, row_target=SEGM
     return SegmentPlan(blk_vid, vid_blk)
 
 
-def segment_shortlist_reference(embeddings, offsets, queries, n):
+def segment_shortlist_reference(embeddings, offsets, queries, n, allow=None):
     """THE DEFINITION of a segmented shortlist, in float64 (usable on the CPU).  embeddings (R, E), queries (S, E); offsets: V + 1
     non-decreasing integers from 0 to R, video v owning the rows offsets[v] .. offsets[v + 1] - 1, row r being segment r - offsets[v]
     of its video.  score[s, v] = the maximum over v's rows of sum_e queries[s, e] * embeddings[r, e] (a NaN among them makes it NaN);
     rows[s, v] = the lowest segment number that reaches it.  Sentence s lists the videos that own a row and whose score is finite,
     ordered by higher score, then lower position, cut to n.  Past the list ids = -1, scores = 0 and rows = -1; n[s] is its length (a NaN
-    query row lists nothing).  -> SegmentShortlist on the inputs' device, scores rounded to float32."""
+    query row lists nothing).  allow: as in shortlist_reference, a bool tensor (V,) or (S, V) over VIDEOS, not rows: a video with
+    allow == False is no candidate for that sentence.  -> SegmentShortlist on the inputs' device, scores rounded to float32."""
     n = int(n)
     emb, q = embeddings.double(), queries.double()
     dev = emb.device
@@ -141,6 +160,8 @@ def segment_shortlist_reference(embeddings, offsets, queries, n):
     rows = torch.full((S, V), R, dtype=torch.int64, device=dev).scatter_reduce(
         1, index, torch.where(reaches, segment[None, :].expand(S, R), torch.full_like(index, R)), "amin", include_self=True)
     finite = torch.isfinite(score) & (lens > 0)[None, :]
+    if allow is not None:
+        finite = finite & _allowed(allow, S, V, dev)
     key = torch.where(finite, score, torch.full_like(score, float("-inf")))
     # a stable sort by descending score keeps equal scores in position order
     order = torch.sort(key, dim=1, descending=True, stable=True).indices
@@ -154,6 +175,38 @@ def segment_shortlist_reference(embeddings, offsets, queries, n):
     scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
     segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order[:, :m]).to(torch.int32), segs[:, :m])
     return SegmentShortlist(ids, scores, count.to(torch.int32), segs)
+
+
+def pack_allow_reference(mask):
+    """THE DEFINITION of a packed allow mask, in numpy: mask (V,) or (S, V) of booleans (an array, a sequence or a host tensor) -> int32
+    words (W,) or (S, W), W = ceil(V / 32): bit v & 31 of word v >> 5 is mask[..., v], the bits at or past V are zero."""
+    m = np.asarray(mask.detach().cpu().numpy() if torch.is_tensor(mask) else mask)
+    if m.dtype != np.bool_ or m.ndim not in (1, 2) or m.shape[-1] < 1 or m.shape[0] < 1:
+        raise DrnError("pack_allow_reference: the mask must be booleans (V,) or (S, V) with V >= 1 and S >= 1, not %s %s" % (m.dtype, m.shape))
+    V = m.shape[-1]
+    W = ops.allow_words(V)
+    padded = np.zeros(m.shape[:-1] + (32 * W,), dtype=np.bool_)
+    padded[..., :V] = m
+    return np.ascontiguousarray(np.packbits(padded, axis=-1, bitorder="little")).view("<u4").astype(np.uint32).view(np.int32)
+
+
+def pack_allow(mask, out=None):
+    """mask: a contiguous bool tensor (V,) or (S, V) ON THE DEVICE -> the packed mask shortlist(allow=) takes, int32 (W,) or (S, W) with
+    W = ceil(V / 32), on the device (pack_allow_reference defines it).  ONE launch on the current stream, no host synchronisation, and
+    it can be captured in a graph: a filter computed on the device never leaves it.  out: written in place, every word, with zero bits
+    past V, and returned."""
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise DrnError("pack_allow: the mask must be a tensor on the GPU; there is no CPU fallback (Shortlister.allow_of packs host lists)")
+    if mask.dtype != torch.bool or mask.dim() not in (1, 2) or mask.shape[-1] < 1 or mask.shape[0] < 1 or not mask.is_contiguous():
+        raise DrnError("pack_allow: the mask must be a contiguous bool tensor (V,) or (S, V) with V >= 1 and S >= 1, not %s %s"
+                       % (mask.dtype, tuple(mask.shape)))
+    shape = tuple(mask.shape[:-1]) + (ops.allow_words(mask.shape[-1]),)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=mask.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.device != mask.device or out.dtype != torch.int32 or tuple(out.shape) != shape \
+            or not out.is_contiguous():
+        raise DrnError("pack_allow: out must be a contiguous %s torch.int32 tensor on the mask's device" % (shape,))
+    return ops.pack_allow(mask, out)
 
 
 def quantized_score_bound(embeddings, scales, queries):
@@ -344,6 +397,58 @@ class Shortlister(object):
         if self.names is None or self.names != list(store.names):
             raise DrnError("Shortlister: the table's names are not the store's (row v must belong to store position v)")
 
+    def allow_of(self, keep=None, drop=None):
+        """HOST names or store positions -> a packed mask on the table's device, (W,) int32, shared by all sentences: what
+        shortlist(allow=) takes.  Exactly one of keep / drop is given: keep=[...] allows those videos alone, drop=[...] -- the
+        tombstone list of videos deleted since the table was built -- all the others.  An entry is a name, resolved through
+        self.names, or a position in [0, V); an unknown name, a position outside the table or an entry that is neither raises.
+        Packed on the host (pack_allow_reference) and put on the device in ONE upload from pinned memory."""
+        if (keep is None) == (drop is None):
+            raise DrnError("Shortlister.allow_of: exactly one of keep= and drop= must be given")
+        V = len(self)
+        mask = np.zeros(V, dtype=np.bool_) if drop is None else np.ones(V, dtype=np.bool_)
+        where = None
+        for item in (keep if drop is None else drop):
+            if isinstance(item, str):
+                if self.names is None:
+                    raise DrnError("Shortlister.allow_of: %r is a name and this table has no names" % (item,))
+                if where is None:
+                    where = {name: v for v, name in enumerate(self.names)}
+                if item not in where:
+                    raise DrnError("Shortlister.allow_of: no video named %r in this table" % (item,))
+                v = where[item]
+            elif isinstance(item, (numbers.Integral, np.integer)) and not isinstance(item, (bool, np.bool_)):
+                v = int(item)
+                if not 0 <= v < V:
+                    raise DrnError("Shortlister.allow_of: position %d outside [0, %d)" % (v, V))
+            else:
+                raise DrnError("Shortlister.allow_of: an entry must be a name or a position, not %r" % (item,))
+            mask[v] = drop is None
+        words = torch.from_numpy(pack_allow_reference(mask))
+        dev = self._table().device
+        if dev.type != "cuda":                    # (a table that is not on a GPU can be asked for its mask, never for a shortlist)
+            return words
+        return words.pin_memory().to(dev, non_blocking=True)
+
+    def _check_allow(self, allow, S):
+        """The refusals of shortlist(allow=), before the library is reached."""
+        V, dev = len(self), self._table().device
+        W = ops.allow_words(V)
+        if not torch.is_tensor(allow):
+            raise DrnError("Shortlister.shortlist: allow must be a packed mask, a tensor (pack_allow or allow_of makes one)")
+        if allow.dtype == torch.bool:
+            raise DrnError("Shortlister.shortlist: allow is a bool tensor; pack it first -- allow=pack_allow(mask) -- into ceil(V / 32) "
+                           "int32 words a row")
+        if allow.dtype != torch.int32:
+            raise DrnError("Shortlister.shortlist: allow must be torch.int32 packed words (pack_allow makes them), not %s" % allow.dtype)
+        if not allow.is_cuda or allow.device != dev:
+            raise DrnError("Shortlister.shortlist: allow must be on the table's device %s, not %s" % (dev, allow.device))
+        if tuple(allow.shape) not in ((W,), (S, W)):
+            raise DrnError("Shortlister.shortlist: allow must be (%d,) -- one mask for all sentences -- or (%d, %d), ceil(V / 32) words a "
+                           "row for V = %d videos, not %s" % (W, S, W, V, tuple(allow.shape)))
+        if not allow.is_contiguous():
+            raise DrnError("Shortlister.shortlist: allow must be contiguous")
+
     def _check(self, queries, n, out):
         """shortlist's refusals, before the library is reached -> (S, n)."""
         E, dtype = self.E, self.dtype
@@ -373,7 +478,7 @@ class Shortlister(object):
                     raise DrnError("Shortlister.shortlist: out.%s must be a contiguous %s %s tensor on the GPU" % (name, shape, dt))
         return S, n
 
-    def shortlist(self, queries, n, out=None):
+    def shortlist(self, queries, n, out=None, allow=None):
         """queries (S, E) on the device in the table's dtype, 1 <= n <= SHORTLIST_MAX -> Shortlist (shortlist_reference defines it),
         on the device.  out: a Shortlist (or 3-tuple) of buffers written in place, every element, and returned.  Runs on the current
         stream without a host synchronisation and can be captured in a graph (the workspace is kept per (S, n): warm the shape once
@@ -387,8 +492,18 @@ class Shortlister(object):
         On a quantised table (quantize="mxfp8", from_mx8) the queries have the recorded dtype and the definition is
         shortlist_reference(mx8_dequantize(codes, scales), queries, n) -- with offsets, segment_shortlist_reference of the same
         dequantised table: the result types, the order, the padding, rows, out= and graph capture are unchanged, and every field is
-        bit for bit what dequantized().shortlist(queries, n) gives."""
+        bit for bit what dequantized().shortlist(queries, n) gives.
+
+        allow: a PACKED MASK on the table's device -- contiguous int32 (W,), shared by all sentences, or (S, W), one row per sentence,
+        W = ceil(V / 32), bit v & 31 of word v >> 5 set = video v may be listed, bits at or past V ignored; pack_allow makes one from a
+        bool tensor on the device, allow_of from host names or positions (a bool tensor itself is refused).  The list is then the
+        definition with allow= applied -- shortlist_reference(..., allow=mask), segment_shortlist_reference(..., allow=mask), over
+        videos, not rows -- on all four tables, with out=, without a host synchronisation and under graph capture, where the mask's
+        CONTENTS may change in place between replays.  A listed score has the bits the unfiltered shortlist gives it.  allow=None is
+        the unfiltered path, entry and bits."""
         S, n = self._check(queries, n, out)
+        if allow is not None:
+            self._check_allow(allow, S)
         dev = self._table().device
         q8 = self.quantize is not None
         seg = getattr(self, "_seg", None)
@@ -402,14 +517,22 @@ class Shortlister(object):
             if ws is None:
                 keys = ops.shortlist_segments_ws_keys(int(seg[1].shape[0]) - 1, S, n)
                 ws = self._ws[(S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
-            if q8:
+            if allow is not None and q8:
+                ops.shortlist_segments_topn_q8_allow(self.codes, self.scales, queries.contiguous(), seg[0], seg[1], seg[2], allow, n, ws, *out)
+            elif allow is not None:
+                ops.shortlist_segments_topn_allow(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], allow, n, ws, *out)
+            elif q8:
                 ops.shortlist_segments_topn_q8(self.codes, self.scales, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
             else:
                 ops.shortlist_segments_topn(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
             return SegmentShortlist(*out)
         if ws is None:
             ws = self._ws[(S, n)] = torch.empty(ops.shortlist_ws_keys(len(self), S, n), dtype=torch.int64, device=dev)
-        if q8:
+        if allow is not None and q8:
+            ops.shortlist_topn_q8_allow(self.codes, self.scales, queries.contiguous(), allow, n, ws, *out)
+        elif allow is not None:
+            ops.shortlist_topn_allow(self.embeddings, queries.contiguous(), allow, n, ws, *out)
+        elif q8:
             ops.shortlist_topn_q8(self.codes, self.scales, queries.contiguous(), n, ws, *out)
         else:
             ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)

@@ -685,6 +685,31 @@ int drn_shortlist_topn_q8(const uint8_t* codes, const uint8_t* scales, const voi
 int drn_shortlist_segments_topn_q8(const uint8_t* codes, const uint8_t* scales, const void* queries, const int32_t* offsets,
                                    const int32_t* blk_vid, const int32_t* vid_blk, int R, int V, int nblocks, int E, int S, int n, int dtype,
                                    void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
+/* The four shortlist entries above with a packed ALLOW MASK (drn_amd/csrc/retrieve_allow.hip): each takes its twin's arguments plus
+ * allow and allow_stride.  A packed mask is W = ceil(V / 32) int32 words a row on the device, 4-byte aligned: bit v & 31 of word v >> 5
+ * set = video v may be listed; bits at or past V are ignored.  allow_stride = 0: allow [W], one mask for every sentence; allow_stride =
+ * W: allow [S][W], row s for sentence s; any other stride is refused.  A video whose bit is clear is no candidate for that sentence,
+ * exactly like a video whose score is not finite: the list is the twin's definition applied to the allowed videos (on a ragged table
+ * the mask is over VIDEOS, not rows), and a listed score has the bits the twin gives it -- the same MFMA chain.  Everything else -- the
+ * order, the padding, the workspace and its size, the block plan, the clamps, the checks, the launches (two and three) -- is the twin's.
+ * A workgroup whose block holds no allowed video for any sentence of its tile reads no row of the table.  The mask is not read on the
+ * host; its contents may change between replays of a captured graph. */
+int drn_shortlist_topn_allow(const void* emb, const void* queries, const int32_t* allow, int allow_stride, int V, int E, int S, int n,
+                             int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, void* stream);
+int drn_shortlist_segments_topn_allow(const void* emb, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
+                                      const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S,
+                                      int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows,
+                                      void* stream);
+int drn_shortlist_topn_q8_allow(const uint8_t* codes, const uint8_t* scales, const void* queries, const int32_t* allow, int allow_stride,
+                                int V, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts,
+                                void* stream);
+int drn_shortlist_segments_topn_q8_allow(const uint8_t* codes, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                         const int32_t* blk_vid, const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V,
+                                         int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
+                                         int32_t* counts, int32_t* rows, void* stream);
+/* mask [S][V], one byte a video (a torch.bool tensor: non-zero = allowed) -> words [S][ceil(V / 32)], the packed mask above: every
+ * word written, bits at or past V zero.  S = 1 packs a mask shared by all sentences.  One launch, nothing read back. */
+int drn_pack_allow(const uint8_t* mask, int S, int V, int32_t* words, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

@@ -76,7 +76,18 @@
            floor; the bytes of both tables (asserted equal to Shortlister.bytes_of); the time to quantise the table; whether the two
            answers are the same bits; the tolerance_ratio of tests/test_q8_shortlist_gpu.py's lossy case; and, on the random table, the
            share of sentences whose first video and whose n-list agree with those of the ORIGINAL unquantised table.  Random
-           embeddings: nothing here says anything about recall."""
+           embeddings: nothing here says anything about recall.
+
+  --filtered-shortlist  instead of the above -> profiles/search_filtered_shortlist_bench.json: Shortlister.shortlist(allow=) on R =
+           65,536 rows x 512 (bf16 queries, n = 16, S in {1, 8, 64}; the plain table as 65,536 x 1, the ragged one as 4,096 x 16, the
+           quantised plain table at S = 8), launch-inclusive us, median [min, max] of 5 interleaved rounds in one process, under five
+           masks -- all ones, random 50 %, random 1 %, a contiguous 1/16 of the videos (15/16 of the blocks dark), a per-sentence random
+           1 % -- beside (a) the unmasked launch on the same table, the parent's code unchanged, and (b), for the shared masks, the
+           parent's only exact way: Shortlister(emb[keep].contiguous()), shortlist, keep[ids], with and without the construction.
+           Two conditions are derived, not measured, and reported shape by shape: (C1) the all-ones mask costs the unmasked launch plus
+           at most 128 (144 ragged) mask words per workgroup -- the difference against (a) is printed, in capitals where it exceeds (a)'s
+           max - min; (C2) the contiguous-1/16 and the 1 % mask do no more work than the all-ones mask and may not take longer than it
+           beyond its max - min.  Random embeddings: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1407,10 +1418,124 @@ def main_q8_shortlist(args):
     print("wrote", out)
 
 
+FILTER_SHAPES = [("65536x1", [1] * 65536, None, S) for S in (1, 8, 64)] + [("4096x16", [16] * 4096, None, S) for S in (1, 8, 64)] \
+    + [("65536x1", [1] * 65536, "mxfp8", 8)]
+FILTER_MASKS = ("ones", "half", "one_pct", "sixteenth", "per_sentence_one_pct")
+
+
+def bench_filtered_shortlist(name, lens, quantize, emb, S, n, rounds):
+    """shortlist(allow=) under the five masks beside (a) the unmasked launch on the same table and (b) for the shared masks the
+    sub-table way -- gather the kept rows, build a Shortlister over them, shortlist, map the ids back -- with and without the
+    construction; the masked all-ones list against the unmasked one and every shared masked list against the sub-table's, bit for bit."""
+    import numpy as np
+    from drn_amd import Shortlister, pack_allow
+    dev = "cuda:0"
+    R, V = int(emb.shape[0]), len(lens)
+    lens_np = np.asarray(lens, dtype=np.int64)
+    off = None if V == R else np.concatenate([[0], np.cumsum(lens_np)])
+    g = torch.Generator(device=dev).manual_seed(S + n)
+    q = torch.randn(S, 512, generator=g, device=dev).to(torch.bfloat16).contiguous()
+    sl = Shortlister(emb, offsets=off, quantize=quantize)
+    lens_dev = torch.as_tensor(lens_np, device=dev)
+    sixteenth = torch.zeros(V, dtype=torch.bool, device=dev)
+    sixteenth[5 * V // 16:6 * V // 16] = True
+    masks = {"ones": torch.ones(V, dtype=torch.bool, device=dev), "half": torch.rand(V, generator=g, device=dev) < 0.5,
+             "one_pct": torch.rand(V, generator=g, device=dev) < 0.01, "sixteenth": sixteenth,
+             "per_sentence_one_pct": torch.rand(S, V, generator=g, device=dev) < 0.01}
+    assert tuple(masks) == FILTER_MASKS
+    words = {k: pack_allow(m.contiguous()) for k, m in masks.items()}
+    outs = {k: sl.shortlist(q, n, allow=w) for k, w in words.items()}
+    out_plain = sl.shortlist(q, n)
+
+    def sub_table(mask):
+        keep = torch.nonzero(mask)[:, 0]
+        if off is None:
+            return Shortlister(emb[keep].contiguous(), quantize=quantize), keep
+        sub_off = np.concatenate([[0], np.cumsum(lens_np[keep.cpu().numpy()])])
+        return Shortlister(emb[torch.repeat_interleave(mask, lens_dev)].contiguous(), offsets=sub_off, quantize=quantize), keep
+
+    def via(sub, keep, out=None):
+        got = sub.shortlist(q, n, out=out)
+        return got, torch.where(got.ids >= 0, keep[got.ids.clamp(min=0).long()].to(torch.int32), got.ids)
+    variants = {"unmasked": lambda: sl.shortlist(q, n, out=out_plain)}
+    for k in FILTER_MASKS:
+        variants[k] = lambda k=k: sl.shortlist(q, n, out=outs[k], allow=words[k])
+    same = {"ones_equals_unmasked_bit_for_bit": all(torch.equal(a, b) for a, b in zip(outs["ones"], out_plain))}
+    shared = ("half", "one_pct", "sixteenth")
+    for k in shared:
+        sub, keep = sub_table(masks[k])
+        got, ids = via(sub, keep)
+        same[k + "_equals_sub_table_bit_for_bit"] = bool(torch.equal(ids, outs[k].ids) and torch.equal(got.scores, outs[k].scores)
+                                                         and torch.equal(got.n, outs[k].n))
+        variants["sub_table_" + k] = lambda sub=sub, keep=keep, out=got: via(sub, keep, out)
+        variants["sub_table_built_" + k] = lambda k=k: via(*sub_table(masks[k]))
+    times, reps = interleaved_windows(variants, rounds)
+    med = {k: statistics.median(ts) for k, ts in times.items()}
+    width = lambda ts: max(ts) - min(ts)
+    row = {"layout": name, "quantize": quantize, "R": R, "V": V, "E": 512, "S": S, "n": n, "dtype": "bf16",
+           "entry": "drn_shortlist_%stopn%s_allow" % ("" if off is None else "segments_", "" if quantize is None else "_q8"),
+           "blocks": -(-V // 256) if off is None else int(sl.plan.blk_vid.shape[0]) - 1, "table_bytes": sl.nbytes, "table_reads": -(-S // 16),
+           "allowed": {k: int(m.sum()) for k, m in masks.items()}, "launches_per_window": reps, "answers": same,
+           "unmasked_us": spread(times["unmasked"]), "masked_us": {}, "sub_table_us": {},
+           "read_floor_us_at_6.29TB/s": -(-S // 16) * sl.nbytes / HBM_COPY_BYTES_PER_S * 1e6}
+    for k in FILTER_MASKS:
+        row["masked_us"][k] = dict(spread(times[k]), over_unmasked=med[k] / med["unmasked"], against_unmasked=verdict(times[k], times["unmasked"]))
+    for k in shared:
+        a, b = times["sub_table_" + k], times["sub_table_built_" + k]
+        row["sub_table_us"][k] = {"shortlist_and_remap": spread(a), "with_construction": spread(b),
+                                  "masked_over_shortlist_and_remap": med[k] / statistics.median(a), "masked_against_shortlist_and_remap": verdict(times[k], a),
+                                  "masked_over_with_construction": med[k] / statistics.median(b), "masked_against_with_construction": verdict(times[k], b)}
+    d = med["ones"] - med["unmasked"]
+    row["C1"] = {"ones_minus_unmasked_median_us": d, "unmasked_max_minus_min_us": width(times["unmasked"]), "holds": d <= width(times["unmasked"]),
+                 "says": "inside the unmasked launch's own spread" if d <= width(times["unmasked"])
+                 else "THE ALL-ONES MASK IS SLOWER THAN THE UNMASKED LAUNCH BY MORE THAN ITS max - min"}
+    row["C2"] = {}
+    for k in ("sixteenth", "one_pct"):
+        d = med[k] - med["ones"]
+        row["C2"][k] = {"median_minus_ones_median_us": d, "ones_max_minus_min_us": width(times["ones"]), "holds": d <= width(times["ones"]),
+                        "says": "no longer than the all-ones mask beyond its spread" if d <= width(times["ones"])
+                        else "SLOWER THAN THE ALL-ONES MASK BY MORE THAN ITS max - min"}
+    row["note"] = ("launch-inclusive, every launch of the entry; the sub-table way gathers the kept rows, builds a Shortlister over them (one "
+                   "synchronise and a finiteness pass; a ragged table also rebuilds its offsets on the host), shortlists and maps the ids "
+                   "back; its construction is timed inside the same event windows")
+    return row
+
+
+def main_filtered_shortlist(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_filtered_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the tables resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "(a) unmasked: the parent's entry on the same table, its code unchanged; (b) sub_table: the parent's only "
+                                   "exact way for a shared mask, Shortlister(emb[keep].contiguous()) + shortlist + keep[ids], with and "
+                                   "without the construction.  A difference inside the baseline's own max - min is NO DIFFERENCE",
+                      "conditions": "derived, not measured: (C1) the all-ones mask does the unmasked launch's work plus at most 128 (ragged: "
+                                    "144) mask words per workgroup; (C2) on one table the contiguous-1/16 and the 1 % mask do no more work than "
+                                    "the all-ones mask and may not take longer than it beyond ITS max - min",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall; pack_allow and allow_of are not "
+                                                "timed; no kernel-only times (no profiler run); n = 16 only"},
+           "masks": {"ones": "every video", "half": "random 50 %", "one_pct": "random 1 %",
+                     "sixteenth": "the videos [5 V / 16, 6 V / 16): 15/16 of the blocks dark", "per_sentence_one_pct": "a random 1 % per sentence, (S, W)"},
+           "filtered_shortlist": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for name, lens, quantize, S in FILTER_SHAPES:
+        row = bench_filtered_shortlist(name, lens, quantize, emb, S, 16, args.rounds)
+        res["filtered_shortlist"].append(row)
+        print(json.dumps({"filtered_shortlist": row}), flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
-                                            "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist)")
+                                            "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
+                                            "search_filtered_shortlist_bench.json with --filtered-shortlist)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1426,9 +1551,13 @@ def main():
                                                                      "beside the plain kernel on the same rows and matmul + amax + topk")
     ap.add_argument("--quantized-shortlist", action="store_true", help="measure Shortlister(quantize=\"mxfp8\").shortlist on 65,536 rows in three "
                                                                        "layouts beside the plain table over the same dequantised rows")
+    ap.add_argument("--filtered-shortlist", action="store_true", help="measure Shortlister.shortlist(allow=) under five masks beside the unmasked "
+                                                                      "launch and the sub-table way")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.filtered_shortlist:
+        return main_filtered_shortlist(args)
     if args.quantized_shortlist:
         return main_q8_shortlist(args)
     if args.segment_shortlist:
