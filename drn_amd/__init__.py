@@ -7,5 +7,5 @@ from .grounding import Grounder, Hits, Moments, group_by_video, plan_candidate_s
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
 from .index import SearchIndex  # noqa: E402,F401
 from .search_eval import SearchRecall, evaluate_search, search_batches  # noqa: E402,F401
-from .retrieve import (SegmentShortlist, Shortlist, Shortlister, pack_allow, pack_allow_reference, plan_segment_blocks,  # noqa: E402,F401
-                       segment_shortlist_reference, shortlist_reference)
+from .retrieve import (LATE_MAX_TOKENS, SegmentShortlist, Shortlist, Shortlister, late_shortlist_reference, pack_allow,  # noqa: E402,F401
+                       pack_allow_reference, plan_segment_blocks, segment_shortlist_reference, shortlist_reference)

@@ -23,6 +23,7 @@ MERGE_MAX_CAND = 2048     # DRN_MERGE_MAX_CAND: K + Vc * kv candidates one drn_m
 SHORTLIST_MAX = 128       # DRN_SHORTLIST_MAX: the longest list drn_shortlist_topn returns (a choice, not a measurement)
 SHORTLIST_BLOCK = 256     # videos one workgroup of drn_shortlist_topn's first launch ranks (its workspace is sized by it)
 SHORTLIST_SEG_BLOCK = 256  # videos of one block of drn_shortlist_segments_topn's plan at most, and rows of one pass (SG_BLOCK)
+LATE_MAX_TOKENS = 64      # DRN_LATE_MAX_TOKENS: token vectors of one sentence of drn_shortlist_late_topn (a choice that bounds a workgroup's time)
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 
 
@@ -190,6 +191,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_segments_topn_q8_allow": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_late_topn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_late_topn_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_pack_allow": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }

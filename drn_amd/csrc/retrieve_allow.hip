@@ -15,7 +15,7 @@
 // the list is the unmasked definition applied to the allowed videos.  The scores come from the chain of the unmasked kernels -- the
 // same fragments, the same K-steps in ascending order, the same sl_mfma -- so a listed score has the bits those kernels give it.
 //
-// Phase one is TWO kernel bodies, the ranked block and the ranked segment block, templated on the TABLE OPERAND: AlPlain<T> loads a
+// Phase one is TWO kernel bodies, the ranked block and the ranked segment block, templated on the TABLE OPERAND (shortlist.h): AlPlain<T> loads a
 // row's fragments (sl_frag / sl_frag_tail), AlQ8<T, NB> builds them from codes and scale bytes (sq_scores: sl_codes_q8 / sl_frag_q8,
 // NB scale blocks of loads in flight as in retrieve_q8.hip: two in the ranked block's bf16 chain, one elsewhere).
 //
@@ -29,55 +29,6 @@
 #define AL_LD (AL_BLOCK + 1)
 #define AL_WORDS 8          // mask words of a ranked block: AL_BLOCK / 32
 #define AL_SEG_WORDS 9      // of a ragged block, which starts at any video
-
-template <typename T>
-struct AlPlain {
-  typedef T Q;
-  const T* emb;
-  // acc[j] += q[16 sentences] x the rows row[j] (j = 0..3): shortlist_block_kernel's chain (retrieve.hip)
-  __device__ __forceinline__ void scores(const T* qrow, const long (&row)[4], const int E, const int g, f32x4 (&acc)[4]) const {
-    constexpr int COLS = SlStep<T>::COLS, PER_LANE = SlStep<T>::PER_LANE;
-    const T* erow[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) erow[j] = emb + row[j] * E;
-    // whole steps on 16-byte loads where every row starts on a 16-byte boundary (the tables are 16-byte aligned), then the rest
-    const int whole = E % PER_LANE == 0 ? E / COLS * COLS : 0;
-    int c = 0;
-    for (; c < whole; c += COLS) {
-      const int c0 = c + g * PER_LANE;
-      const auto a = sl_frag(qrow, c0);
-      decltype(sl_frag(qrow, c0)) bv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[j] = sl_frag(erow[j], c0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a, bv[j], acc[j]);
-    }
-    for (; c < E; c += COLS) {
-      const int c0 = c + g * PER_LANE;
-      const auto a = sl_frag_tail(qrow, c0, E);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a, sl_frag_tail(erow[j], c0, E), acc[j]);
-    }
-  }
-};
-
-template <typename T, int NB>
-struct AlQ8 {
-  typedef T Q;
-  const uint8_t* codes;
-  const uint8_t* scales;
-  // the same from a block-scaled FP8 table: shortlist_block_q8_kernel's chain (retrieve_q8.hip); E % MX8_BLOCK == 0
-  __device__ __forceinline__ void scores(const T* qrow, const long (&row)[4], const int E, const int g, f32x4 (&acc)[4]) const {
-    const uint8_t* crow[4];
-    const uint8_t* srow[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      crow[j] = codes + row[j] * E;
-      srow[j] = scales + row[j] * (E / MX8_BLOCK);
-    }
-    sq_scores<T, NB>(qrow, crow, srow, E, g, acc);
-  }
-};
 
 // The tile's mask words of the videos [v0, v1) into mw[sentence of the tile][word - (v0 >> 5)], NW words a row, bits outside
 // [v0, v1) cleared, words past the block zero -> does any bit remain (workgroup-uniform; ends in a barrier).  A sentence slot past S

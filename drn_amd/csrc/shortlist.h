@@ -3,6 +3,7 @@
 // host-side launch of the merging kernel, which lives in retrieve.hip and serves both.  retrieve_q8.hip ranks the same two tables kept in
 // block-scaled FP8: its table operand is sl_frag_q8 below, everything after the scores is what is declared here.  retrieve_allow.hip
 // ranks all four under an allow mask: the plain chain, and the FP8 chain sq_scores below, which it shares with retrieve_q8.hip.
+// retrieve_late.hip ranks the ragged tables by late interaction (per-token queries) on the table operands AlPlain / AlQ8 below.
 #pragma once
 #include "common.h"
 #include "mx8.h"
@@ -126,6 +127,57 @@ __device__ __forceinline__ void sq_scores(const T* qrow, const uint8_t* const (&
   for (; c + NB * MX8_BLOCK <= E; c += NB * MX8_BLOCK) sq_blocks<T, NB>(qrow, crow, srow, c, g, acc);
   if (NB > 1 && c < E) sq_blocks<T, 1>(qrow, crow, srow, c, g, acc);      // (an odd number of blocks)
 }
+
+// THE TABLE OPERAND of the kernels that are templated on it (retrieve_allow.hip, retrieve_late.hip): AlPlain<T> loads a row's fragments
+// (sl_frag / sl_frag_tail), AlQ8<T, NB> builds them from codes and scale bytes (sq_scores).  Either runs the chain of the kernel it names.
+template <typename T>
+struct AlPlain {
+  typedef T Q;
+  const T* emb;
+  // acc[j] += q[16 sentences] x the rows row[j] (j = 0..3): shortlist_block_kernel's chain (retrieve.hip)
+  __device__ __forceinline__ void scores(const T* qrow, const long (&row)[4], const int E, const int g, f32x4 (&acc)[4]) const {
+    constexpr int COLS = SlStep<T>::COLS, PER_LANE = SlStep<T>::PER_LANE;
+    const T* erow[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) erow[j] = emb + row[j] * E;
+    // whole steps on 16-byte loads where every row starts on a 16-byte boundary (the tables are 16-byte aligned), then the rest
+    const int whole = E % PER_LANE == 0 ? E / COLS * COLS : 0;
+    int c = 0;
+    for (; c < whole; c += COLS) {
+      const int c0 = c + g * PER_LANE;
+      const auto a = sl_frag(qrow, c0);
+      decltype(sl_frag(qrow, c0)) bv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[j] = sl_frag(erow[j], c0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a, bv[j], acc[j]);
+    }
+    for (; c < E; c += COLS) {
+      const int c0 = c + g * PER_LANE;
+      const auto a = sl_frag_tail(qrow, c0, E);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = sl_mfma(a, sl_frag_tail(erow[j], c0, E), acc[j]);
+    }
+  }
+};
+
+template <typename T, int NB>
+struct AlQ8 {
+  typedef T Q;
+  const uint8_t* codes;
+  const uint8_t* scales;
+  // the same from a block-scaled FP8 table: shortlist_block_q8_kernel's chain (retrieve_q8.hip); E % MX8_BLOCK == 0
+  __device__ __forceinline__ void scores(const T* qrow, const long (&row)[4], const int E, const int g, f32x4 (&acc)[4]) const {
+    const uint8_t* crow[4];
+    const uint8_t* srow[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      crow[j] = codes + row[j] * E;
+      srow[j] = scales + row[j] * (E / MX8_BLOCK);
+    }
+    sq_scores<T, NB>(qrow, crow, srow, E, g, acc);
+  }
+};
 
 // shortlist_merge_kernel (retrieve.hip) on `stream`: sentence s merges its nblocks sorted lists of m keys, ws[s][block][0..m), into
 // ids, scores [S][n] and counts [S].  Not part of the C ABI.

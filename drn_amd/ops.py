@@ -1761,6 +1761,54 @@ def shortlist_segments_topn_q8_allow(codes, scales, queries, offsets, blk_vid, v
     return ids, scores, counts, rows
 
 
+def shortlist_late_ws_keys(nblocks, S, n):
+    """The 8-byte keys of workspace drn_shortlist_late_topn needs: S * nblocks * min(n, SHORTLIST_SEG_BLOCK)."""
+    return int(S) * int(nblocks) * min(int(n), _lib.SHORTLIST_SEG_BLOCK)
+
+
+def shortlist_late_topn(table, queries, lengths, offsets, blk_vid, n, ws, ids, scores, counts, allow=None):
+    """The shortlist by late interaction over a ragged table: table is emb (R, E), float32 / bfloat16, or a pair (codes, scales) of a
+    block-scaled FP8 table (codes (R, E) and scales (R, E / 32) uint8, E % 32 == 0); queries (S, L, E) of the table's dtype (float32 /
+    bfloat16 beside codes), 1 <= L <= LATE_MAX_TOKENS; lengths (S,) int32 on the device, the live tokens of each sentence, clamped into
+    [0, L] there; offsets (V + 1,) and blk_vid (nblocks + 1,) int32 on the device as in shortlist_segments_topn -> ids, scores (S, n)
+    and counts (S,), written in place: each sentence's best n videos by the sum over its live tokens of the video's best row
+    (drn_shortlist_late_topn / drn_shortlist_late_topn_q8; drn_amd.retrieve.late_shortlist_reference is the definition).  allow: None, or
+    a packed mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_late_ws_keys(nblocks, S, n) elements.  Two
+    launches on the current stream behind one entry (one tag, shortlist_late_topn); nothing is read on the host."""
+    what = "shortlist_late_topn"
+    q8 = isinstance(table, (tuple, list))
+    _need_gpu(*((tuple(table) if q8 else (table,)) + (queries, lengths, offsets, blk_vid, ws, ids, scores, counts)
+                + (() if allow is None else (allow,))))
+    n = int(n)
+    if queries.dim() != 3 or not queries.is_contiguous() or not 1 <= queries.shape[1] <= _lib.LATE_MAX_TOKENS:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, L, E) tensor with 1 <= L <= %d, not %s"
+                            % (what, _lib.LATE_MAX_TOKENS, tuple(queries.shape)))
+    S, L = int(queries.shape[0]), int(queries.shape[1])
+    flat = queries.view(S * L, -1)
+    R, E = _q8_table(what, table[0], table[1], flat) if q8 else _plain_table(what, table, flat)
+    if S < 1:
+        raise _lib.DrnError("%s: queries must hold a sentence at least, not %s" % (what, tuple(queries.shape)))
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
+        raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
+    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
+        raise _lib.DrnError("%s: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1" % what)
+    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
+    for name, t in (("offsets", offsets), ("blk_vid", blk_vid)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous torch.int32 tensor" % (what, name))
+    _shortlist_buffers(what, S, n, shortlist_late_ws_keys(nblocks, S, n), ws, ids, scores, counts)
+    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
+    mask = None if allow is None else _p(allow)
+    tail = (_p(queries), _p(lengths), _p(offsets), _p(blk_vid), mask, stride, R, V, nblocks, E, S, L, n, dtype_code(queries), _p(ws),
+            int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _stream())
+    if q8:
+        launch = lambda: check(lib().drn_shortlist_late_topn_q8(_p(table[0]), _p(table[1]), *tail), "drn_shortlist_late_topn_q8")
+    else:
+        launch = lambda: check(lib().drn_shortlist_late_topn(_p(table), *tail), "drn_shortlist_late_topn")
+    _timed(what, 2.0 * S * L * R * E, launch)
+    return ids, scores, counts
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -23,7 +23,12 @@ shortlist(allow=) FILTERS any of the four tables on the device: a packed mask --
 one per sentence, made by pack_allow from a bool tensor or by Shortlister.allow_of from host names or positions -- says which videos a
 sentence may list (a metadata filter, deleted videos, per-user visibility).  A video whose bit is clear is no candidate, exactly like
 one whose score is not finite: shortlist_reference(..., allow=) and segment_shortlist_reference(..., allow=) are the definition, the
-four *_allow entries (csrc/retrieve_allow.hip) the launches, and a listed score has the bits the unfiltered shortlist gives it."""
+four *_allow entries (csrc/retrieve_allow.hip) the launches, and a listed score has the bits the unfiltered shortlist gives it.
+
+Shortlister.shortlist_late takes the QUERY side multi-vector too (late interaction, as token-level dual encoders score): queries
+(S, L, E), one vector per token, lengths (S,) on the device saying how many are live, and a video's score is the sum over the live
+tokens of the token's best row of the video.  late_shortlist_reference is the definition, drn_shortlist_late_topn
+(csrc/retrieve_late.hip) the launch, on a ragged table plain or quantised, with or without a mask."""
 import collections
 import numbers
 
@@ -31,7 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from ._lib import LATE_MAX_TOKENS, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
@@ -175,6 +180,50 @@ def segment_shortlist_reference(embeddings, offsets, queries, n, allow=None):
     scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
     segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order[:, :m]).to(torch.int32), segs[:, :m])
     return SegmentShortlist(ids, scores, count.to(torch.int32), segs)
+
+
+def late_shortlist_reference(embeddings, offsets, queries, lengths, n, allow=None):
+    """THE DEFINITION of a shortlist by late interaction, in float64 (usable on the CPU).  embeddings (R, E) and offsets as in
+    segment_shortlist_reference; queries (S, L, E), one vector per token; lengths (S,) integers, clamped into [0, L]: token t of sentence
+    s is live iff t < lengths[s], and the contents of a token that is not live are ignored, NaN included.  sim[s, t, v] = the maximum
+    over v's rows of sum_e queries[s, t, e] * embeddings[r, e] (a NaN among them makes it NaN); score[s, v] = the sum of sim[s, t, v]
+    over the live tokens.  Sentence s lists the videos that own a row, that allow (a bool tensor (V,) or (S, V), as in the other
+    references) does not exclude and whose score is finite, ordered by higher score, then lower position, cut to n; a sentence without a
+    live token lists nothing.  Past the list ids = -1 and scores = 0; n[s] is its length.  With one token per sentence this is
+    segment_shortlist_reference without its rows.  -> Shortlist on the inputs' device, scores rounded to float32."""
+    n = int(n)
+    emb, q = embeddings.double(), queries.double()
+    dev = emb.device
+    R = int(emb.shape[0])
+    S, L = int(q.shape[0]), int(q.shape[1])
+    off = torch.as_tensor(check_segment_offsets(offsets, R), device=dev)
+    V = int(off.shape[0]) - 1
+    lens = off[1:] - off[:-1]
+    live = torch.arange(L, device=dev)[None, :] < torch.as_tensor(lengths, device=dev).to(torch.int64).clamp(0, L)[:, None]      # (S, L)
+    q = torch.where(live[:, :, None], q, torch.zeros_like(q))                       # (what a dead token holds never reaches a product)
+    video = torch.repeat_interleave(torch.arange(V, device=dev), lens)             # (R,) the video of a row
+    index = video[None, :].expand(S * L, R)
+    dot = q.reshape(S * L, -1) @ emb.t()                                            # (S L, R)
+    nan = torch.isnan(dot)
+    clean = torch.where(nan, torch.full_like(dot, float("-inf")), dot)
+    sim = torch.full((S * L, V), float("-inf"), dtype=torch.float64, device=dev).scatter_reduce(1, index, clean, "amax", include_self=True)
+    any_nan = torch.zeros((S * L, V), dtype=torch.float64, device=dev).scatter_add(1, index, nan.double()) > 0
+    sim = torch.where(any_nan, torch.full_like(sim, float("nan")), sim).reshape(S, L, V)
+    score = torch.where(live[:, :, None], sim, torch.zeros_like(sim)).sum(dim=1)    # (S, V)
+    finite = torch.isfinite(score) & (lens > 0)[None, :] & live.any(dim=1)[:, None]
+    if allow is not None:
+        finite = finite & _allowed(allow, S, V, dev)
+    key = torch.where(finite, score, torch.full_like(score, float("-inf")))
+    # a stable sort by descending score keeps equal scores in position order
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    count = finite.sum(dim=1).clamp(max=n)
+    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    scores = torch.zeros((S, n), dtype=torch.float32, device=dev)
+    m = min(n, V)
+    listed = torch.arange(m, device=dev)[None, :] < count[:, None]
+    ids[:, :m] = torch.where(listed, order[:, :m].to(torch.int32), ids[:, :m])
+    scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
+    return Shortlist(ids, scores, count.to(torch.int32))
 
 
 def pack_allow_reference(mask):
@@ -536,4 +585,62 @@ class Shortlister(object):
             ops.shortlist_topn_q8(self.codes, self.scales, queries.contiguous(), n, ws, *out)
         else:
             ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)
+        return Shortlist(*out)
+
+    def shortlist_late(self, queries, lengths, n, out=None, allow=None):
+        """The shortlist by LATE INTERACTION (late_shortlist_reference defines it) -> Shortlist, on the device.  queries: contiguous
+        (S, L, E) on the table's device in the table's (on a quantised table, the recorded) dtype, one vector per token, 1 <= L <=
+        LATE_MAX_TOKENS; lengths: contiguous int32 (S,) on the device, the live tokens of each sentence -- clamped into [0, L] on the
+        device and NEVER read on the host; what a token past it holds is ignored, NaN included, and costs nothing.  A video's score is
+        the sum over the live tokens, in ascending order in fp32, of the token's best row of the video; each term has the bits
+        shortlist() gives that (token, video) pair, and the sum depends on the sentence's live tokens and the video's rows alone -- not
+        on S, L, the padding, V, n, the other videos' offsets or the mask.  With one token per sentence the ids, scores and n are
+        shortlist()'s.  n, out= (three buffers: ids, scores, n) and allow= as in shortlist(); ONE tagged entry, two launches on the
+        current stream, no host synchronisation, and it can be captured in a graph (the workspace is kept per (S, n): warm the shape
+        once), where queries, lengths and the mask's contents may change in place between replays.  Works on a ragged table, plain or
+        quantised.  A table without offsets is refused: with one row per video the sum over the tokens of q_t . emb_v is (the sum of
+        q_t) . emb_v, so the caller adds the live tokens and calls shortlist()."""
+        what = "Shortlister.shortlist_late"
+        seg = getattr(self, "_seg", None)
+        if seg is None:
+            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
+                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call shortlist()" % what)
+        E, dtype, dev = self.E, self.dtype, self._table().device
+        if not torch.is_tensor(queries):
+            raise DrnError("%s: the queries must be a tensor" % what)
+        if queries.dim() != 3 or queries.shape[0] < 1 or queries.shape[2] != E:
+            raise DrnError("%s: the queries must be (S, L, %d), one vector per token, not %s" % (what, E, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), int(queries.shape[1])
+        if not 1 <= L <= LATE_MAX_TOKENS:
+            raise DrnError("%s: L = %d tokens outside [1, %d]" % (what, L, LATE_MAX_TOKENS))
+        if queries.dtype != dtype:
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        n = int(n)
+        if not 1 <= n <= SHORTLIST_MAX:
+            raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
+        if not queries.is_cuda or queries.device != dev:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
+        if not queries.is_contiguous():
+            raise DrnError("%s: the queries must be contiguous" % what)
+        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
+            raise DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor, the live tokens of each sentence" % (what, S))
+        if not lengths.is_cuda or lengths.device != dev:
+            raise DrnError("%s: lengths must be on the table's device %s (they are never read on the host)" % (what, dev))
+        if out is not None:
+            if len(out) != 3:
+                raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
+            for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
+                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+        if allow is not None:
+            self._check_allow(allow, S)
+        if out is None:
+            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
+                   torch.empty((S,), dtype=torch.int32, device=dev))
+        ws = self._ws.get(("late", S, n))
+        if ws is None:
+            keys = ops.shortlist_late_ws_keys(int(seg[1].shape[0]) - 1, S, n)
+            ws = self._ws[("late", S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
+        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
+        ops.shortlist_late_topn(table, queries, lengths, seg[0], seg[1], n, ws, *out, allow=allow)
         return Shortlist(*out)

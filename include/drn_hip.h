@@ -707,6 +707,29 @@ int drn_shortlist_segments_topn_q8_allow(const uint8_t* codes, const uint8_t* sc
                                          const int32_t* blk_vid, const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V,
                                          int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
                                          int32_t* counts, int32_t* rows, void* stream);
+/* The shortlist by LATE INTERACTION over a ragged table (drn_amd/csrc/retrieve_late.hip): queries [S][L][E] holds L token vectors a
+ * sentence, lengths [S] int32 on the device says how many of them are live -- clamped into [0, L] on the device, never read on the host;
+ * the contents of a token at or past it are not read.  sim[s][t][v] = drn_shortlist_segments_topn's score of (query row (s, t), video
+ * v) -- the same MFMA chain per (token, row) and the same segmented maximum, so its bits are that entry's -- and score[s][v] = ((0 +
+ * sim[s][0][v]) + sim[s][1][v]) + ... over the live tokens in ascending order, plain fp32 adds: it depends on the sentence's live tokens
+ * and the video's rows alone, not on S, L, the padding, V, n, the other videos' offsets, the mask or the grid.  Sentence s lists the
+ * videos that own a row, whose score is finite (a NaN or an infinity among the terms carries through) and whose mask bit is set, under
+ * the total order of drn_shortlist_topn, cut to n; a sentence without live tokens lists nothing.  1 <= L <= DRN_LATE_MAX_TOKENS (a
+ * choice that bounds one workgroup's time, not a measurement).  offsets, blk_vid, R, V, nblocks: the table and the block plan of
+ * drn_shortlist_segments_topn (vid_blk is not needed: no segment is looked up).  allow: a packed mask as in the *_allow entries, or NULL
+ * for none (allow_stride is then ignored).  ws: ws_keys >= S * nblocks * min(n, 256) 8-byte keys.  Two launches -- workgroup (block,
+ * sentence) walks the sentence's live tokens in tiles of 16 against its block's rows, then the merge of drn_shortlist_topn -- no atomics,
+ * no host synchronisation; lengths, the queries and the mask may change between replays of a captured graph.  The _q8 twin takes the
+ * table as codes and scales (drn_shortlist_segments_topn_q8 says how) and answers bit for bit like the plain entry over the dequantised
+ * table. */
+#define DRN_LATE_MAX_TOKENS 64
+int drn_shortlist_late_topn(const void* emb, const void* queries, const int32_t* lengths, const int32_t* offsets, const int32_t* blk_vid,
+                            const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int L, int n, int dtype,
+                            void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, void* stream);
+int drn_shortlist_late_topn_q8(const uint8_t* codes, const uint8_t* scales, const void* queries, const int32_t* lengths,
+                               const int32_t* offsets, const int32_t* blk_vid, const int32_t* allow, int allow_stride, int R, int V,
+                               int nblocks, int E, int S, int L, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
+                               int32_t* counts, void* stream);
 /* mask [S][V], one byte a video (a torch.bool tensor: non-zero = allowed) -> words [S][ceil(V / 32)], the packed mask above: every
  * word written, bits at or past V zero.  S = 1 packs a mask shared by all sentences.  One launch, nothing read back. */
 int drn_pack_allow(const uint8_t* mask, int S, int V, int32_t* words, void* stream);

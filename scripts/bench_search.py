@@ -87,7 +87,18 @@
            Two conditions are derived, not measured, and reported shape by shape: (C1) the all-ones mask costs the unmasked launch plus
            at most 128 (144 ragged) mask words per workgroup -- the difference against (a) is printed, in capitals where it exceeds (a)'s
            max - min; (C2) the contiguous-1/16 and the 1 % mask do no more work than the all-ones mask and may not take longer than it
-           beyond its max - min.  Random embeddings: nothing here says anything about recall."""
+           beyond its max - min.  Random embeddings: nothing here says anything about recall.
+
+  --late-shortlist      instead of the above -> profiles/search_late_shortlist_bench.json: Shortlister.shortlist_late (drn_shortlist_late_topn,
+           both launches) on R = 65,536 rows x 512 in bf16 laid out as 4,096 x 16 and 546 x 120, n = 16, S in {1, 8, 64}, with L = 8 all
+           live, L = 16 all live, L = 16 with lengths 6 and L = 32 with lengths 16; launch-inclusive us, median [min, max] of 5
+           interleaved rounds in one process, beside (a) what a caller can do without the feature -- torch.matmul on the flattened
+           tokens, scatter_reduce_(amax), a masked sum, torch.topk -- at the shapes whose (S L, R) matrix and index stay below 512 rows, and
+           (b) shortlist() on the same table with the S L flattened tokens as queries: another answer, the same MFMA work and table reads
+           per 16 query rows.  Two conditions are derived, not measured, and reported shape by shape: (C1) L = 16 all live takes no longer
+           than (b) at 16 S query rows beyond (b)'s max - min; (C2) L = 32 with lengths 16 takes no longer than L = 16 all live beyond the
+           latter's max - min, with a control beside it: L = 16 all live once more on other random tokens.  The largest error / tolerance ratio of tests/test_late_shortlist_gpu.py's random case.  Random
+           embeddings: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1531,11 +1542,140 @@ def main_filtered_shortlist(args):
     print("wrote", out)
 
 
+LATE_TOKENS = (("L8", 8, 8), ("L16", 16, 16), ("L16_len6", 16, 6), ("L32_len16", 32, 16))        # (name, L, live tokens of every sentence)
+LATE_TORCH_MAX_ROWS = 512                                   # (a) is measured where S L stays at or below it: a 256 MiB int64 index beside the matrix
+
+
+def bench_late_shortlist(name, lens, emb, S, n, rounds):
+    """drn_shortlist_late_topn on R = 65,536 rows cut into videos by `lens`, the four token shapes of one (layout, S) taking turns with
+    (b) shortlist() on the flattened tokens and (a) matmul + amax + masked sum + topk inside every round."""
+    import numpy as np
+    from drn_amd import SegmentShortlist, Shortlist, Shortlister
+    R, V = int(emb.shape[0]), len(lens)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    assert off[-1] == R
+    g = torch.Generator(device="cuda:0").manual_seed(S + n)
+    seg = Shortlister(emb, offsets=off)
+    variants, flops = {}, {}
+    for tag, L, live in LATE_TOKENS:
+        q = torch.randn(S, L, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+        lengths = torch.full((S,), live, dtype=torch.int32, device="cuda:0")
+        out = Shortlist(*seg.shortlist_late(q, lengths, n))
+        variants["late_" + tag] = (lambda q=q, lengths=lengths, out=out: seg.shortlist_late(q, lengths, n, out=out))
+        flops[tag] = 2.0 * S * live * R * 512
+        if live == L:                                       # (b) cannot skip padding: it is measured at the all-live shapes and at 32 S rows
+            flat = q.reshape(S * L, 512)
+            out_flat = SegmentShortlist(*seg.shortlist(flat, n))
+            variants["flat_" + tag] = (lambda flat=flat, out_flat=out_flat: seg.shortlist(flat, n, out=out_flat))
+        if S * L <= LATE_TORCH_MAX_ROWS:
+            index = torch.repeat_interleave(torch.arange(V, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(S * L, R).contiguous()
+            best = torch.empty((S * L, V), dtype=torch.bfloat16, device="cuda:0")
+            alive = (torch.arange(L, device="cuda:0")[None, :] < lengths[:, None])[:, :, None]
+
+            def torch_way(q=q, index=index, best=best, alive=alive, L=L):
+                best.fill_(float("-inf"))
+                best.scatter_reduce_(1, index, torch.matmul(q.reshape(S * L, 512), emb.t()), "amax")
+                sim = best.view(S, L, V).float()
+                return torch.topk(torch.where(alive, sim, torch.zeros_like(sim)).sum(dim=1), min(n, V), dim=1)
+            variants["torch_" + tag] = torch_way
+    # a control for (C2): L = 16 all live once more, on other random tokens in another tensor -- what two inputs of ONE shape differ by
+    q16b, l16b = torch.randn(S, 16, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous(), torch.full((S,), 16, dtype=torch.int32, device="cuda:0")
+    out16b = Shortlist(*seg.shortlist_late(q16b, l16b, n))
+    variants["late_L16_other_tokens"] = lambda: seg.shortlist_late(q16b, l16b, n, out=out16b)
+    q32 = torch.randn(S * 32, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    out32 = SegmentShortlist(*seg.shortlist(q32, n))
+    variants["flat_L32"] = lambda: seg.shortlist(q32, n, out=out32)
+    times, reps = interleaved_windows(variants, rounds)
+    row = {"layout": name, "R": R, "V": V, "E": 512, "S": S, "n": n, "dtype": "bf16", "blocks": int(seg.plan.blk_vid.shape[0]) - 1,
+           "launches_per_window": reps, "table_bytes": emb.numel() * emb.element_size(), "shapes": []}
+    for tag, L, live in LATE_TOKENS:
+        late = times["late_" + tag]
+        shape = {"tokens": tag, "L": L, "live": live, "late_us": spread(late), "flops": flops[tag],
+                 "tflops": flops[tag] / (statistics.median(late) * 1e-6) / 1e12, "table_reads": S * -(-live // 16)}
+        if "flat_" + tag in times:
+            shape["flat_shortlist_us"] = spread(times["flat_" + tag])
+            shape["late_against_flat_shortlist"] = verdict(late, times["flat_" + tag])
+        if "torch_" + tag in times:
+            shape["matmul_amax_sum_topk_us"] = spread(times["torch_" + tag])
+            shape["late_over_matmul_amax_sum_topk"] = statistics.median(late) / statistics.median(times["torch_" + tag])
+            shape["late_against_matmul_amax_sum_topk"] = verdict(late, times["torch_" + tag])
+        row["shapes"].append(shape)
+    row["flat_shortlist_32S_rows_us"] = spread(times["flat_L32"])
+    b, l16, l32 = times["flat_L16"], times["late_L16"], times["late_L32_len16"]
+    over1, over2 = statistics.median(l16) - statistics.median(b), statistics.median(l32) - statistics.median(l16)
+    row["C1"] = {"late_L16_minus_flat_16S_rows_us": over1, "flat_max_minus_min_us": max(b) - min(b), "holds": over1 <= max(b) - min(b)}
+    row["C2"] = {"late_L32_len16_minus_late_L16_us": over2, "late_L16_max_minus_min_us": max(l16) - min(l16), "holds": over2 <= max(l16) - min(l16),
+                 "control_late_L16_other_tokens_minus_late_L16_us": statistics.median(times["late_L16_other_tokens"]) - statistics.median(l16)}
+    row["late_L16_other_tokens_us"] = spread(times["late_L16_other_tokens"])
+    row["note"] = ("launch-inclusive, both launches of the late shortlist; flat_shortlist ranks the S L tokens as S L sentences (another answer: "
+                   "per-token lists, all three launches of the segmented shortlist); torch scores in bf16, here fp32; table_reads counts the "
+                   "block rows read once per (sentence, token tile)")
+    return row
+
+
+def late_tolerance_ratio():
+    """tests/test_late_shortlist_gpu.py's random case (E = 512, run lengths 1, 3, 0, 17 twenty times, then 300 and 2; S = 5, L = 33 with
+    lengths 33, 1, 16, 17, 20, n = 16, bf16): the largest |returned score - the float64 score| over tol = sum over the live t of the
+    largest E * 2^-23 * sum |q_t * emb_r| of the video's rows + L * 2^-23 * sum over the live t of |sim_t|."""
+    import numpy as np
+    from drn_amd import Shortlister
+    lens = [1, 3, 0, 17] * 20 + [300, 2]
+    V, L, E = len(lens), 33, 512
+    g = torch.Generator().manual_seed(4)
+    emb = torch.randn(sum(lens), E, generator=g).to("cuda:0", torch.bfloat16).contiguous()
+    q = torch.randn(17, 64, E, generator=g).to("cuda:0", torch.bfloat16)[:5, :L].contiguous()
+    lengths = torch.tensor([33, 1, 16, 17, 20], dtype=torch.int32, device="cuda:0")
+    got = Shortlister(emb, offsets=np.concatenate([[0], np.cumsum(lens)])).shortlist_late(q, lengths, 16)
+    video = torch.repeat_interleave(torch.arange(V, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(5 * L, -1)
+    flat = q.double().reshape(5 * L, E)
+    sim = torch.full((5 * L, V), float("-inf"), dtype=torch.float64, device="cuda:0").scatter_reduce(1, video, flat @ emb.double().t(), "amax")
+    tol = torch.zeros_like(sim).scatter_reduce(1, video, E * 2.0 ** -23 * (flat.abs() @ emb.double().abs().t()), "amax")
+    live = (torch.arange(L, device="cuda:0")[None] < lengths[:, None])[:, :, None] & (torch.as_tensor(lens, device="cuda:0") > 0)[None, None]
+    sim = torch.where(live, sim.reshape(5, L, V), torch.zeros((), dtype=torch.float64, device="cuda:0"))
+    tol = torch.where(live, tol.reshape(5, L, V), torch.zeros((), dtype=torch.float64, device="cuda:0")).sum(dim=1) + L * 2.0 ** -23 * sim.abs().sum(dim=1)
+    ids = got.ids.long()
+    return float(((got.scores.double() - torch.gather(sim.sum(dim=1), 1, ids)).abs() / torch.gather(tol, 1, ids)).max())
+
+
+def main_late_shortlist(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_late_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "(a) matmul_amax_sum_topk: torch.matmul on the flattened tokens, scatter_reduce_(amax) over the videos' rows, "
+                                   "a masked sum over the tokens, torch.topk -- where S L <= %d; (b) flat_shortlist: shortlist() of the same "
+                                   "table on the S L flattened tokens, the parent's code unchanged.  A difference inside the baseline's own "
+                                   "max - min is NO DIFFERENCE" % LATE_TORCH_MAX_ROWS,
+                      "conditions": "derived, not measured: (C1) L = 16 all live runs the tiles of (b) at 16 S query rows, sorts one key row "
+                                    "where (b) sorts 16 and merges S lists where (b) merges 16 S, so it may not take longer than (b) beyond "
+                                    "(b)'s max - min; (C2) L = 32 with lengths 16 never enters its second tile and may not take longer than "
+                                    "L = 16 all live beyond ITS max - min",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall; no kernel-only times (no profiler "
+                                                "run); n = 16 only"},
+           "tolerance_ratio": late_tolerance_ratio(), "late_shortlist": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for name, lens in SEGMENT_LAYOUTS[1:]:
+            row = bench_late_shortlist(name, lens, emb, S, 16, args.rounds)
+            res["late_shortlist"].append(row)
+            print(json.dumps({"late_shortlist": row}), flush=True)
+            for c in ("C1", "C2"):
+                print("%s %s S = %d: %s" % (c, name, S, "holds" if row[c]["holds"] else "MISSED"), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
                                             "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
-                                            "search_filtered_shortlist_bench.json with --filtered-shortlist)")
+                                            "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
+                                            "--late-shortlist)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1553,9 +1693,13 @@ def main():
                                                                        "layouts beside the plain table over the same dequantised rows")
     ap.add_argument("--filtered-shortlist", action="store_true", help="measure Shortlister.shortlist(allow=) under five masks beside the unmasked "
                                                                       "launch and the sub-table way")
+    ap.add_argument("--late-shortlist", action="store_true", help="measure Shortlister.shortlist_late at four token shapes beside shortlist() on "
+                                                                  "the flattened tokens and matmul + amax + sum + topk")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.late_shortlist:
+        return main_late_shortlist(args)
     if args.filtered_shortlist:
         return main_filtered_shortlist(args)
     if args.quantized_shortlist:
