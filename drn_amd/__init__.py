@@ -6,6 +6,7 @@ __version__ = "0.1.0"
 from .grounding import Grounder, Hits, Moments, group_by_video, plan_candidate_steps, search  # noqa: E402,F401
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
 from .index import SearchIndex  # noqa: E402,F401
-from .search_eval import SearchRecall, evaluate_search, search_batches  # noqa: E402,F401
-from .retrieve import (LATE_MAX_TOKENS, SegmentShortlist, Shortlist, Shortlister, late_shortlist_reference, pack_allow,  # noqa: E402,F401
-                       pack_allow_reference, plan_segment_blocks, segment_shortlist_reference, shortlist_reference)
+from .search_eval import SearchRecall, ShortlistRecall, evaluate_search, evaluate_shortlist, search_batches  # noqa: E402,F401
+from .retrieve import (LATE_MAX_TOKENS, SegmentShortlist, Shortlist, Shortlister, TargetRank, late_rank_reference,  # noqa: E402,F401
+                       late_shortlist_reference, pack_allow, pack_allow_reference, plan_segment_blocks, rank_reference,
+                       segment_rank_reference, segment_shortlist_reference, shortlist_reference)

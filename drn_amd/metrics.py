@@ -146,6 +146,30 @@ def recall_from_first_hits(first_hits, ious, topks):
     return [float((fh[:, q] < k).sum()) / total for q in range(len(ious)) for k in topks]
 
 
+def recall_from_ranks(ranks, topks):
+    """The host twin of evaluate_shortlist's recalls: ranks, one integer per sentence -- the 0-based place of its target video in the
+    FULL shortlist order (Shortlister.rank), -1 where the target is no candidate -> the fraction with 0 <= rank < k, one per k of
+    topks; -1 counts as a miss at every depth.  No sentences: zeros."""
+    r = np.asarray(ranks).reshape(-1)
+    total = max(r.shape[0], 1)
+    return [float(((r >= 0) & (r < int(k))).sum()) / total for k in topks]
+
+
+def mrr_from_ranks(ranks):
+    """The mean reciprocal rank, 1 / (rank + 1), of the same ranks; -1 is a miss and adds 0.  No sentences: 0."""
+    r = np.asarray(ranks).reshape(-1).astype(np.float64)
+    return float(np.where(r >= 0, 1.0 / (np.maximum(r, 0) + 1.0), 0.0).sum()) / max(r.shape[0], 1)
+
+
+def median_rank_from_ranks(ranks):
+    """The median 0-based rank of the same ranks; -1 is a miss and counts as infinitely deep (inf where half the sentences or more
+    missed).  No sentences: nan."""
+    r = np.asarray(ranks).reshape(-1).astype(np.float64)
+    if r.shape[0] == 0:
+        return float("nan")
+    return float(np.median(np.where(r >= 0, r, np.inf)))
+
+
 def search_first_hits(rows, gt_video, gt, ious, K):
     """Where the right moment of the right video first appears in a search's hits: the host twin of drn_search_recall
     (ops.search_recall), for callers that hold host records.  rows: Hits.tolist()'s, per sentence [[video, start, end, score], ...]

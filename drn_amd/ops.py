@@ -1809,6 +1809,114 @@ def shortlist_late_topn(table, queries, lengths, offsets, blk_vid, n, ws, ids, s
     return ids, scores, counts
 
 
+def shortlist_rank_ws_bytes(nblocks, S):
+    """The bytes of workspace the three rank entries need: 8 * S * (1 + nblocks) -- each sentence's target key, then two int32 counts
+    per (sentence, block); nblocks = ceil(V / SHORTLIST_BLOCK) on a plain table, the plan's on a ragged one."""
+    return 8 * int(S) * (1 + int(nblocks))
+
+
+def _rank_table(what, table, flat):
+    """table: emb, or a pair (codes, scales), beside queries flattened to (rows of queries, E) -> (tensors, table pointer, scales pointer
+    or None, rows, E)."""
+    if isinstance(table, (tuple, list)):
+        rows, E = _q8_table(what, table[0], table[1], flat)
+        return tuple(table), _p(table[0]), _p(table[1]), rows, E
+    rows, E = _plain_table(what, table, flat)
+    if table.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.DrnError("%s: emb must be float32 / bfloat16, not %s" % (what, table.dtype))
+    return (table,), _p(table), None, rows, E
+
+
+def _rank_buffers(what, S, need, targets, ws, rank, score, total):
+    """The checks the rank wrappers share: targets, the three outputs and the workspace."""
+    for name, t, dt in (("targets", targets, torch.int32), ("rank", rank, torch.int32), ("score", score, torch.float32),
+                        ("total", total, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous (%d,) %s tensor" % (what, name, S, dt))
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() * 8 < need:
+        raise _lib.DrnError("%s: ws must be a contiguous int64 tensor of at least %d bytes (shortlist_rank_ws_bytes)" % (what, need))
+    return int(min(ws.numel() * 8, 0x7fffffff))
+
+
+def _rank_plan(what, offsets, blk_vid):
+    """The checks of a ragged table's offsets and block starts -> (V, nblocks)."""
+    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
+        raise _lib.DrnError("%s: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1" % what)
+    for name, t in (("offsets", offsets), ("blk_vid", blk_vid)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous torch.int32 tensor" % (what, name))
+    return int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
+
+
+def shortlist_rank(table, queries, targets, ws, rank, score, total, allow=None):
+    """The place of targets[s] in sentence s's FULL shortlist order over a plain table (drn_shortlist_rank;
+    drn_amd.retrieve.rank_reference is the definition): table is emb (V, E), float32 / bfloat16, or a pair (codes, scales) of a
+    block-scaled FP8 table; queries (S, E) of the table's dtype (float32 / bfloat16 beside codes); targets (S,) int32 ON THE DEVICE, a
+    value outside [0, V) meaning "no target" -> rank (S,) int32 (-1: the target is no candidate), score (S,) float32 (the target's, with
+    shortlist_topn's bits; 0 beside -1) and total (S,) int32 (the sentence's candidates), written in place.  allow: None, or a packed
+    mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_rank_ws_bytes(ceil(V / SHORTLIST_BLOCK), S) bytes.
+    Three launches on the current stream behind one entry (one tag, shortlist_rank); nothing is read on the host."""
+    what = "shortlist_rank"
+    if queries.dim() != 2:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, E) tensor, not %s" % (what, tuple(queries.shape)))
+    tensors, tab, scl, V, E = _rank_table(what, table, queries)
+    _need_gpu(*(tensors + (queries, targets, ws, rank, score, total) + (() if allow is None else (allow,))))
+    S = int(queries.shape[0])
+    have = _rank_buffers(what, S, shortlist_rank_ws_bytes(-(-V // _lib.SHORTLIST_BLOCK), S), targets, ws, rank, score, total)
+    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
+    mask = None if allow is None else _p(allow)
+    _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_rank(
+        tab, scl, _p(queries), _p(targets), mask, stride, V, E, S, dtype_code(queries), _p(ws), have, _p(rank), _p(score), _p(total),
+        _stream()), "drn_shortlist_rank"))
+    return rank, score, total
+
+
+def shortlist_segments_rank(table, queries, offsets, blk_vid, targets, ws, rank, score, total, allow=None):
+    """shortlist_rank over a RAGGED table, a video scoring by its best row (drn_shortlist_segments_rank;
+    drn_amd.retrieve.segment_rank_reference is the definition): table (R, E) or (codes, scales); offsets (V + 1,) and blk_vid
+    (nblocks + 1,) int32 on the device as in shortlist_segments_topn; a target that owns no row gets -1.  ws: at least
+    shortlist_rank_ws_bytes(nblocks, S) bytes.  Every other argument as in shortlist_rank.  Three launches behind one entry (one tag,
+    shortlist_segments_rank); nothing is read on the host."""
+    what = "shortlist_segments_rank"
+    if queries.dim() != 2:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, E) tensor, not %s" % (what, tuple(queries.shape)))
+    tensors, tab, scl, R, E = _rank_table(what, table, queries)
+    _need_gpu(*(tensors + (queries, offsets, blk_vid, targets, ws, rank, score, total) + (() if allow is None else (allow,))))
+    S = int(queries.shape[0])
+    V, nblocks = _rank_plan(what, offsets, blk_vid)
+    have = _rank_buffers(what, S, shortlist_rank_ws_bytes(nblocks, S), targets, ws, rank, score, total)
+    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
+    mask = None if allow is None else _p(allow)
+    _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_rank(
+        tab, scl, _p(queries), _p(offsets), _p(blk_vid), _p(targets), mask, stride, R, V, nblocks, E, S, dtype_code(queries), _p(ws), have,
+        _p(rank), _p(score), _p(total), _stream()), "drn_shortlist_segments_rank"))
+    return rank, score, total
+
+
+def shortlist_late_rank(table, queries, lengths, offsets, blk_vid, targets, ws, rank, score, total, allow=None):
+    """shortlist_rank by LATE INTERACTION over a ragged table (drn_shortlist_late_rank; drn_amd.retrieve.late_rank_reference is the
+    definition): queries (S, L, E), 1 <= L <= LATE_MAX_TOKENS, and lengths (S,) int32 on the device as in shortlist_late_topn; a
+    sentence without a live token has no candidate (rank -1, total 0).  Every other argument as in shortlist_segments_rank.  Three
+    launches behind one entry (one tag, shortlist_late_rank); nothing is read on the host."""
+    what = "shortlist_late_rank"
+    if queries.dim() != 3 or not queries.is_contiguous() or not 1 <= queries.shape[1] <= _lib.LATE_MAX_TOKENS or queries.shape[0] < 1:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, L, E) tensor with S >= 1 and 1 <= L <= %d, not %s"
+                            % (what, _lib.LATE_MAX_TOKENS, tuple(queries.shape)))
+    S, L = int(queries.shape[0]), int(queries.shape[1])
+    tensors, tab, scl, R, E = _rank_table(what, table, queries.view(S * L, -1))
+    _need_gpu(*(tensors + (queries, lengths, offsets, blk_vid, targets, ws, rank, score, total) + (() if allow is None else (allow,))))
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
+        raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
+    V, nblocks = _rank_plan(what, offsets, blk_vid)
+    have = _rank_buffers(what, S, shortlist_rank_ws_bytes(nblocks, S), targets, ws, rank, score, total)
+    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
+    mask = None if allow is None else _p(allow)
+    _timed(what, 2.0 * S * L * R * E, lambda: check(lib().drn_shortlist_late_rank(
+        tab, scl, _p(queries), _p(lengths), _p(offsets), _p(blk_vid), _p(targets), mask, stride, R, V, nblocks, E, S, L, dtype_code(queries),
+        _p(ws), have, _p(rank), _p(score), _p(total), _stream()), "drn_shortlist_late_rank"))
+    return rank, score, total
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -28,7 +28,13 @@ four *_allow entries (csrc/retrieve_allow.hip) the launches, and a listed score 
 Shortlister.shortlist_late takes the QUERY side multi-vector too (late interaction, as token-level dual encoders score): queries
 (S, L, E), one vector per token, lengths (S,) on the device saying how many are live, and a video's score is the sum over the live
 tokens of the token's best row of the video.  late_shortlist_reference is the definition, drn_shortlist_late_topn
-(csrc/retrieve_late.hip) the launch, on a ragged table plain or quantised, with or without a mask."""
+(csrc/retrieve_late.hip) the launch, on a ragged table plain or quantised, with or without a mask.
+
+Shortlister.rank and rank_late answer what a list of at most SHORTLIST_MAX cannot: the place of a NAMED video in the FULL order -- how
+many candidates precede targets[s], over the whole table, with its score and the number of candidates -- from the kernels' own scores
+and total order, without a list, a sort or a host read.  rank_reference, segment_rank_reference and late_rank_reference are the
+definitions, drn_shortlist_rank / _segments_rank / _late_rank (csrc/retrieve_rank.hip) the launches, on all the tables above, with or
+without a mask; drn_amd.search_eval.evaluate_shortlist turns the ranks of annotated sentences into recall at any depth."""
 import collections
 import numbers
 
@@ -36,7 +42,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import LATE_MAX_TOKENS, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from ._lib import LATE_MAX_TOKENS, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
@@ -57,24 +63,85 @@ def shortlist_reference(embeddings, queries, n, allow=None):
     scores = 0; n[s] is its length (a NaN query row lists nothing).  allow: a bool tensor (V,), shared by all sentences, or (S, V), one
     row per sentence: a video with allow == False is no candidate for that sentence, exactly like one whose score is not finite (its
     score, NaN or the best, changes nothing for the others).  -> Shortlist on the inputs' device, scores rounded to float32."""
-    n = int(n)
+    score, finite = _plain_scores(embeddings, queries, allow)
+    ids, scores, count, _ = _listed(score, finite, int(n))
+    return Shortlist(ids, scores, count)
+
+
+def _plain_scores(embeddings, queries, allow):
+    """What shortlist_reference and rank_reference share -> score (S, V) float64 and candidate (S, V) bool: the score is finite and the
+    video allowed."""
     emb, q = embeddings.double(), queries.double()
     V, S = int(emb.shape[0]), int(q.shape[0])
     score = q @ emb.t()
     finite = torch.isfinite(score)
     if allow is not None:
         finite = finite & _allowed(allow, S, V, emb.device)
+    return score, finite
+
+
+def _listed(score, finite, n):
+    """The list every reference cuts from its scores (S, V) and candidates -> ids, scores (S, n), count (S,) int32 and the (S, m)
+    positions listed, m = min(n, V), with the bool (S, m) that says which of them lie inside the list."""
+    S, V = (int(x) for x in score.shape)
+    dev = score.device
     key = torch.where(finite, score, torch.full_like(score, float("-inf")))
     # a stable sort by descending score keeps equal scores in position order
     order = torch.sort(key, dim=1, descending=True, stable=True).indices
     count = finite.sum(dim=1).clamp(max=n)
-    ids = torch.full((S, n), -1, dtype=torch.int32, device=emb.device)
-    scores = torch.zeros((S, n), dtype=torch.float32, device=emb.device)
+    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    scores = torch.zeros((S, n), dtype=torch.float32, device=dev)
     m = min(n, V)
-    listed = torch.arange(m, device=emb.device)[None, :] < count[:, None]
+    listed = torch.arange(m, device=dev)[None, :] < count[:, None]
     ids[:, :m] = torch.where(listed, order[:, :m].to(torch.int32), ids[:, :m])
     scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
-    return Shortlist(ids, scores, count.to(torch.int32))
+    return ids, scores, count.to(torch.int32), (order[:, :m], listed)
+
+
+TargetRank = collections.namedtuple("TargetRank", "rank score total")
+TargetRank.__doc__ = """rank (S,) int32: how many candidates precede the sentence's target video in the FULL shortlist order (score
+descending, then position ascending), -1 where the target is no candidate; score (S,) float32: the target's score, 0 beside -1; total
+(S,) int32: the sentence's candidates, the length of its list were n unbounded.  All on the device."""
+
+
+def _ranked(score, finite, targets):
+    """The rank every rank reference takes from its scores (S, V) and candidates -> TargetRank."""
+    S, V = (int(x) for x in score.shape)
+    dev = score.device
+    t = torch.as_tensor(targets, device=dev).to(torch.int64).reshape(-1)
+    if int(t.shape[0]) != S:
+        raise DrnError("rank reference: %d targets for %d sentences" % (int(t.shape[0]), S))
+    tc = t.clamp(0, V - 1)[:, None]
+    ts = torch.gather(score, 1, tc)                                                # (S, 1) the target's score
+    found = ((t >= 0) & (t < V))[:, None] & torch.gather(finite, 1, tc)
+    before = finite & ((score > ts) | ((score == ts) & (torch.arange(V, device=dev)[None, :] < tc)))
+    rank = torch.where(found[:, 0], before.sum(dim=1), torch.full((S,), -1, dtype=torch.int64, device=dev))
+    value = torch.where(found[:, 0], ts[:, 0], torch.zeros_like(ts[:, 0]))
+    return TargetRank(rank.to(torch.int32), value.float(), finite.sum(dim=1).to(torch.int32))
+
+
+def rank_reference(embeddings, queries, targets, allow=None):
+    """THE DEFINITION of a target's rank, in float64 (usable on the CPU).  Scores and candidates are shortlist_reference's: a video is
+    a candidate of sentence s when its score is finite and allow does not exclude it.  targets: S integers (a sequence or a tensor);
+    with t = targets[s], total[s] = the candidates of s; where 0 <= t < V and t is a candidate, rank[s] = the candidates u with
+    score[s, u] > score[s, t], or score[s, u] == score[s, t] and u < t, and score[s] = t's score rounded to float32; otherwise
+    rank[s] = -1 and score[s] = 0 (a value outside [0, V) is legal and means "no target").  So rank[s] = k >= 0 exactly when
+    shortlist_reference(..., n).ids[s, k] == t for every n > k.  -> TargetRank on the inputs' device."""
+    return _ranked(*_plain_scores(embeddings, queries, allow), targets)
+
+
+def segment_rank_reference(embeddings, offsets, queries, targets, allow=None):
+    """rank_reference with the scores and candidates of segment_shortlist_reference: a video scores by its best row and is a candidate
+    when it owns a row, its score is finite and allow (over VIDEOS) does not exclude it.  -> TargetRank."""
+    score, _, finite = _segment_scores(embeddings, offsets, queries, allow)
+    return _ranked(score, finite, targets)
+
+
+def late_rank_reference(embeddings, offsets, queries, lengths, targets, allow=None):
+    """rank_reference with the scores and candidates of late_shortlist_reference: queries (S, L, E), lengths (S,); a video scores by
+    the sum over the live tokens of its best row and is a candidate when it owns a row, the sum is finite, allow does not exclude it
+    and the sentence has a live token (one without has total = 0 and rank = -1).  -> TargetRank."""
+    return _ranked(*_late_scores(embeddings, offsets, queries, lengths, allow), targets)
 
 
 SegmentShortlist = collections.namedtuple("SegmentShortlist", "ids scores n rows")
@@ -145,7 +212,17 @@ def segment_shortlist_reference(embeddings, offsets, queries, n, allow=None):
     ordered by higher score, then lower position, cut to n.  Past the list ids = -1, scores = 0 and rows = -1; n[s] is its length (a NaN
     query row lists nothing).  allow: as in shortlist_reference, a bool tensor (V,) or (S, V) over VIDEOS, not rows: a video with
     allow == False is no candidate for that sentence.  -> SegmentShortlist on the inputs' device, scores rounded to float32."""
-    n = int(n)
+    score, rows, finite = _segment_scores(embeddings, offsets, queries, allow)
+    ids, scores, count, (order, listed) = _listed(score, finite, int(n))
+    segs = torch.full(tuple(ids.shape), -1, dtype=torch.int32, device=ids.device)
+    m = int(order.shape[1])
+    segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order).to(torch.int32), segs[:, :m])
+    return SegmentShortlist(ids, scores, count, segs)
+
+
+def _segment_scores(embeddings, offsets, queries, allow):
+    """What segment_shortlist_reference and segment_rank_reference share -> score (S, V) float64, rows (S, V) int64 (the lowest
+    segment that reaches it) and candidate (S, V) bool: the video owns a row, its score is finite and it is allowed."""
     emb, q = embeddings.double(), queries.double()
     dev = emb.device
     R, S = int(emb.shape[0]), int(q.shape[0])
@@ -167,19 +244,7 @@ def segment_shortlist_reference(embeddings, offsets, queries, n, allow=None):
     finite = torch.isfinite(score) & (lens > 0)[None, :]
     if allow is not None:
         finite = finite & _allowed(allow, S, V, dev)
-    key = torch.where(finite, score, torch.full_like(score, float("-inf")))
-    # a stable sort by descending score keeps equal scores in position order
-    order = torch.sort(key, dim=1, descending=True, stable=True).indices
-    count = finite.sum(dim=1).clamp(max=n)
-    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
-    scores = torch.zeros((S, n), dtype=torch.float32, device=dev)
-    segs = torch.full((S, n), -1, dtype=torch.int32, device=dev)
-    m = min(n, V)
-    listed = torch.arange(m, device=dev)[None, :] < count[:, None]
-    ids[:, :m] = torch.where(listed, order[:, :m].to(torch.int32), ids[:, :m])
-    scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
-    segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order[:, :m]).to(torch.int32), segs[:, :m])
-    return SegmentShortlist(ids, scores, count.to(torch.int32), segs)
+    return score, rows, finite
 
 
 def late_shortlist_reference(embeddings, offsets, queries, lengths, n, allow=None):
@@ -191,7 +256,13 @@ def late_shortlist_reference(embeddings, offsets, queries, lengths, n, allow=Non
     references) does not exclude and whose score is finite, ordered by higher score, then lower position, cut to n; a sentence without a
     live token lists nothing.  Past the list ids = -1 and scores = 0; n[s] is its length.  With one token per sentence this is
     segment_shortlist_reference without its rows.  -> Shortlist on the inputs' device, scores rounded to float32."""
-    n = int(n)
+    ids, scores, count, _ = _listed(*_late_scores(embeddings, offsets, queries, lengths, allow), int(n))
+    return Shortlist(ids, scores, count)
+
+
+def _late_scores(embeddings, offsets, queries, lengths, allow):
+    """What late_shortlist_reference and late_rank_reference share -> score (S, V) float64 and candidate (S, V) bool: the video owns a
+    row, the sum is finite, the video is allowed and the sentence has a live token."""
     emb, q = embeddings.double(), queries.double()
     dev = emb.device
     R = int(emb.shape[0])
@@ -213,17 +284,7 @@ def late_shortlist_reference(embeddings, offsets, queries, lengths, n, allow=Non
     finite = torch.isfinite(score) & (lens > 0)[None, :] & live.any(dim=1)[:, None]
     if allow is not None:
         finite = finite & _allowed(allow, S, V, dev)
-    key = torch.where(finite, score, torch.full_like(score, float("-inf")))
-    # a stable sort by descending score keeps equal scores in position order
-    order = torch.sort(key, dim=1, descending=True, stable=True).indices
-    count = finite.sum(dim=1).clamp(max=n)
-    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
-    scores = torch.zeros((S, n), dtype=torch.float32, device=dev)
-    m = min(n, V)
-    listed = torch.arange(m, device=dev)[None, :] < count[:, None]
-    ids[:, :m] = torch.where(listed, order[:, :m].to(torch.int32), ids[:, :m])
-    scores[:, :m] = torch.where(listed, torch.gather(score, 1, order[:, :m]).float(), scores[:, :m])
-    return Shortlist(ids, scores, count.to(torch.int32))
+    return score, finite
 
 
 def pack_allow_reference(mask):
@@ -644,3 +705,100 @@ class Shortlister(object):
         table = self.embeddings if self.quantize is None else (self.codes, self.scales)
         ops.shortlist_late_topn(table, queries, lengths, seg[0], seg[1], n, ws, *out, allow=allow)
         return Shortlist(*out)
+
+    def _check_rank(self, what, S, targets, out, allow):
+        """What rank() and rank_late() refuse about targets, out= and allow=, before the library is reached -> out, made where None."""
+        dev = self._table().device
+        if not torch.is_tensor(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (S,) or not targets.is_contiguous():
+            raise DrnError("%s: targets must be a contiguous (%d,) torch.int32 tensor, the store position of each sentence's video" % (what, S))
+        if not targets.is_cuda or targets.device != dev:
+            raise DrnError("%s: targets must be on the table's device %s (they are never read on the host)" % (what, dev))
+        if out is not None:
+            if len(out) != 3:
+                raise DrnError("%s: out must hold the three buffers of a TargetRank (rank, score, total), not %d" % (what, len(out)))
+            for name, t, dt in zip(TargetRank._fields, out, (torch.int32, torch.float32, torch.int32)):
+                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+                    raise DrnError("%s: out.%s must be a contiguous (%d,) %s tensor on the GPU" % (what, name, S, dt))
+        if allow is not None:
+            self._check_allow(allow, S)
+        if out is None:
+            out = (torch.empty((S,), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.float32, device=dev),
+                   torch.empty((S,), dtype=torch.int32, device=dev))
+        return tuple(out)
+
+    def _rank_ws(self, key, nblocks, S):
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.empty(ops.shortlist_rank_ws_bytes(nblocks, S) // 8, dtype=torch.int64, device=self._table().device)
+        return ws
+
+    def rank(self, queries, targets, out=None, allow=None):
+        """The place of each sentence's TARGET video in its full shortlist order -> TargetRank (rank_reference defines it; on a ragged
+        table segment_rank_reference), on the device.  queries as in shortlist(); targets: contiguous int32 (S,) on the table's device,
+        the store position of each sentence's video, NEVER read on the host -- a value outside [0, V) is legal and means "no target".
+        rank[s] counts the candidates that precede the target over the WHOLE table -- no cap at SHORTLIST_MAX, no list, no sort -- so
+        rank[s] = k >= 0 exactly when shortlist(queries, n).ids[s, k] is the target for every n > k, and score[s] has the listed
+        score's bits; -1 (and score 0) where the target is no candidate: out of range, without rows, masked, or its score is not
+        finite.  total[s] is the number of candidates.  An answer depends on the sentence, its target, the table and the mask alone.
+        Works on all four tables; on a quantised one every field is bit for bit dequantized().rank(...).  out: three (S,) buffers
+        (rank, score, total) written in place.  allow= as in shortlist().  ONE tagged entry, three launches on the current stream,
+        no host synchronisation, and it can be captured in a graph (the workspace is kept per S: warm the shape once), where queries,
+        targets and the mask's contents may change in place between replays."""
+        what = "Shortlister.rank"
+        E, dtype, dev = self.E, self.dtype, self._table().device
+        if not torch.is_tensor(queries):
+            raise DrnError("%s: the queries must be a tensor" % what)
+        if queries.dim() != 2 or queries.shape[0] < 1 or queries.shape[1] != E:
+            raise DrnError("%s: the queries must be (S, %d), not %s" % (what, E, tuple(queries.shape)))
+        if queries.dtype != dtype:
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        if not queries.is_cuda or queries.device != dev:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
+        S = int(queries.shape[0])
+        out = self._check_rank(what, S, targets, out, allow)
+        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
+        seg = getattr(self, "_seg", None)
+        if seg is None:
+            ws = self._rank_ws(("rank", S), -(-len(self) // SHORTLIST_BLOCK), S)
+            ops.shortlist_rank(table, queries.contiguous(), targets, ws, *out, allow=allow)
+        else:
+            ws = self._rank_ws(("rank", S), int(seg[1].shape[0]) - 1, S)
+            ops.shortlist_segments_rank(table, queries.contiguous(), seg[0], seg[1], targets, ws, *out, allow=allow)
+        return TargetRank(*out)
+
+    def rank_late(self, queries, lengths, targets, out=None, allow=None):
+        """rank() by LATE INTERACTION -> TargetRank (late_rank_reference defines it), on the device: queries (S, L, E) and lengths
+        (S,) as in shortlist_late(), targets, out= and allow= as in rank().  rank[s] = k >= 0 exactly when
+        shortlist_late(queries, lengths, n).ids[s, k] is the target for every n > k, with the listed score's bits; a sentence without
+        a live token has no candidate (rank -1, total 0).  With one token per sentence this is rank().  Works on a ragged table,
+        plain or quantised (bit for bit dequantized().rank_late(...)); three launches, no host synchronisation, capturable in a graph
+        (the workspace is kept per S), where queries, lengths, targets and the mask's contents may change in place between replays.
+        A table without offsets is refused as in shortlist_late()."""
+        what = "Shortlister.rank_late"
+        seg = getattr(self, "_seg", None)
+        if seg is None:
+            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
+                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call rank()" % what)
+        E, dtype, dev = self.E, self.dtype, self._table().device
+        if not torch.is_tensor(queries):
+            raise DrnError("%s: the queries must be a tensor" % what)
+        if queries.dim() != 3 or queries.shape[0] < 1 or queries.shape[2] != E:
+            raise DrnError("%s: the queries must be (S, L, %d), one vector per token, not %s" % (what, E, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), int(queries.shape[1])
+        if not 1 <= L <= LATE_MAX_TOKENS:
+            raise DrnError("%s: L = %d tokens outside [1, %d]" % (what, L, LATE_MAX_TOKENS))
+        if queries.dtype != dtype:
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        if not queries.is_cuda or queries.device != dev:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
+        if not queries.is_contiguous():
+            raise DrnError("%s: the queries must be contiguous" % what)
+        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
+            raise DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor, the live tokens of each sentence" % (what, S))
+        if not lengths.is_cuda or lengths.device != dev:
+            raise DrnError("%s: lengths must be on the table's device %s (they are never read on the host)" % (what, dev))
+        out = self._check_rank(what, S, targets, out, allow)
+        ws = self._rank_ws(("rank_late", S), int(seg[1].shape[0]) - 1, S)
+        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
+        ops.shortlist_late_rank(table, queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
+        return TargetRank(*out)

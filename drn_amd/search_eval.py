@@ -12,13 +12,52 @@ import torch
 
 from . import ops
 from ._lib import DrnError
-from .metrics import recall_from_first_hits
+from .metrics import median_rank_from_ranks, mrr_from_ranks, recall_from_first_hits, recall_from_ranks
 from .store import _upload
 
 SearchRecall = collections.namedtuple("SearchRecall", "n ious topks moment video first_hits")
 SearchRecall.__doc__ = """n sentences scored at the tIoU thresholds `ious` and the depths `topks`.  moment: recall of the right moment in
 the right video, in run_evaluate's order (for iou: for topk); video: recall of the right video, one per topk, counted in the ranking
 of DISTINCT videos; first_hits (n, len(ious) + 1) int32 numpy array, ops.search_recall's rows in the order the sentences were seen."""
+
+
+ShortlistRecall = collections.namedtuple("ShortlistRecall", "n topks recall mrr median_rank ranks")
+ShortlistRecall.__doc__ = """n sentences ranked at the depths `topks`.  recall: the fraction whose target video has 0 <= rank < k, one per
+topk; mrr: the mean of 1 / (rank + 1); median_rank: the median 0-based rank -- a target that is no candidate (rank -1) is a miss at every
+depth, adds 0 to mrr and counts as infinitely deep; ranks (n,) int32 numpy array, Shortlister.rank's in the order the sentences were
+seen."""
+
+
+@torch.no_grad()
+def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=False, allow=None):
+    """How deep must a shortlist be?  batches: an iterable of (names, queries) -- names[q] the video sentence q is annotated in, queries
+    (S, E) what shortlister.rank takes -- or, with late=True, (names, queries, lengths) for shortlister.rank_late; the embeddings come
+    from the CALLER's encoder (this project has none).  Every batch's names are resolved through shortlister.names on the host before
+    anything of that batch is launched (an unknown name raises), the positions go up through one pinned non-blocking copy, and ONE
+    rank launch group runs per batch; the rank tensors are concatenated and copied ONCE, after the last batch: nothing inside the loop
+    waits for the device.  allow: None, or a packed mask shared by all sentences, (W,), passed to every batch.  topks may exceed
+    SHORTLIST_MAX: the ranks are taken in the full order.  -> ShortlistRecall; no batches: n = 0 and recalls of 0."""
+    topks = [int(k) for k in topks]
+    if not topks:
+        raise DrnError("evaluate_shortlist: at least one top-k")
+    if shortlister.names is None:
+        raise DrnError("evaluate_shortlist: the shortlister has no names to resolve the annotated videos through")
+    where = {name: v for v, name in enumerate(shortlister.names)}
+    dev, ranks = shortlister._table().device, []
+    for batch in batches:
+        names = batch[0]
+        ids = []
+        for name in names:
+            if name not in where:
+                raise DrnError("evaluate_shortlist: the shortlister has no video named %s" % (name,))
+            ids.append(where[name])
+        targets = _upload(torch.tensor(ids, dtype=torch.int32), dev)
+        if late:
+            ranks.append(shortlister.rank_late(batch[1], batch[2], targets, allow=allow).rank)
+        else:
+            ranks.append(shortlister.rank(batch[1], targets, allow=allow).rank)
+    r = torch.cat(ranks).cpu().numpy() if ranks else np.zeros((0,), dtype=np.int32)
+    return ShortlistRecall(int(r.shape[0]), topks, recall_from_ranks(r, topks), mrr_from_ranks(r), median_rank_from_ranks(r), r)
 
 
 def search_batches(loader):

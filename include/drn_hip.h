@@ -730,6 +730,33 @@ int drn_shortlist_late_topn_q8(const uint8_t* codes, const uint8_t* scales, cons
                                const int32_t* offsets, const int32_t* blk_vid, const int32_t* allow, int allow_stride, int R, int V,
                                int nblocks, int E, int S, int L, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
                                int32_t* counts, void* stream);
+/* The RANK OF A NAMED VIDEO in the full order of the three shortlists above (drn_amd/csrc/retrieve_rank.hip): targets [S] int32 on the
+ * device, never read on the host; with t = targets[s], a CANDIDATE of sentence s being a video the matching *_topn entry could list
+ * (it owns a row, its score is finite, its mask bit is set and -- late -- the sentence has a live token):
+ *   total[s] = the number of candidates of s (the length of the list, were n unbounded);
+ *   rank[s]  = the number of candidates that precede t under the total order of drn_shortlist_topn (score descending, then position
+ *              ascending), score[s] = t's score, where 0 <= t < V and t is a candidate; rank[s] = -1 and score[s] = 0 otherwise (a value
+ *              outside [0, V) is legal, is clamped for every read and means "no target").
+ * So rank[s] = k >= 0 exactly when the entry's list with any n > k holds t at place k, with score[s] there, bit for bit: the scores
+ * come from the same MFMA chain.  Counted over the WHOLE table: no cap at DRN_SHORTLIST_MAX, no list, no sort.  table is emb, or the
+ * codes of a block-scaled FP8 table with scales beside them (scales == NULL: a plain table; E % 32 == 0 with scales); dtype is that
+ * of the queries.  allow: a packed mask as in the *_allow entries, or NULL for none (allow_stride is then ignored).  queries [S][E],
+ * or [S][L][E] with lengths [S] for drn_shortlist_late_rank; offsets, blk_vid, R, V, nblocks as in drn_shortlist_segments_topn.  ws:
+ * ws_bytes >= 8 * S * (1 + blocks) bytes, 8-byte aligned, blocks = ceil(V / 256) on the plain table and nblocks on a ragged one (each
+ * sentence's target key, then two int32 counts per (sentence, block)).  Three launches -- the target keys, the block counts, one
+ * wavefront per sentence sums them -- no atomics, no host synchronisation; an answer depends on the sentence, its target, the table and
+ * the mask alone, and targets, the queries, lengths and the mask may change between replays of a captured graph. */
+int drn_shortlist_rank(const void* table, const uint8_t* scales, const void* queries, const int32_t* targets, const int32_t* allow,
+                       int allow_stride, int V, int E, int S, int dtype, void* ws, int ws_bytes, int32_t* rank, float* score,
+                       int32_t* total, void* stream);
+int drn_shortlist_segments_rank(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride, int R, int V,
+                                int nblocks, int E, int S, int dtype, void* ws, int ws_bytes, int32_t* rank, float* score, int32_t* total,
+                                void* stream);
+int drn_shortlist_late_rank(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths, const int32_t* offsets,
+                            const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride, int R, int V,
+                            int nblocks, int E, int S, int L, int dtype, void* ws, int ws_bytes, int32_t* rank, float* score,
+                            int32_t* total, void* stream);
 /* mask [S][V], one byte a video (a torch.bool tensor: non-zero = allowed) -> words [S][ceil(V / 32)], the packed mask above: every
  * word written, bits at or past V zero.  S = 1 packs a mask shared by all sentences.  One launch, nothing read back. */
 int drn_pack_allow(const uint8_t* mask, int S, int V, int32_t* words, void* stream);

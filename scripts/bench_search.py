@@ -98,7 +98,17 @@
            per 16 query rows.  Two conditions are derived, not measured, and reported shape by shape: (C1) L = 16 all live takes no longer
            than (b) at 16 S query rows beyond (b)'s max - min; (C2) L = 32 with lengths 16 takes no longer than L = 16 all live beyond the
            latter's max - min, with a control beside it: L = 16 all live once more on other random tokens.  The largest error / tolerance ratio of tests/test_late_shortlist_gpu.py's random case.  Random
-           embeddings: nothing here says anything about recall."""
+           embeddings: nothing here says anything about recall.
+
+  --rank                instead of the above -> profiles/search_rank_bench.json: Shortlister.rank (drn_shortlist_rank / _segments_rank, all
+           three launches) on R = 65,536 rows x 512 in bf16 as 65,536 x 1 and 4,096 x 16, and rank_late (drn_shortlist_late_rank) at L = 16
+           on the ragged layout, S in {1, 8, 64}; launch-inclusive us, median [min, max] of 5 interleaved rounds in one process, beside (a)
+           the shortlist of n = 16 on the same table and queries, the parent's code path, and (b) what a caller does today for depth
+           past 128: torch.matmul (plus scatter_reduce_(amax) when ragged, a sum over the tokens when late), two comparisons and sums.
+           One condition is derived, not measured, and reported HOLDS / MISSED shape by shape: (C1) rank takes no longer than (a) beyond
+           (a)'s max - min.  Agreement counts: whether every rank below 16 is the target's place in (a)'s list, and how many sentences
+           equal (b) (near-ties in bf16 may differ).  Then evaluate_shortlist on PLANTED queries -- a target's row plus noise, no trained
+           encoder -- on the plain table and on quantize="mxfp8" side by side: recall at 1 / 10 / 100 / 1000 and the median rank."""
 import argparse
 import json
 import os
@@ -1670,12 +1680,148 @@ def main_late_shortlist(args):
     print("wrote", out)
 
 
+RANK_NOISE = 6.0                                            # the planted queries: a target's row plus this many standard normals a column
+
+
+def bench_rank(emb, S, rounds):
+    """Shortlister.rank / rank_late on R = 65,536 rows as 65,536 x 1 (plain), 4,096 x 16 (ragged) and late interaction at L = 16 on the
+    ragged layout, each beside (a) the shortlist of n = 16 on the same table and queries, the parent's code path, and (b) what a caller
+    does today for depth past 128: torch.matmul (scatter_reduce_(amax) when ragged, a sum over the tokens when late), two comparisons
+    and sums.  All variants of one S take turns inside every round."""
+    import numpy as np
+    from drn_amd import Shortlister, TargetRank
+    R, E, n, L = int(emb.shape[0]), 512, 16, 16
+    lens = dict(SEGMENT_LAYOUTS)["4096x16"]
+    V2 = len(lens)
+    g = torch.Generator(device="cuda:0").manual_seed(S)
+    q = torch.randn(S, E, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    tok = torch.randn(S, L, E, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    lengths = torch.full((S,), L, dtype=torch.int32, device="cuda:0")
+    plain, seg = Shortlister(emb), Shortlister(emb, offsets=np.concatenate([[0], np.cumsum(lens)]))
+    index = torch.repeat_interleave(torch.arange(V2, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))
+    # targets: the first sentences take places 0 .. 15 of their own list, the rest any video
+    lists = {"plain": plain.shortlist(q, n), "ragged": seg.shortlist(q, n), "late": seg.shortlist_late(tok, lengths, n)}
+    targets = {}
+    for kind, short in lists.items():
+        V = R if kind == "plain" else V2
+        t = torch.randint(0, V, (S,), generator=g, device="cuda:0", dtype=torch.int32)
+        k = min(S, n)
+        t[:k] = short.ids[torch.arange(k, device="cuda:0"), torch.arange(k, device="cuda:0")]
+        targets[kind] = t.contiguous()
+    outs = {kind: TargetRank(*(plain.rank(q, targets[kind]) if kind == "plain" else seg.rank(q, targets[kind]) if kind == "ragged"
+                               else seg.rank_late(tok, lengths, targets[kind]))) for kind in lists}
+    best = torch.empty((S, V2), dtype=torch.bfloat16, device="cuda:0")
+    best_late = torch.empty((S * L, V2), dtype=torch.bfloat16, device="cuda:0")
+    where = {"plain": torch.arange(R, device="cuda:0")[None, :], "ragged": torch.arange(V2, device="cuda:0")[None, :]}
+
+    def counted(sc, t, ar):
+        ts = torch.gather(sc, 1, t.long()[:, None])
+        return ((sc > ts) | ((sc == ts) & (ar < t[:, None]))).sum(dim=1), torch.isfinite(sc).sum(dim=1)
+
+    def torch_plain():
+        return counted(torch.matmul(q, emb.t()), targets["plain"], where["plain"])
+
+    def torch_ragged():
+        best.fill_(float("-inf"))
+        best.scatter_reduce_(1, index[None].expand(S, R), torch.matmul(q, emb.t()), "amax")
+        return counted(best, targets["ragged"], where["ragged"])
+
+    def torch_late():
+        best_late.fill_(float("-inf"))
+        best_late.scatter_reduce_(1, index[None].expand(S * L, R), torch.matmul(tok.reshape(S * L, E), emb.t()), "amax")
+        return counted(best_late.view(S, L, V2).float().sum(dim=1), targets["late"], where["ragged"])
+    variants = {
+        "rank_plain": lambda: plain.rank(q, targets["plain"], out=outs["plain"]),
+        "shortlist_plain": lambda: plain.shortlist(q, n, out=lists["plain"]),
+        "torch_plain": torch_plain,
+        "rank_ragged": lambda: seg.rank(q, targets["ragged"], out=outs["ragged"]),
+        "shortlist_ragged": lambda: seg.shortlist(q, n, out=lists["ragged"]),
+        "torch_ragged": torch_ragged,
+        "rank_late": lambda: seg.rank_late(tok, lengths, targets["late"], out=outs["late"]),
+        "shortlist_late": lambda: seg.shortlist_late(tok, lengths, n, out=lists["late"]),
+        "torch_late": torch_late,
+    }
+    times, reps = interleaved_windows(variants, rounds)
+    torch_counts = {"plain": torch_plain()[0], "ragged": torch_ragged()[0], "late": torch_late()[0]}
+    rows = []
+    for kind in ("plain", "ragged", "late"):
+        r, a, b = times["rank_" + kind], times["shortlist_" + kind], times["torch_" + kind]
+        over = statistics.median(r) - statistics.median(a)
+        got, short, t = outs[kind].rank.tolist(), lists[kind].ids.tolist(), targets[kind].tolist()
+        agree_a = all((short[s][k] == t[s]) if 0 <= k < n else (t[s] not in short[s]) for s, k in enumerate(got))
+        agree_b = sum(int(x == y) for x, y in zip(got, torch_counts[kind].tolist()))
+        rows.append({"ranking": kind, "layout": "65536x1" if kind == "plain" else "4096x16", "R": R, "V": R if kind == "plain" else V2, "E": E, "S": S,
+                     "L": L if kind == "late" else None, "dtype": "bf16", "launches_per_window": {k: reps[k + "_" + kind] for k in ("rank", "shortlist", "torch")},
+                     "rank_us": spread(r), "shortlist_n16_us": spread(a), "matmul_compare_sum_us": spread(b),
+                     "C1": {"rank_minus_shortlist_us": over, "shortlist_max_minus_min_us": max(a) - min(a), "verdict": "HOLDS" if over <= max(a) - min(a) else "MISSED"},
+                     "rank_over_shortlist_n16": statistics.median(r) / statistics.median(a),
+                     "rank_over_matmul_compare_sum": statistics.median(r) / statistics.median(b),
+                     "every_rank_below_16_is_the_lists_place": agree_a, "sentences_equal_to_matmul_compare_sum": agree_b,
+                     "ranks_below_16": sum(1 for k in got if 0 <= k < n)})
+    return rows
+
+
+def rank_planted_recall(emb, sentences=256, batch=64):
+    """evaluate_shortlist on PLANTED structure -- a query is its target's row plus RANK_NOISE standard normals a column; no trained encoder
+    is involved -- on the plain table and on the same table quantised to block-scaled FP8, side by side."""
+    from drn_amd import Shortlister, evaluate_shortlist
+    R = int(emb.shape[0])
+    names = ["v%05d" % v for v in range(R)]
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    t = torch.randint(0, R, (sentences,), generator=g, device="cuda:0")
+    q = (emb[t].float() + RANK_NOISE * torch.randn(sentences, 512, generator=g, device="cuda:0")).to(torch.bfloat16).contiguous()
+    host = t.tolist()
+    batches = [([names[v] for v in host[a:a + batch]], q[a:a + batch].contiguous()) for a in range(0, sentences, batch)]
+    res = {"sentences": sentences, "noise": RANK_NOISE, "what_this_is": "planted structure (a target's row plus noise), not a trained encoder"}
+    ranks = {}
+    for kind, sl in (("bf16", Shortlister(emb, names=names)), ("mxfp8", Shortlister(emb, names=names, quantize="mxfp8"))):
+        got = evaluate_shortlist(sl, batches, topks=(1, 10, 100, 1000))
+        ranks[kind] = got.ranks
+        res[kind] = {"recall_at": dict(zip(("1", "10", "100", "1000"), got.recall)), "mrr": got.mrr, "median_rank": got.median_rank}
+    d = ranks["mxfp8"].astype("int64") - ranks["bf16"].astype("int64")
+    res["mxfp8_minus_bf16_places"] = {"mean": float(d.mean()), "largest_loss": int(d.max()), "largest_gain": int(-d.min()),
+                                      "sentences_unchanged": int((d == 0).sum())}
+    return res
+
+
+def main_rank(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_rank_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "(a) shortlist_n16: shortlist() / shortlist_late() with n = 16 on the same table and queries, the parent's code "
+                                   "unchanged; (b) matmul_compare_sum: torch.matmul (scatter_reduce_(amax) over the videos' rows when ragged, a sum "
+                                   "over the tokens when late), two comparisons and sums -- what a caller does today for depth past 128",
+                      "condition": "derived, not measured: (C1) rank does the reads and the MFMA chain of (a), counts where (a) sorts 256 keys a "
+                                   "sentence and merges, and pays one more small launch, so it may not take longer than (a) beyond (a)'s max - min",
+                      "what_this_does_not_say": "random embeddings: the timings say nothing about recall; planted_recall is planted structure, not "
+                                                "a trained encoder; no kernel-only times (no profiler run)"},
+           "rank": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for row in bench_rank(emb, S, args.rounds):
+            res["rank"].append(row)
+            print(json.dumps({"rank": row}), flush=True)
+            print("C1 %s S = %d: %s (rank / (b) = %.3f)" % (row["ranking"], S, row["C1"]["verdict"], row["rank_over_matmul_compare_sum"]), flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+    res["shapes_where_every_rank_below_16_is_the_lists_place"] = "%d of %d" % (sum(r["every_rank_below_16_is_the_lists_place"] for r in res["rank"]),
+                                                                               len(res["rank"]))
+    res["planted_recall"] = rank_planted_recall(emb)
+    print(json.dumps({"planted_recall": res["planted_recall"]}), flush=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
                                             "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
                                             "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
-                                            "--late-shortlist)")
+                                            "--late-shortlist, search_rank_bench.json with --rank)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1695,9 +1841,13 @@ def main():
                                                                       "launch and the sub-table way")
     ap.add_argument("--late-shortlist", action="store_true", help="measure Shortlister.shortlist_late at four token shapes beside shortlist() on "
                                                                   "the flattened tokens and matmul + amax + sum + topk")
+    ap.add_argument("--rank", action="store_true", help="measure Shortlister.rank / rank_late beside the shortlist of n = 16 and matmul + "
+                                                        "comparisons + sums, and evaluate_shortlist on planted queries, plain and FP8")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.rank:
+        return main_rank(args)
     if args.late_shortlist:
         return main_late_shortlist(args)
     if args.filtered_shortlist:
