@@ -25,6 +25,8 @@ SHORTLIST_BLOCK = 256     # videos one workgroup of drn_shortlist_topn's first l
 SHORTLIST_SEG_BLOCK = 256  # videos of one block of drn_shortlist_segments_topn's plan at most, and rows of one pass (SG_BLOCK)
 LATE_MAX_TOKENS = 64      # DRN_LATE_MAX_TOKENS: token vectors of one sentence of drn_shortlist_late_topn (a choice that bounds a workgroup's time)
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
+RERANK_MAX_CANDIDATES = CANDIDATES_MAX  # DRN_RERANK_MAX_CANDIDATES: columns of the list drn_shortlist_rerank takes (a CHOICE: the width the Grounder takes)
+RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
 
 
 class DrnError(RuntimeError):
@@ -201,6 +203,8 @@ SIGNATURES = {
                                     c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_late_rank": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_rerank": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_pack_allow": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }

@@ -1,0 +1,251 @@
+// RERANKING A CANDIDATE LIST (drn_amd/retrieve.py, Shortlister.rerank / rerank_late): candidates [S][C] holds, per sentence, a SET of
+// store positions as it lies on the device -- the ids of another shortlist, -1 padding, repeats and values outside [0, V) included --
+// and only the listed (sentence, video) pairs are scored:
+//   drn_shortlist_rerank   each sentence's best n LISTED videos by the late-interaction score, under the total order of retrieve.hip.
+// The answer is the full shortlist under the mask "listed, and allowed", field for field and bit for bit; the table rows of the videos
+// that are not listed are never read.
+#include "common.h"
+#include "shortlist.h"
+#include "../../include/drn_hip.h"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// This is shortlist_late_kernel (retrieve_late.hip; the passes, the segmented maximum and the states are retrieve_seg.hip's) with a
+// VIRTUAL BLOCK in the place of a block of the plan.  Workgroup (g, s) owns the RR_GROUP slots [RR_GROUP g, RR_GROUP g + RR_GROUP) of
+// sentence s's list.  It reads the sentence's whole row of candidates into LDS (C <= 1024 words, 4 KiB).  A slot of its own is LIVE when
+// its id lies in [0, V), no EARLIER slot of the whole row holds the same id (sixteen lanes a slot scan the row: of a repeated position
+// the first occurrence counts, the rule of drn_plan_candidates), the mask bit is set and the video owns a row.  A prefix sum of the
+// live slots' runs gives the group's virtual offsets, RR_GROUP + 1 words: virtual row x belongs to the slot k with voff[k] <= x <
+// voff[k + 1] (a scan of RR_GROUP entries) and is table row offsets[id_k] + (x - voff[k]); on a table without offsets the run of video
+// v is the single row v.  Every index taken from a device table is clamped, and a virtual row past the data reads some valid row whose
+// score nobody folds.  From there everything is the late kernel's: token tiles of 16 as the A operand, passes of RR_PASS virtual rows
+// through op.scores into sc, the segmented maximum into the states [token of the tile][slot], the fold in ascending token order.  A
+// live slot becomes the key sl_key(sum, id) -- the key carries the REAL store position, so the order among the listed is the full
+// shortlist's and the place in the list means nothing -- ONE row of RR_GROUP keys is sorted and its first m = min(n, RR_GROUP) go to
+// ws[s][g][0..m).  Phase two is shortlist_merge_kernel of retrieve.hip as it stands, over ceil(C / RR_GROUP) lists: the de-duplication
+// above is what keeps its premise, that no video reaches it twice.  Two launches, no atomics, no tickets.
+//
+// WHY THE BITS ARE THE FULL SHORTLISTS': an accumulator element of the chain (the table operand's scores(), AlPlain / AlQ8 of
+// shortlist.h) depends on its token row and its table row alone -- not on which rows share the MFMA tile with it -- so a (token, row)
+// dot product has the bits every other shortlist kernel gives it; the maximum over a video's rows is exact, however the rows are
+// grouped into passes and lanes; and the adds run over the live tokens in ascending order.  With L = 1 the sum is (0 + sim), the
+// best-segment score, and with one row per video the plain score.
+//
+// RR_GROUP = 16 is a CHOICE, not a measurement: one MFMA tile of rows when every run is a single row, one sorted row of 16 keys, and
+// C / 16 <= 64 workgroups a sentence.  A group whose videos are long walks them alone; balancing groups by rows is not done here.
+#define RR_GROUP DRN_RERANK_GROUP
+#define RR_PASS 256         // virtual rows of a pass = LT_BLOCK of retrieve_late.hip
+#define RR_LD (RR_PASS + 1)
+static_assert(RR_GROUP == 16, "the slot scan, the states and the sorted row are laid out for 16 slots a group");
+
+template <typename Op>
+__global__ __launch_bounds__(256) void shortlist_rerank_kernel(const Op op, const typename Op::Q* __restrict__ q, const int* __restrict__ lengths,
+                                                               const int* __restrict__ offsets, const int* __restrict__ candidates,
+                                                               const int* __restrict__ allow, const int allow_stride, const int R, const int V,
+                                                               const int E, const int L, const int C, const int m, const int nblocks,
+                                                               sl_key_t* __restrict__ ws) {
+  __shared__ int cand[DRN_RERANK_MAX_CANDIDATES];             // 4 KiB: the sentence's row of the list
+  __shared__ sl_key_t keys[16 * RR_GROUP];                    // [token of the tile][slot] states; at the end one row of keys
+  __shared__ float sc[16 * RR_LD];                            // [token of the tile][virtual row of the pass]
+  __shared__ int voff[RR_GROUP + 1];                          // the virtual offsets of the group's slots
+  __shared__ int sbase[RR_GROUP], srun[RR_GROUP], sid[RR_GROUP];   // a slot's first table row, its rows (0: not live) and its video
+  __shared__ float sums[RR_GROUP];                            // each slot's running sum over the tokens
+  __shared__ int slong;                                       // the longest run
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gb = blockIdx.x, s = blockIdx.y;
+  const int r = lane & 15, g = lane >> 4;
+  const int Lt = lengths == nullptr ? L : min(max(lengths[s], 0), L);
+  for (int i = tid; i < C; i += 256) cand[i] = candidates[(long)s * C + i];
+  keys[tid] = 0ull;                                           // (16 * RR_GROUP = 256 states)
+  if (tid < RR_GROUP) sums[tid] = 0.f;
+  __syncthreads();
+  {
+    // slot k = tid >> 4 of the group, part = tid & 15 of its scan of the EARLIER slots of the whole row
+    const int k = tid >> 4, part = tid & 15, j = RR_GROUP * gb + k;
+    const int id = j < C ? cand[j] : -1;
+    int dup = 0;
+    for (int i = part; i < min(j, C); i += 16) dup |= cand[i] == id;
+#pragma unroll
+    for (int w = 1; w < 16; w <<= 1) dup |= __shfl_xor(dup, w, 64);
+    if (part == 0) {
+      int base = 0, run = 0;
+      if (id >= 0 && id < V && !dup && (allow == nullptr || ((allow[(long)s * allow_stride + (id >> 5)] >> (id & 31)) & 1))) {
+        if (offsets == nullptr) {
+          base = min(id, R - 1);
+          run = 1;
+        } else {
+          base = min(max(offsets[id], 0), R);
+          run = min(max(offsets[id + 1], base), R) - base;
+        }
+      }
+      sbase[k] = base;
+      srun[k] = run;
+      sid[k] = id;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int at = 0, longest = 0;
+    for (int k = 0; k < RR_GROUP; ++k) {
+      voff[k] = at;
+      at += srun[k];
+      longest = max(longest, srun[k]);
+    }
+    voff[RR_GROUP] = at;
+    slong = longest;
+  }
+  __syncthreads();
+  const int longest = min(slong, RR_PASS);                    // (of one pass at most)
+  int plg = 0;                                                // P = 1 << plg lanes per (token, slot): one per 16 rows of the longest run
+  while (plg < 4 && (16 << plg) < longest) ++plg;
+  const int P = 1 << plg;
+  const int r1 = voff[RR_GROUP];                              // the group's virtual rows: [0, r1)
+  for (int t0 = 0; t0 < Lt; t0 += 16) {                       // (workgroup-uniform: Lt is the sentence's)
+    const int live = min(16, Lt - t0);
+    // (a token slot past Lt reads the last live token instead: nobody folds its scores)
+    const typename Op::Q* qrow = q + ((long)s * L + min(t0 + r, Lt - 1)) * E;
+    for (int p0 = 0; p0 < r1; p0 += RR_PASS) {
+      const int p1 = min(p0 + RR_PASS, r1), rw = p0 + wave * 64;
+      if (rw < p1) {                                          // (wave-uniform: a wave whose 64 rows lie past the data reads nothing)
+        // virtual row -> table row; one past the data reads a valid row instead: nobody folds its score
+        long row[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int x = rw + 16 * j + r;
+          int k = 0;
+#pragma unroll
+          for (int i = 1; i < RR_GROUP; ++i) k += voff[i] <= x;          // the last slot that starts at or before x
+          row[j] = min(max(sbase[k] + (x - voff[k]), 0), R - 1);
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        op.scores(qrow, row, E, g, acc);
+        // C/D: column (virtual row) lane & 15, row (token) 4 (lane >> 4) + i
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sc[(4 * g + i) * RR_LD + wave * 64 + 16 * j + r] = acc[j][i];
+      }
+      __syncthreads();
+      // the segmented maximum of retrieve_late.hip over the tile's LIVE tokens: item p = (pair p >> plg, part p & (P - 1)), pair =
+      // (token pair / RR_GROUP, slot pair % RR_GROUP); the P lanes of a pair are adjacent and aligned and leave the loop together
+      const int items = (live * RR_GROUP) << plg;
+      for (int p = tid; p < items; p += 256) {
+        const int pair = p >> plg, part = p & (P - 1);
+        const int tl = pair / RR_GROUP, vi = pair - tl * RR_GROUP;
+        const int base = voff[vi], lo = max(base, p0), hi = min(voff[vi + 1], p1);
+        const int share = (max(hi - lo, 0) + P - 1) >> plg;
+        const int from = lo + part * share, to = min(from + share, hi);
+        const float* mine = sc + tl * RR_LD;
+        sl_key_t best = 0ull;
+        for (int x = from; x < to; ++x) {
+          const float d = mine[x - p0];
+          const unsigned o = d != d ? 0xffffffffu : sl_word(d);
+          const sl_key_t c = ((sl_key_t)o << 32) | (sl_key_t)(~(unsigned)(x - base));
+          best = c > best ? c : best;
+        }
+        for (int d = 1; d < P; d <<= 1) {
+          const sl_key_t other = __shfl_xor(best, d, 64);
+          best = other > best ? other : best;
+        }
+        if (part == 0 && best != 0ull) {
+          const sl_key_t had = keys[tl * RR_GROUP + vi];
+          keys[tl * RR_GROUP + vi] = best > had ? best : had;
+        }
+      }
+      __syncthreads();
+    }
+    // the fold of retrieve_late.hip: the slot's thread adds the tile's live tokens in ascending t and clears their states
+    if (tid < RR_GROUP) {
+      float sum = sums[tid];
+      for (int tl = 0; tl < live; ++tl) {
+        sum += sl_score(keys[tl * RR_GROUP + tid]);
+        keys[tl * RR_GROUP + tid] = 0ull;
+      }
+      sums[tid] = sum;
+    }
+    __syncthreads();
+  }
+  // sums -> ONE row of keys with the REAL store positions (every state is zero again: the row is written whole).  sl_key makes no key
+  // of a sum that is not finite; a slot that is not live (srun == 0: out of range, repeated, masked or without rows) becomes no key.
+  if (tid < RR_GROUP) keys[tid] = (srun[tid] > 0 && Lt > 0) ? sl_key(sums[tid], sid[tid]) : 0ull;
+  __syncthreads();
+  sl_sort_desc<RR_GROUP, 256>(keys, 1, tid);
+  for (int i = tid; i < m; i += 256) ws[((long)s * nblocks + gb) * m + i] = keys[i];          // (m <= RR_GROUP)
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The entry: one argument record, one list of checks (lt_check's of retrieve_late.hip), one launch switch.
+
+struct RrArgs {
+  const void* table;                                          // emb, or the codes
+  const uint8_t* scales;                                      // null: a plain table
+  const void* queries;
+  const int32_t *lengths, *offsets, *candidates, *allow;      // (lengths, offsets and allow may be null)
+  int allow_stride, R, V, E, S, L, C, n, dtype;
+  void* ws;
+  int ws_keys;
+  int32_t* ids;
+  float* scores;
+  int32_t* counts;
+};
+
+static int rr_check(const char* what, const RrArgs& a) {
+  DRN_CHECK_ARG(a.table && a.queries && a.candidates && a.ws && a.ids && a.scores && a.counts, "%s: null pointer", what);
+  DRN_CHECK_ARG(a.R >= 1 && a.V >= 1 && a.E >= 1 && a.S >= 1, "%s: bad args (R = %d rows, V = %d videos, E = %d columns, S = %d sentences)", what,
+                a.R, a.V, a.E, a.S);
+  DRN_CHECK_ARG(a.offsets || a.R == a.V, "%s: without offsets row v is video v, but R = %d rows and V = %d videos", what, a.R, a.V);
+  DRN_CHECK_ARG(a.L >= 1 && a.L <= DRN_LATE_MAX_TOKENS, "%s: L = %d tokens outside [1, %d]", what, a.L, DRN_LATE_MAX_TOKENS);
+  DRN_CHECK_ARG(a.C >= 1 && a.C <= DRN_RERANK_MAX_CANDIDATES, "%s: C = %d candidates a sentence outside [1, %d]", what, a.C,
+                DRN_RERANK_MAX_CANDIDATES);
+  if (a.scales) DRN_CHECK_ARG(a.E % MX8_BLOCK == 0, "%s: E = %d is not a multiple of the block of %d columns", what, a.E, MX8_BLOCK);
+  DRN_CHECK_ARG(a.n >= 1 && a.n <= DRN_SHORTLIST_MAX, "%s: n = %d outside [1, %d]", what, a.n, DRN_SHORTLIST_MAX);
+  DRN_CHECK_ARG(a.dtype == DRN_F32 || a.dtype == DRN_BF16, "%s: dtype %d (float32 / bfloat16 only)", what, a.dtype);
+  // (the chain loads 16 bytes at once only where E makes every row, a token's among them, a multiple of 16 bytes)
+  DRN_CHECK_ARG(((uintptr_t)a.table & 15) == 0 && ((uintptr_t)a.queries & 15) == 0 && ((uintptr_t)a.ws & 7) == 0,
+                "%s: the table and the queries must be 16-byte aligned, the workspace 8-byte aligned", what);
+  DRN_CHECK_ARG(((uintptr_t)a.lengths & 3) == 0 && ((uintptr_t)a.offsets & 3) == 0 && ((uintptr_t)a.candidates & 3) == 0,
+                "%s: lengths, offsets and candidates must be 4-byte aligned", what);
+  if (a.allow) {
+    DRN_CHECK_ARG(a.allow_stride == 0 || a.allow_stride == cdiv(a.V, 32),
+                  "%s: allow_stride = %d is neither 0 (one mask for all sentences) nor ceil(V / 32) = %d (one row per sentence)", what,
+                  a.allow_stride, cdiv(a.V, 32));
+    DRN_CHECK_ARG(((uintptr_t)a.allow & 3) == 0, "%s: the mask must be 4-byte aligned", what);
+  }
+  const int m = a.n < RR_GROUP ? a.n : RR_GROUP;
+  const long need = (long)a.S * cdiv(a.C, RR_GROUP) * m;
+  DRN_CHECK_ARG(need <= 0x7fffffffL && a.ws_keys >= need, "%s: the workspace holds %d keys, %ld are needed (S * ceil(C / %d) * min(n, %d))", what,
+                a.ws_keys, need, RR_GROUP, RR_GROUP);
+  DRN_CHECK_ARG(a.S <= 65535, "%s: S = %d, more than 65535 sentences", what, a.S);
+  return DRN_OK;
+}
+
+// phase one with the operand Op, then the merge of the other shortlists
+template <typename Op>
+static void rr_launch(const Op op, const RrArgs& a, hipStream_t stream) {
+  typedef typename Op::Q Q;
+  const int m = a.n < RR_GROUP ? a.n : RR_GROUP, nblocks = cdiv(a.C, RR_GROUP);
+  const dim3 grid(nblocks, a.S);
+  sl_key_t* lists = (sl_key_t*)a.ws;
+  shortlist_rerank_kernel<Op><<<grid, 256, 0, stream>>>(op, (const Q*)a.queries, a.lengths, a.offsets, a.candidates, a.allow,
+                                                         a.allow ? a.allow_stride : 0, a.R, a.V, a.E, a.L, a.C, m, nblocks, lists);
+  sl_launch_merge(lists, a.S, a.n, m, nblocks, a.ids, a.scores, a.counts, stream);
+}
+
+extern "C" int drn_shortlist_rerank(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths,
+                                    const int32_t* offsets, const int32_t* candidates, const int32_t* allow, int allow_stride, int R, int V,
+                                    int E, int S, int L, int C, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
+                                    int32_t* counts, void* stream) {
+  const char* what = "drn_shortlist_rerank";
+  const RrArgs a = {table, scales, queries, lengths, offsets, candidates, allow, allow_stride, R, V, E, S, L, C, n, dtype, ws, ws_keys,
+                    ids, scores, counts};
+  drn_clear_status();
+  if (const int rc = rr_check(what, a)) return rc;
+  const bool bf16 = dtype == DRN_BF16;
+  // (a quantised chain keeps one scale block of loads in flight, as in retrieve_late.hip)
+  if (!scales && bf16) rr_launch(AlPlain<bf16_t>{(const bf16_t*)table}, a, (hipStream_t)stream);
+  else if (!scales) rr_launch(AlPlain<float>{(const float*)table}, a, (hipStream_t)stream);
+  else if (bf16) rr_launch(AlQ8<bf16_t, 1>{(const uint8_t*)table, scales}, a, (hipStream_t)stream);
+  else rr_launch(AlQ8<float, 1>{(const uint8_t*)table, scales}, a, (hipStream_t)stream);
+  return drn_launch_status(what);
+}

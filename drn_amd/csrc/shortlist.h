@@ -5,6 +5,7 @@
 // ranks all four under an allow mask: the plain chain, and the FP8 chain sq_scores below, which it shares with retrieve_q8.hip.
 // retrieve_late.hip ranks the ragged tables by late interaction (per-token queries) on the table operands AlPlain / AlQ8 below.
 // retrieve_rank.hip counts, on the same operands and keys, the videos that precede a named one: no sort, no list.
+// retrieve_rerank.hip scores, on the same operands, keys and merge, only the (sentence, video) pairs a candidate list names.
 #pragma once
 #include "common.h"
 #include "mx8.h"

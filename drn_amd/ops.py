@@ -1917,6 +1917,54 @@ def shortlist_late_rank(table, queries, lengths, offsets, blk_vid, targets, ws, 
     return rank, score, total
 
 
+def shortlist_rerank_ws_keys(C, S, n):
+    """The 8-byte keys of workspace drn_shortlist_rerank needs: S * ceil(C / RERANK_GROUP) * min(n, RERANK_GROUP)."""
+    return int(S) * (-(-int(C) // _lib.RERANK_GROUP)) * min(int(n), _lib.RERANK_GROUP)
+
+
+def shortlist_rerank(table, queries, lengths, offsets, candidates, n, ws, ids, scores, counts, allow=None):
+    """Rerank a candidate list: only the listed (sentence, video) pairs are scored (drn_shortlist_rerank; the *_rerank_reference
+    functions of drn_amd.retrieve are the definition).  table is emb (R, E), float32 / bfloat16, or a pair (codes, scales) of a
+    block-scaled FP8 table; queries (S, L, E) of the table's dtype (float32 / bfloat16 beside codes), 1 <= L <= LATE_MAX_TOKENS;
+    lengths (S,) int32 on the device as in shortlist_late_topn, or None: every token is live; offsets (V + 1,) int32 on the device as
+    in shortlist_segments_topn, or None: row v is video v; candidates (S, C) int32 ON THE DEVICE, 1 <= C <= RERANK_MAX_CANDIDATES, row
+    s the set of positions sentence s may list -- an entry outside [0, V) means nothing, a repeat counts once -> ids, scores (S, n) and
+    counts (S,), written in place, bit for bit what shortlist_late_topn gives under the mask "listed, and allowed".  allow: None, or a
+    packed mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_rerank_ws_keys(C, S, n) elements.  Two launches
+    on the current stream behind one entry (one tag, shortlist_rerank); nothing is read on the host -- so the flop figure handed to
+    the timer is NOMINAL, 2 S L C (R / V) E: every slot a distinct valid video of the mean run, which the host cannot know."""
+    what = "shortlist_rerank"
+    if queries.dim() != 3 or not queries.is_contiguous() or not 1 <= queries.shape[1] <= _lib.LATE_MAX_TOKENS or queries.shape[0] < 1:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, L, E) tensor with S >= 1 and 1 <= L <= %d, not %s"
+                            % (what, _lib.LATE_MAX_TOKENS, tuple(queries.shape)))
+    S, L = int(queries.shape[0]), int(queries.shape[1])
+    tensors, tab, scl, R, E = _rank_table(what, table, queries.view(S * L, -1))
+    _need_gpu(*(tensors + (queries, candidates, ws, ids, scores, counts)
+                + tuple(t for t in (lengths, offsets, allow) if t is not None)))
+    n = int(n)
+    if lengths is not None and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous()):
+        raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
+    if offsets is None:
+        V = R
+    else:
+        if offsets.dim() != 1 or offsets.numel() < 2 or offsets.dtype != torch.int32 or not offsets.is_contiguous():
+            raise _lib.DrnError("%s: offsets must be a contiguous (V + 1,) torch.int32 tensor, V >= 1" % what)
+        V = int(offsets.numel()) - 1
+    if candidates.dim() != 2 or candidates.dtype != torch.int32 or not candidates.is_contiguous() or int(candidates.shape[0]) != S \
+            or not 1 <= candidates.shape[1] <= _lib.RERANK_MAX_CANDIDATES:
+        raise _lib.DrnError("%s: candidates must be a contiguous (%d, C) torch.int32 tensor with 1 <= C <= %d, not %s %s"
+                            % (what, S, _lib.RERANK_MAX_CANDIDATES, candidates.dtype, tuple(candidates.shape)))
+    C = int(candidates.shape[1])
+    _shortlist_buffers(what, S, n, shortlist_rerank_ws_keys(C, S, n), ws, ids, scores, counts)
+    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
+    mask = None if allow is None else _p(allow)
+    _timed(what, 2.0 * S * L * C * (float(R) / V) * E, lambda: check(lib().drn_shortlist_rerank(
+        tab, scl, _p(queries), None if lengths is None else _p(lengths), None if offsets is None else _p(offsets), _p(candidates), mask,
+        stride, R, V, E, S, L, C, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts),
+        _stream()), "drn_shortlist_rerank"))
+    return ids, scores, counts
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -34,7 +34,14 @@ Shortlister.rank and rank_late answer what a list of at most SHORTLIST_MAX canno
 many candidates precede targets[s], over the whole table, with its score and the number of candidates -- from the kernels' own scores
 and total order, without a list, a sort or a host read.  rank_reference, segment_rank_reference and late_rank_reference are the
 definitions, drn_shortlist_rank / _segments_rank / _late_rank (csrc/retrieve_rank.hip) the launches, on all the tables above, with or
-without a mask; drn_amd.search_eval.evaluate_shortlist turns the ranks of annotated sentences into recall at any depth."""
+without a mask; drn_amd.search_eval.evaluate_shortlist turns the ranks of annotated sentences into recall at any depth.
+
+Shortlister.rerank and rerank_late are the SECOND stage of a cascade: they take another shortlist's ids as they lie on the device --
+candidates_mask defines what such a tensor means: a set per sentence, -1 and out-of-range entries meaning nothing, repeats counting
+once -- and score only the listed (sentence, video) pairs, with the bits and the total order of the full filtered shortlists.
+rerank_reference, segment_rerank_reference and late_rerank_reference are the definitions (the existing ones under the mask "listed, and
+allowed"), drn_shortlist_rerank (csrc/retrieve_rerank.hip) the one launch, on all the tables above; a coarse table, a fine rerank and
+Grounder.search(candidates=) never leave the device, and drn_amd.search_eval.evaluate_cascade says what depth the coarse stage needs."""
 import collections
 import numbers
 
@@ -42,7 +49,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import LATE_MAX_TOKENS, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from ._lib import LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
@@ -142,6 +149,56 @@ def late_rank_reference(embeddings, offsets, queries, lengths, targets, allow=No
     the sum over the live tokens of its best row and is a candidate when it owns a row, the sum is finite, allow does not exclude it
     and the sentence has a live token (one without has total = 0 and rank = -1).  -> TargetRank."""
     return _ranked(*_late_scores(embeddings, offsets, queries, lengths, allow), targets)
+
+
+def candidates_mask(candidates, V):
+    """THE DEFINITION of what a candidates tensor means (usable on the CPU): candidates (S, C) integers, row s = the SET of store
+    positions sentence s may list -> bool (S, V) on its device, mask[s, v] true iff some column of row s equals v.  An entry outside
+    [0, V) means nothing -- the -1 padding of a Shortlist is one -- and a position listed twice counts once; the order of a row means
+    nothing.  This is the meaning Grounder.search gives a device candidates tensor."""
+    if not torch.is_tensor(candidates) or candidates.dim() != 2 or candidates.is_floating_point() or candidates.is_complex() \
+            or candidates.dtype == torch.bool:
+        raise DrnError("candidates_mask: candidates must be an integer tensor (S, C), a row of store positions per sentence")
+    V = int(V)
+    c = candidates.to(torch.int64)
+    S = int(c.shape[0])
+    valid = (c >= 0) & (c < V)
+    mask = torch.zeros((S, V + 1), dtype=torch.bool, device=c.device)            # (column V collects what means nothing)
+    mask.scatter_(1, torch.where(valid, c, torch.full_like(c, V)), torch.ones_like(valid))
+    return mask[:, :V].contiguous()
+
+
+def _listed_and_allowed(candidates, S, V, allow, device):
+    """candidates_mask(candidates, V) & allow, the mask of a rerank reference -> bool (S, V)."""
+    mask = candidates_mask(candidates, V).to(device)
+    if int(mask.shape[0]) != S:
+        raise DrnError("rerank reference: %d rows of candidates for %d sentences" % (int(mask.shape[0]), S))
+    return mask if allow is None else mask & _allowed(allow, S, V, device)
+
+
+def rerank_reference(embeddings, candidates, queries, n, allow=None):
+    """THE DEFINITION of a reranked list on a table of one row per video, in float64 (usable on the CPU): shortlist_reference with
+    allow replaced by candidates_mask(candidates, V) & allow.  Score, candidate-hood (finite score, listed, allowed) and the total
+    order (score descending, then store position ascending) are shortlist_reference's: the order of the input list means nothing, and
+    ties fall by store position, not by place in the list.  n > C is legal: past the list ids = -1 and scores = 0.  -> Shortlist."""
+    V, S = int(embeddings.shape[0]), int(queries.shape[0])
+    return shortlist_reference(embeddings, queries, n, allow=_listed_and_allowed(candidates, S, V, allow, embeddings.device))
+
+
+def segment_rerank_reference(embeddings, offsets, candidates, queries, n, allow=None):
+    """rerank_reference on a RAGGED table: segment_shortlist_reference with allow replaced by candidates_mask(candidates, V) & allow,
+    without its rows -- a listed video scores by its best row and is a candidate when it owns one.  -> Shortlist."""
+    V, S = len(offsets) - 1, int(queries.shape[0])
+    out = segment_shortlist_reference(embeddings, offsets, queries, n, allow=_listed_and_allowed(candidates, S, V, allow, embeddings.device))
+    return Shortlist(out.ids, out.scores, out.n)
+
+
+def late_rerank_reference(embeddings, offsets, candidates, queries, lengths, n, allow=None):
+    """rerank_reference by LATE INTERACTION: late_shortlist_reference with allow replaced by candidates_mask(candidates, V) & allow
+    (queries (S, L, E), lengths (S,); a sentence without a live token lists nothing).  -> Shortlist."""
+    V, S = len(offsets) - 1, int(queries.shape[0])
+    return late_shortlist_reference(embeddings, offsets, queries, lengths, n,
+                                    allow=_listed_and_allowed(candidates, S, V, allow, embeddings.device))
 
 
 SegmentShortlist = collections.namedtuple("SegmentShortlist", "ids scores n rows")
@@ -666,27 +723,8 @@ class Shortlister(object):
         if seg is None:
             raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
                            "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call shortlist()" % what)
-        E, dtype, dev = self.E, self.dtype, self._table().device
-        if not torch.is_tensor(queries):
-            raise DrnError("%s: the queries must be a tensor" % what)
-        if queries.dim() != 3 or queries.shape[0] < 1 or queries.shape[2] != E:
-            raise DrnError("%s: the queries must be (S, L, %d), one vector per token, not %s" % (what, E, tuple(queries.shape)))
-        S, L = int(queries.shape[0]), int(queries.shape[1])
-        if not 1 <= L <= LATE_MAX_TOKENS:
-            raise DrnError("%s: L = %d tokens outside [1, %d]" % (what, L, LATE_MAX_TOKENS))
-        if queries.dtype != dtype:
-            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
-        n = int(n)
-        if not 1 <= n <= SHORTLIST_MAX:
-            raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
-        if not queries.is_cuda or queries.device != dev:
-            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
-        if not queries.is_contiguous():
-            raise DrnError("%s: the queries must be contiguous" % what)
-        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
-            raise DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor, the live tokens of each sentence" % (what, S))
-        if not lengths.is_cuda or lengths.device != dev:
-            raise DrnError("%s: lengths must be on the table's device %s (they are never read on the host)" % (what, dev))
+        dev = self._table().device
+        S, L, n = self._check_late(what, queries, lengths, n)
         if out is not None:
             if len(out) != 3:
                 raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
@@ -705,6 +743,129 @@ class Shortlister(object):
         table = self.embeddings if self.quantize is None else (self.codes, self.scales)
         ops.shortlist_late_topn(table, queries, lengths, seg[0], seg[1], n, ws, *out, allow=allow)
         return Shortlist(*out)
+
+    def _check_late(self, what, queries, lengths, n=None):
+        """What shortlist_late, rank_late and rerank_late refuse about per-token queries, lengths and (where given) n, before the
+        library is reached -> (S, L, n)."""
+        E, dtype, dev = self.E, self.dtype, self._table().device
+        if not torch.is_tensor(queries):
+            raise DrnError("%s: the queries must be a tensor" % what)
+        if queries.dim() != 3 or queries.shape[0] < 1 or queries.shape[2] != E:
+            raise DrnError("%s: the queries must be (S, L, %d), one vector per token, not %s" % (what, E, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), int(queries.shape[1])
+        if not 1 <= L <= LATE_MAX_TOKENS:
+            raise DrnError("%s: L = %d tokens outside [1, %d]" % (what, L, LATE_MAX_TOKENS))
+        if queries.dtype != dtype:
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        if n is not None:
+            n = int(n)
+            if not 1 <= n <= SHORTLIST_MAX:
+                raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
+        if not queries.is_cuda or queries.device != dev:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
+        if not queries.is_contiguous():
+            raise DrnError("%s: the queries must be contiguous" % what)
+        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
+            raise DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor, the live tokens of each sentence" % (what, S))
+        if not lengths.is_cuda or lengths.device != dev:
+            raise DrnError("%s: lengths must be on the table's device %s (they are never read on the host)" % (what, dev))
+        return S, L, n
+
+    def _check_candidates(self, what, candidates, n):
+        """What rerank and rerank_late refuse about the table's device, the list and n, before the library is reached -> (S, C, n)."""
+        dev = self._table().device
+        if not self._table().is_cuda:
+            raise DrnError("%s: the table must be on the GPU; there is no CPU fallback" % what)
+        if not torch.is_tensor(candidates):
+            raise DrnError("%s: candidates must be a tensor (the ids of a Shortlist can be passed as they are)" % what)
+        if candidates.dtype != torch.int32:
+            raise DrnError("%s: candidates must be torch.int32 store positions, not %s" % (what, candidates.dtype))
+        if candidates.dim() != 2 or candidates.shape[0] < 1:
+            raise DrnError("%s: candidates must be (S, C), a row of store positions per sentence, not %s" % (what, tuple(candidates.shape)))
+        S, C = int(candidates.shape[0]), int(candidates.shape[1])
+        if not 1 <= C <= RERANK_MAX_CANDIDATES:
+            raise DrnError("%s: C = %d candidates a sentence outside [1, %d]" % (what, C, RERANK_MAX_CANDIDATES))
+        if not candidates.is_cuda or candidates.device != dev:
+            raise DrnError("%s: candidates must be on the table's device %s (they are never read on the host)" % (what, dev))
+        if not candidates.is_contiguous():
+            raise DrnError("%s: candidates must be contiguous" % what)
+        n = min(C, SHORTLIST_MAX) if n is None else int(n)
+        if not 1 <= n <= SHORTLIST_MAX:
+            raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
+        return S, C, n
+
+    def _rerank(self, what, S, C, n, candidates, queries, lengths, out, allow):
+        """What rerank and rerank_late share once their tensors are checked: out=, allow=, the workspace and the launch."""
+        dev = self._table().device
+        if out is not None:
+            if len(out) != 3:
+                raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
+            for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
+                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+        if allow is not None:
+            self._check_allow(allow, S)
+        if out is None:
+            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
+                   torch.empty((S,), dtype=torch.int32, device=dev))
+        ws = self._ws.get(("rerank", S, C, n))
+        if ws is None:
+            ws = self._ws[("rerank", S, C, n)] = torch.empty(ops.shortlist_rerank_ws_keys(C, S, n), dtype=torch.int64, device=dev)
+        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
+        seg = getattr(self, "_seg", None)
+        ops.shortlist_rerank(table, queries, lengths, None if seg is None else seg[0], candidates, n, ws, *out, allow=allow)
+        return Shortlist(*out)
+
+    def rerank(self, candidates, queries, n=None, out=None, allow=None):
+        """RERANK A CANDIDATE LIST: score only the listed (sentence, video) pairs -> Shortlist, on the device (rerank_reference
+        defines it; on a ragged table segment_rerank_reference, a video scoring by its best row).  candidates: contiguous int32 (S, C)
+        on the table's device, 1 <= C <= RERANK_MAX_CANDIDATES, row s the SET of store positions sentence s may list
+        (candidates_mask defines it): NEVER read on the host; a value outside [0, V) means nothing, a repeat counts once, and the
+        order of a row means nothing -- Shortlist.ids and SegmentShortlist.ids of any other Shortlister over the same store positions
+        can be passed as they are, -1 padding included.  queries, out= (three buffers: ids, scores, n) and allow= as in shortlist();
+        n: None means min(C, SHORTLIST_MAX), otherwise 1 <= n <= SHORTLIST_MAX, and n > C is legal (the rest is padding).
+
+        Every field equals, bit for bit, the filtered call over the whole table, shortlist(queries, n,
+        allow=pack_allow(candidates_mask(candidates, V) [& allow])) without its rows -- a score has the bits the full shortlist gives
+        that pair, and ties fall by store position, not by place in the list -- but only the rows of the listed videos are read.
+        Consequently rerank(shortlist(q, n).ids, q, n) is shortlist(q, n).  An answer depends on the sentence, the SET of its valid
+        candidates, the table and the mask alone: not on the list's order, its padding, repeats, C, S, the other sentences' lists or n
+        (beyond the cut).  Works on all four tables and returns a Shortlist on every one: the winning segment (rows) of a ragged
+        table is NOT reported here.  On a quantised table every field is bit for bit dequantized().rerank(...).  ONE tagged entry, two
+        launches on the current stream, no host synchronisation, and it can be captured in a graph (the workspace is kept per
+        ("rerank", S, C, n): warm the shape once before capturing), where candidates, the queries and the mask's contents may change
+        in place between replays."""
+        what = "Shortlister.rerank"
+        S, C, n = self._check_candidates(what, candidates, n)
+        E, dtype, dev = self.E, self.dtype, self._table().device
+        if not torch.is_tensor(queries):
+            raise DrnError("%s: the queries must be a tensor" % what)
+        if queries.dim() != 2 or queries.shape[0] != S or queries.shape[1] != E:
+            raise DrnError("%s: the queries must be (%d, %d), a row per row of candidates, not %s" % (what, S, E, tuple(queries.shape)))
+        if queries.dtype != dtype:
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        if not queries.is_cuda or queries.device != dev:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
+        return self._rerank(what, S, C, n, candidates, queries.contiguous().view(S, 1, E), None, out, allow)
+
+    def rerank_late(self, candidates, queries, lengths, n=None, out=None, allow=None):
+        """rerank() by LATE INTERACTION -> Shortlist (late_rerank_reference defines it), on the device: candidates and n as in
+        rerank(), queries (S, L, E) and lengths (S,) as in shortlist_late(), out= and allow= as there.  Every field equals, bit for
+        bit, shortlist_late(queries, lengths, n, allow=pack_allow(candidates_mask(candidates, V) [& allow])), reading the rows of the
+        listed videos alone; with one token per sentence this is rerank().  The promises of rerank() hold: the answer depends on the
+        sentence, the set of its valid candidates, the table and the mask alone.  Works on a ragged table, plain or quantised (bit
+        for bit dequantized().rerank_late(...)); two launches, no host synchronisation, capturable in a graph (the workspace is kept
+        per ("rerank", S, C, n)), where candidates, queries, lengths and the mask's contents may change in place between replays.  A
+        table without offsets is refused as in shortlist_late()."""
+        what = "Shortlister.rerank_late"
+        if getattr(self, "_seg", None) is None:
+            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
+                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call rerank()" % what)
+        S, C, n = self._check_candidates(what, candidates, n)
+        Sq, _, _ = self._check_late(what, queries, lengths)
+        if Sq != S:
+            raise DrnError("%s: the queries hold %d sentences, candidates has %d rows" % (what, Sq, S))
+        return self._rerank(what, S, C, n, candidates, queries, lengths, out, allow)
 
     def _check_rank(self, what, S, targets, out, allow):
         """What rank() and rank_late() refuse about targets, out= and allow=, before the library is reached -> out, made where None."""
@@ -779,24 +940,7 @@ class Shortlister(object):
         if seg is None:
             raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
                            "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call rank()" % what)
-        E, dtype, dev = self.E, self.dtype, self._table().device
-        if not torch.is_tensor(queries):
-            raise DrnError("%s: the queries must be a tensor" % what)
-        if queries.dim() != 3 or queries.shape[0] < 1 or queries.shape[2] != E:
-            raise DrnError("%s: the queries must be (S, L, %d), one vector per token, not %s" % (what, E, tuple(queries.shape)))
-        S, L = int(queries.shape[0]), int(queries.shape[1])
-        if not 1 <= L <= LATE_MAX_TOKENS:
-            raise DrnError("%s: L = %d tokens outside [1, %d]" % (what, L, LATE_MAX_TOKENS))
-        if queries.dtype != dtype:
-            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
-        if not queries.is_cuda or queries.device != dev:
-            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
-        if not queries.is_contiguous():
-            raise DrnError("%s: the queries must be contiguous" % what)
-        if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
-            raise DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor, the live tokens of each sentence" % (what, S))
-        if not lengths.is_cuda or lengths.device != dev:
-            raise DrnError("%s: lengths must be on the table's device %s (they are never read on the host)" % (what, dev))
+        S, L, _ = self._check_late(what, queries, lengths)
         out = self._check_rank(what, S, targets, out, allow)
         ws = self._rank_ws(("rank_late", S), int(seg[1].shape[0]) - 1, S)
         table = self.embeddings if self.quantize is None else (self.codes, self.scales)

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import DrnError
+from ._lib import SHORTLIST_MAX, DrnError
 from .metrics import median_rank_from_ranks, mrr_from_ranks, recall_from_first_hits, recall_from_ranks
 from .store import _upload
 
@@ -56,6 +56,45 @@ def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=Fals
             ranks.append(shortlister.rank_late(batch[1], batch[2], targets, allow=allow).rank)
         else:
             ranks.append(shortlister.rank(batch[1], targets, allow=allow).rank)
+    r = torch.cat(ranks).cpu().numpy() if ranks else np.zeros((0,), dtype=np.int32)
+    return ShortlistRecall(int(r.shape[0]), topks, recall_from_ranks(r, topks), mrr_from_ranks(r), median_rank_from_ranks(r), r)
+
+
+@torch.no_grad()
+def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=False, allow=None):
+    """How deep must the COARSE stage of a cascade be?  coarse and fine: two Shortlisters over the same store positions
+    (coarse.names == fine.names, refused otherwise) -- a cheap table, pooled or quantised, and the table the second stage reranks.
+    batches: an iterable of (names, coarse_queries, fine_queries) -- names[q] the video sentence q is annotated in -- or, with
+    late=True, (names, coarse_queries, fine_queries, lengths) for fine.rerank_late; the embeddings come from the CALLER's encoders.
+    Per batch: coarse.shortlist(coarse_queries, depth).ids, then fine.rerank / rerank_late(ids, ..., n=depth), and the target's rank
+    is its place in the reranked list, -1 where it is not listed (the coarse stage missed it, or it is no candidate of the fine one).
+    1 <= depth <= SHORTLIST_MAX, refused otherwise; a topk > depth is legal and SATURATES: no rank reaches depth, so its recall is
+    the recall at depth.  Names are resolved on the host before the batch's first launch, the rank is plain torch on the device, and
+    the ranks are copied ONCE, after the last batch: nothing inside the loop waits for the device.  allow: None, or a packed mask
+    shared by all sentences, (W,), passed to both stages.  -> ShortlistRecall; no batches: n = 0 and recalls of 0."""
+    topks, depth = [int(k) for k in topks], int(depth)
+    if not topks:
+        raise DrnError("evaluate_cascade: at least one top-k")
+    if coarse.names is None or coarse.names != fine.names:
+        raise DrnError("evaluate_cascade: the coarse and the fine table must carry the same names, position by position")
+    if not 1 <= depth <= SHORTLIST_MAX:
+        raise DrnError("evaluate_cascade: depth = %d outside [1, %d]" % (depth, SHORTLIST_MAX))
+    where = {name: v for v, name in enumerate(fine.names)}
+    dev, ranks = fine._table().device, []
+    for batch in batches:
+        ids = []
+        for name in batch[0]:
+            if name not in where:
+                raise DrnError("evaluate_cascade: the tables have no video named %s" % (name,))
+            ids.append(where[name])
+        targets = _upload(torch.tensor(ids, dtype=torch.int32), dev)
+        listed = coarse.shortlist(batch[1], depth, allow=allow).ids
+        if late:
+            reranked = fine.rerank_late(listed, batch[2], batch[3], n=depth, allow=allow).ids
+        else:
+            reranked = fine.rerank(listed, batch[2], n=depth, allow=allow).ids
+        hit = reranked == targets[:, None]
+        ranks.append(torch.where(hit.any(dim=1), hit.int().argmax(dim=1), torch.full_like(targets, -1, dtype=torch.int64)).to(torch.int32))
     r = torch.cat(ranks).cpu().numpy() if ranks else np.zeros((0,), dtype=np.int32)
     return ShortlistRecall(int(r.shape[0]), topks, recall_from_ranks(r, topks), mrr_from_ranks(r), median_rank_from_ranks(r), r)
 

@@ -757,6 +757,28 @@ int drn_shortlist_late_rank(const void* table, const uint8_t* scales, const void
                             const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride, int R, int V,
                             int nblocks, int E, int S, int L, int dtype, void* ws, int ws_bytes, int32_t* rank, float* score,
                             int32_t* total, void* stream);
+/* RERANK A CANDIDATE LIST (drn_amd/csrc/retrieve_rerank.hip): candidates [S][C] int32 on the device, never read on the host, row s =
+ * sentence s's SET of store positions: an entry outside [0, V) is no candidate (the -1 padding of a shortlist is one), and of a position
+ * repeated in a row the first occurrence counts, across the whole row.  Only the listed (sentence, video) pairs are scored -- the rows
+ * of the listed videos are the only table rows read -- and the answer is, field for field and bit for bit, what the matching *_topn
+ * entry gives over the whole table under the mask "listed, and allowed": score[s][v] is drn_shortlist_late_topn's (the sum over the live
+ * tokens, in ascending order, of the token's best row of v; with L = 1 that is drn_shortlist_segments_topn's score, and on a table of
+ * one row per video drn_shortlist_topn's), a candidate owns a row, has a finite score and a set mask bit, the sentence has a live token,
+ * and the order is drn_shortlist_topn's total order by STORE POSITION: the place of a video in the list means nothing.  table is emb,
+ * or the codes of a block-scaled FP8 table with scales beside them (scales == NULL: a plain table; E % 32 == 0 with scales); dtype is
+ * that of the queries [S][L][E].  lengths [S] as in drn_shortlist_late_topn, or NULL: every token is live.  offsets [V + 1] as in
+ * drn_shortlist_segments_topn, or NULL: row v is video v (R == V).  allow: a packed mask as in the *_allow entries, or NULL for none
+ * (allow_stride is then ignored).  1 <= C <= DRN_RERANK_MAX_CANDIDATES (a choice: the width of the candidates tensor
+ * drn_plan_candidates takes, one row in 4 KiB of LDS), 1 <= n <= DRN_SHORTLIST_MAX (n > C is legal: the rest is padding).  ws: ws_keys >=
+ * S * ceil(C / DRN_RERANK_GROUP) * min(n, DRN_RERANK_GROUP) 8-byte keys.  Two launches -- workgroup (group, sentence) scores the
+ * DRN_RERANK_GROUP slots of its group (a choice, not a measurement), then the merge of drn_shortlist_topn -- no atomics, no host
+ * synchronisation; an answer depends on the sentence, the set of its valid candidates, the table and the mask alone, and candidates,
+ * the queries, lengths and the mask may change between replays of a captured graph. */
+#define DRN_RERANK_MAX_CANDIDATES 1024
+#define DRN_RERANK_GROUP 16
+int drn_shortlist_rerank(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths, const int32_t* offsets,
+                         const int32_t* candidates, const int32_t* allow, int allow_stride, int R, int V, int E, int S, int L, int C, int n,
+                         int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, void* stream);
 /* mask [S][V], one byte a video (a torch.bool tensor: non-zero = allowed) -> words [S][ceil(V / 32)], the packed mask above: every
  * word written, bits at or past V zero.  S = 1 packs a mask shared by all sentences.  One launch, nothing read back. */
 int drn_pack_allow(const uint8_t* mask, int S, int V, int32_t* words, void* stream);

@@ -108,7 +108,15 @@
            One condition is derived, not measured, and reported HOLDS / MISSED shape by shape: (C1) rank takes no longer than (a) beyond
            (a)'s max - min.  Agreement counts: whether every rank below 16 is the target's place in (a)'s list, and how many sentences
            equal (b) (near-ties in bf16 may differ).  Then evaluate_shortlist on PLANTED queries -- a target's row plus noise, no trained
-           encoder -- on the plain table and on quantize="mxfp8" side by side: recall at 1 / 10 / 100 / 1000 and the median rank."""
+           encoder -- on the plain table and on quantize="mxfp8" side by side: recall at 1 / 10 / 100 / 1000 and the median rank.
+
+  --rerank              instead of the above -> profiles/search_rerank_bench.json: Shortlister.rerank_late (drn_shortlist_rerank, both
+           launches) on R = 65,536 rows x 512 in bf16 laid out as 4,096 x 16 and 546 x 120, S in {1, 8, 64}, L = 16 all live, n = 16, on
+           C = 128 and C = 32 distinct random candidates a sentence; launch-inclusive us, median [min, max] of 5 interleaved rounds in one
+           process, beside (A) what the parent offers for the same answer -- pack_allow of the candidates' mask + shortlist_late(allow=),
+           the fields asserted equal before timing -- and (B) the unmasked shortlist_late; and rerank (one query row) beside pack_allow +
+           shortlist(allow=).  One condition is derived, not measured, and reported holds / MISSED shape by shape: (R1) rerank_late
+           takes no longer than (A) beyond (A)'s max - min.  Random embeddings and candidates: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1816,12 +1824,107 @@ def main_rank(args):
     print("wrote", out)
 
 
+RERANK_WIDTHS = (128, 32)                                   # C: distinct random positions per sentence
+
+
+def bench_rerank(name, lens, emb, S, n, rounds):
+    """drn_shortlist_rerank on R = 65,536 rows cut into videos by `lens`, L = 16 all live: rerank_late at C = 128 and 32 taking turns with
+    (A) pack_allow of the candidate mask + shortlist_late(allow=), the parent's way to the same answer, (B) the unmasked shortlist_late,
+    and rerank (one query row a sentence) beside shortlist(allow=).  rerank_late's fields are asserted equal to (A)'s before timing."""
+    import numpy as np
+    from drn_amd import SegmentShortlist, Shortlist, Shortlister, candidates_mask, pack_allow
+    R, V, L = int(emb.shape[0]), len(lens), 16
+    off = np.concatenate([[0], np.cumsum(lens)])
+    assert off[-1] == R
+    g = torch.Generator(device="cuda:0").manual_seed(S + n)
+    seg = Shortlister(emb, offsets=off)
+    q = torch.randn(S, L, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    q1 = q[:, 0].contiguous()
+    lengths = torch.full((S,), L, dtype=torch.int32, device="cuda:0")
+    variants = {}
+    out_b = Shortlist(*seg.shortlist_late(q, lengths, n))
+    variants["late_unmasked"] = lambda: seg.shortlist_late(q, lengths, n, out=out_b)
+    for C in RERANK_WIDTHS:
+        cand = torch.stack([torch.randperm(V, generator=g, device="cuda:0")[:C] for _ in range(S)]).to(torch.int32).contiguous()
+        mask = candidates_mask(cand, V)
+        words = pack_allow(mask)
+        out_r, out_a = Shortlist(*seg.rerank_late(cand, q, lengths, n)), Shortlist(*seg.shortlist_late(q, lengths, n, allow=words))
+        for f in Shortlist._fields:
+            assert torch.equal(getattr(out_r, f), getattr(out_a, f)), (name, S, C, f)
+        out_r1, out_a1 = Shortlist(*seg.rerank(cand, q1, n)), SegmentShortlist(*seg.shortlist(q1, n, allow=words))
+        for f in Shortlist._fields:
+            assert torch.equal(getattr(out_r1, f), getattr(out_a1, f)), (name, S, C, f, "rerank")
+
+        def masked_late(mask=mask, words=words, out_a=out_a):
+            pack_allow(mask, out=words)
+            return seg.shortlist_late(q, lengths, n, out=out_a, allow=words)
+
+        def masked_segments(mask=mask, words=words, out_a1=out_a1):
+            pack_allow(mask, out=words)
+            return seg.shortlist(q1, n, out=out_a1, allow=words)
+        variants["rerank_late_C%d" % C] = lambda cand=cand, out_r=out_r: seg.rerank_late(cand, q, lengths, n, out=out_r)
+        variants["masked_late_C%d" % C] = masked_late
+        variants["rerank_C%d" % C] = lambda cand=cand, out_r1=out_r1: seg.rerank(cand, q1, n, out=out_r1)
+        variants["masked_segments_C%d" % C] = masked_segments
+    times, reps = interleaved_windows(variants, rounds)
+    row = {"layout": name, "R": R, "V": V, "E": 512, "S": S, "L": L, "n": n, "dtype": "bf16", "launches_per_window": reps,
+           "late_unmasked_us": spread(times["late_unmasked"]), "widths": []}
+    b = times["late_unmasked"]
+    for C in RERANK_WIDTHS:
+        r, a = times["rerank_late_C%d" % C], times["masked_late_C%d" % C]
+        r1, a1 = times["rerank_C%d" % C], times["masked_segments_C%d" % C]
+        over = statistics.median(r) - statistics.median(a)
+        row["widths"].append({
+            "C": C, "rows_scored_over_R": C * (R / V) / R, "rerank_late_us": spread(r), "A_pack_allow_plus_masked_late_us": spread(a),
+            "rerank_late_over_A": statistics.median(r) / statistics.median(a), "rerank_late_over_B": statistics.median(r) / statistics.median(b),
+            "R1": {"rerank_late_minus_A_us": over, "A_max_minus_min_us": max(a) - min(a), "holds": over <= max(a) - min(a)},
+            "rerank_us": spread(r1), "pack_allow_plus_masked_segments_us": spread(a1),
+            "rerank_over_masked_segments": statistics.median(r1) / statistics.median(a1), "rerank_against_masked_segments": verdict(r1, a1)})
+    row["note"] = ("launch-inclusive: both launches of the rerank; (A) is three launches, pack_allow and the two of the masked late shortlist "
+                   "(the mask itself is given: making it from the ids is not timed); (B) is the unmasked late shortlist; rerank / "
+                   "masked_segments: one query row a sentence, best segment")
+    return row
+
+
+def main_rerank(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_rerank_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "(A) pack_allow of the candidates' mask + shortlist_late(allow=), the parent's way to the same answer, the "
+                                   "fields asserted equal before timing; (B) the unmasked shortlist_late.  A difference inside the baseline's "
+                                   "own max - min is NO DIFFERENCE",
+                      "condition": "derived, not measured: (R1) rerank_late does a subset of (A)'s row reads and MFMAs, C * mean run / R of them, "
+                                   "and one launch fewer, so it may not take longer than (A) beyond (A)'s max - min; at S = 1 both sit on their "
+                                   "launches and may tie",
+                      "what_this_does_not_say": "random embeddings and random candidates: nothing here says anything about recall, or about what "
+                                                "depth a coarse stage needs; bf16 only: no fp32, no FP8 tables; C = 128 and 32 only, not C = "
+                                                "1024; n = 16 and L = 16 only; no kernel-only times (no profiler run)"},
+           "rerank": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for name, lens in SEGMENT_LAYOUTS[1:]:
+            row = bench_rerank(name, lens, emb, S, 16, args.rounds)
+            res["rerank"].append(row)
+            print(json.dumps({"rerank": row}), flush=True)
+            for w in row["widths"]:
+                print("R1 %s S = %d C = %d: %s (rerank_late / A = %.3f, / B = %.3f)" % (name, S, w["C"], "holds" if w["R1"]["holds"] else "MISSED",
+                                                                                        w["rerank_late_over_A"], w["rerank_late_over_B"]), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
                                             "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
                                             "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
-                                            "--late-shortlist, search_rank_bench.json with --rank)")
+                                            "--late-shortlist, search_rank_bench.json with --rank, search_rerank_bench.json with --rerank)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1843,9 +1946,13 @@ def main():
                                                                   "the flattened tokens and matmul + amax + sum + topk")
     ap.add_argument("--rank", action="store_true", help="measure Shortlister.rank / rank_late beside the shortlist of n = 16 and matmul + "
                                                         "comparisons + sums, and evaluate_shortlist on planted queries, plain and FP8")
+    ap.add_argument("--rerank", action="store_true", help="measure Shortlister.rerank_late / rerank on 128 and 32 candidates a sentence beside "
+                                                          "pack_allow + the masked full shortlists and the unmasked late shortlist")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.rerank:
+        return main_rerank(args)
     if args.rank:
         return main_rank(args)
     if args.late_shortlist:
