@@ -27,6 +27,7 @@ LATE_MAX_TOKENS = 64      # DRN_LATE_MAX_TOKENS: token vectors of one sentence o
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 RERANK_MAX_CANDIDATES = CANDIDATES_MAX  # DRN_RERANK_MAX_CANDIDATES: columns of the list drn_shortlist_rerank takes (a CHOICE: the width the Grounder takes)
 RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
+SHARDS_MAX = 64           # DRN_SHARDS_MAX: tables of one ShardedShortlister, lists a sentence drn_shortlist_merge_lists merges (a choice, not a measurement)
 
 
 class DrnError(RuntimeError):
@@ -206,6 +207,9 @@ SIGNATURES = {
     "drn_shortlist_rerank": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_pack_allow": [c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "drn_shortlist_merge_lists": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p],
+    "drn_allow_slices": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

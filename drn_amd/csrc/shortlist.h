@@ -6,6 +6,7 @@
 // retrieve_late.hip ranks the ragged tables by late interaction (per-token queries) on the table operands AlPlain / AlQ8 below.
 // retrieve_rank.hip counts, on the same operands and keys, the videos that precede a named one: no sort, no list.
 // retrieve_rerank.hip scores, on the same operands, keys and merge, only the (sentence, video) pairs a candidate list names.
+// retrieve_shard.hip merges the finished lists of several tables: the same key, rebuilt from (score, base + id), and the same sort.
 #pragma once
 #include "common.h"
 #include "mx8.h"

@@ -1965,6 +1965,69 @@ def shortlist_rerank(table, queries, lengths, offsets, candidates, n, ws, ids, s
     return ids, scores, counts
 
 
+def shortlist_merge_lists(in_ids, in_scores, in_counts, in_rows, bases, n, ids, scores, counts, rows=None):
+    """Merge K stacked per-shard lists a sentence into the corpus's list: in_ids, in_scores (K, S, n_in) and in_counts (K, S) as the
+    shards' shortlist entries wrote them, in_rows (K, S, n_in) beside them on ragged shards or None, bases (K + 1,) int32 ON THE DEVICE
+    (corpus position = bases[k] + id) -> ids, scores (S, n), counts (S,) and -- exactly when in_rows is given -- rows (S, n), written
+    in place, every element (drn_shortlist_merge_lists; drn_amd.retrieve.merge_shortlists_reference is the definition).  1 <= K <=
+    SHARDS_MAX, n_in and n in [1, SHORTLIST_MAX].  One launch (tag shortlist_merge_lists), no workspace; nothing is read on the host."""
+    what = "shortlist_merge_lists"
+    _need_gpu(in_ids, in_scores, in_counts, in_rows, bases, ids, scores, counts, rows)
+    n = int(n)
+    if in_ids.dim() != 3 or not 1 <= in_ids.shape[0] <= _lib.SHARDS_MAX or in_ids.shape[1] < 1 or not 1 <= in_ids.shape[2] <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("%s: in_ids must be (K, S, n_in) with 1 <= K <= %d, S >= 1 and 1 <= n_in <= %d, not %s"
+                            % (what, _lib.SHARDS_MAX, _lib.SHORTLIST_MAX, tuple(in_ids.shape)))
+    K, S, n_in = (int(x) for x in in_ids.shape)
+    if not 1 <= n <= _lib.SHORTLIST_MAX:
+        raise _lib.DrnError("%s: n = %d outside [1, %d]" % (what, n, _lib.SHORTLIST_MAX))
+    if (in_rows is None) != (rows is None):
+        raise _lib.DrnError("%s: rows must be given on both sides (the lists of ragged shards) or on neither" % what)
+    tensors = (("in_ids", in_ids, torch.int32, (K, S, n_in)), ("in_scores", in_scores, torch.float32, (K, S, n_in)),
+               ("in_counts", in_counts, torch.int32, (K, S)), ("bases", bases, torch.int32, (K + 1,)), ("ids", ids, torch.int32, (S, n)),
+               ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)))
+    if rows is not None:
+        tensors += (("in_rows", in_rows, torch.int32, (K, S, n_in)), ("rows", rows, torch.int32, (S, n)))
+    for name, t, dt, shape in tensors:
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous %s %s tensor" % (what, name, shape, dt))
+    _timed(what, 0.0, lambda: check(lib().drn_shortlist_merge_lists(
+        _p(in_ids), _p(in_scores), _p(in_counts), _p(in_rows), _p(bases), K, S, n_in, n, _p(ids), _p(scores), _p(counts), _p(rows), _stream()),
+        "drn_shortlist_merge_lists"))
+    return (ids, scores, counts) if rows is None else (ids, scores, counts, rows)
+
+
+def allow_slice_words(bases):
+    """The int32 words a row of the K pieces drn_allow_slices writes, from HOST bases (K + 1 running sums): sum of allow_words(V_k)."""
+    return sum(allow_words(int(b) - int(a)) for a, b in zip(bases[:-1], bases[1:]))
+
+
+def allow_slices(words, bases, host_bases, out):
+    """A packed mask over the whole corpus, words (W,) or (S, W) int32 with W = allow_words(V), -> the K shards' own packed masks back to
+    back in out, a contiguous int32 tensor of rows * allow_slice_words(host_bases) elements, written in place, every word: piece k is
+    (rows, allow_words(V_k)) from element rows * (the words a row of the pieces before it), its word w holding the corpus bits
+    bases[k] + 32 w .. + 31 with zero bits at or past V_k (drn_allow_slices; drn_amd.retrieve.slice_allow_reference is the definition).
+    bases (K + 1,) int32 ON THE DEVICE, host_bases the same K + 1 running sums on the host (they size the pieces).  One launch (tag
+    allow_slices); the mask and the device's bases are not read on the host."""
+    what = "allow_slices"
+    _need_gpu(words, bases, out)
+    K, V = len(host_bases) - 1, int(host_bases[-1])
+    if not 1 <= K <= _lib.SHARDS_MAX or int(host_bases[0]) != 0 or any(int(b) <= int(a) for a, b in zip(host_bases[:-1], host_bases[1:])):
+        raise _lib.DrnError("%s: host_bases must be the K + 1 running sums of 1 <= K <= %d shards of at least one video, from 0"
+                            % (what, _lib.SHARDS_MAX))
+    W = allow_words(V)
+    if words.dtype != torch.int32 or not words.is_contiguous() or words.dim() not in (1, 2) or int(words.shape[-1]) != W or words.shape[0] < 1:
+        raise _lib.DrnError("%s: words must be a contiguous torch.int32 tensor (%d,) or (S, %d) -- ceil(V / 32) packed words a row -- not %s %s"
+                            % (what, W, W, words.dtype, tuple(words.shape)))
+    rows = 1 if words.dim() == 1 else int(words.shape[0])
+    total = allow_slice_words(host_bases)
+    if bases.dtype != torch.int32 or tuple(bases.shape) != (K + 1,) or not bases.is_contiguous():
+        raise _lib.DrnError("%s: bases must be a contiguous (%d,) torch.int32 tensor" % (what, K + 1))
+    if out.dtype != torch.int32 or out.dim() != 1 or int(out.numel()) != rows * total or not out.is_contiguous():
+        raise _lib.DrnError("%s: out must be a contiguous (%d,) torch.int32 tensor (%d rows of %d words)" % (what, rows * total, rows, total))
+    _timed(what, 0.0, lambda: check(lib().drn_allow_slices(_p(words), rows, V, _p(bases), K, total, _p(out), _stream()), "drn_allow_slices"))
+    return out
+
+
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):
     """cand (S, N) int32 on the device -> table (steps, pairs) int32, written in place, every element (drn_plan_candidates;
     drn_amd.grounding.plan_candidates_reference is the definition): the pair_video rows of a search over device candidates.  One launch

@@ -41,7 +41,13 @@ candidates_mask defines what such a tensor means: a set per sentence, -1 and out
 once -- and score only the listed (sentence, video) pairs, with the bits and the total order of the full filtered shortlists.
 rerank_reference, segment_rerank_reference and late_rerank_reference are the definitions (the existing ones under the mask "listed, and
 allowed"), drn_shortlist_rerank (csrc/retrieve_rerank.hip) the one launch, on all the tables above; a coarse table, a fine rerank and
-Grounder.search(candidates=) never leave the device, and drn_amd.search_eval.evaluate_cascade says what depth the coarse stage needs."""
+Grounder.search(candidates=) never leave the device, and drn_amd.search_eval.evaluate_cascade says what depth the coarse stage needs.
+
+ShardedShortlister keeps a corpus as SEVERAL Shortlisters -- appended without a rebuild, plain and quantised side by side -- at the
+corpus positions bases[k] + position in shard k.  Each shard ranks itself with its own entry; drn_shortlist_merge_lists
+(csrc/retrieve_shard.hip) merges the per-shard lists under the one total order and drn_allow_slices cuts a mask over the corpus into
+the shards' own.  A score's bits do not depend on the table that holds the video and the best n of a set are among the best n of each
+part, so the answer is the single table's, bit for bit: merge_shortlists_reference and slice_allow_reference are the definitions."""
 import collections
 import numbers
 
@@ -49,7 +55,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 is a CHOICE, not a measurement (see _lib.py, include/drn_hip.h)
+from ._lib import LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
@@ -376,6 +382,116 @@ def pack_allow(mask, out=None):
     return ops.pack_allow(mask, out)
 
 
+def slice_allow_reference(words, V, start, stop):
+    """THE DEFINITION of a shard's piece of a packed mask, in numpy: words (W,) or (S, W) int32, W = ceil(V / 32) (an array or a host
+    tensor), a packed mask over V videos -> pack_allow_reference of its unpacked bits [start, stop), 0 <= start < stop <= V: bit j of the
+    result is bit start + j of the input, and the bits at or past stop - start are zero."""
+    w = np.ascontiguousarray(words.detach().cpu().numpy() if torch.is_tensor(words) else words)
+    V, start, stop = int(V), int(start), int(stop)
+    if w.dtype != np.int32 or w.ndim not in (1, 2) or w.shape[-1] != ops.allow_words(V) or not 0 <= start < stop <= V:
+        raise DrnError("slice_allow_reference: words must be int32 (W,) or (S, W) with W = ceil(V / 32) = %d and 0 <= start < stop <= V, "
+                       "not %s %s with [%d, %d)" % (ops.allow_words(V), w.dtype, w.shape, start, stop))
+    bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little").astype(np.bool_)
+    return pack_allow_reference(bits[..., start:stop])
+
+
+def merge_shortlists_reference(lists, bases, n):
+    """THE DEFINITION of the merge of per-shard lists, in plain torch (usable on the CPU).  lists: K Shortlist or K SegmentShortlist
+    tuples over the same S sentences (widths may differ); bases: K + 1 integers, shard k holding the corpus positions bases[k] ..
+    bases[k + 1] - 1.  Entry (k, s, i) is a candidate iff i < min(lists[k].n[s], width of list k), 0 <= ids[s, i] < bases[k + 1] -
+    bases[k] and its score is finite; sentence s lists its candidates by higher score, then lower corpus position bases[k] + id, cut to
+    n.  Past the list ids = -1, scores = 0 (and rows = -1); rows travel with their entry.  When every input is a shard's list of width
+    >= n this is the list of the concatenated table (the best n of a set are among the best n of each part).  -> Shortlist, or
+    SegmentShortlist when the inputs are, on their device."""
+    lists, n = list(lists), int(n)
+    bases = [int(b) for b in bases]
+    if not lists or len(bases) != len(lists) + 1:
+        raise DrnError("merge_shortlists_reference: %d lists need %d bases, not %d" % (len(lists), len(lists) + 1, len(bases)))
+    ragged = len(lists[0]) == 4
+    dev = lists[0][0].device
+    S = int(lists[0][0].shape[0])
+    pos, score, valid, rows = [], [], [], []
+    for k, item in enumerate(lists):
+        if (len(item) == 4) != ragged:
+            raise DrnError("merge_shortlists_reference: the lists must all be Shortlists or all be SegmentShortlists")
+        ids, sc, count = item[0].to(torch.int64), item[1].double(), item[2].to(torch.int64)
+        width = int(ids.shape[1])
+        ok = (torch.arange(width, device=dev)[None, :] < count.clamp(max=width)[:, None]) & (ids >= 0) & (ids < bases[k + 1] - bases[k])
+        ok = ok & torch.isfinite(sc)
+        pos.append(ids + bases[k]), score.append(sc), valid.append(ok)
+        if ragged:
+            rows.append(item[3].to(torch.int64))
+    pos, score, valid = torch.cat(pos, dim=1), torch.cat(score, dim=1), torch.cat(valid, dim=1)
+    # by corpus position first, so that the stable sort by score in _listed keeps equal scores in position order
+    order = torch.sort(torch.where(valid, pos, torch.full_like(pos, 2 ** 62)), dim=1, stable=True).indices
+    pos, score, valid = torch.gather(pos, 1, order), torch.gather(score, 1, order), torch.gather(valid, 1, order)
+    _, scores, count, (at, listed) = _listed(score, valid, n)
+    m = int(at.shape[1])
+    ids = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    ids[:, :m] = torch.where(listed, torch.gather(pos, 1, at).to(torch.int32), ids[:, :m])
+    if not ragged:
+        return Shortlist(ids, scores, count)
+    segs = torch.full((S, n), -1, dtype=torch.int32, device=dev)
+    segs[:, :m] = torch.where(listed, torch.gather(torch.gather(torch.cat(rows, dim=1), 1, order), 1, at).to(torch.int32), segs[:, :m])
+    return SegmentShortlist(ids, scores, count, segs)
+
+
+def _allow_of(what, names, V, dev, keep, drop):
+    """Shortlister.allow_of and ShardedShortlister.allow_of: HOST names or positions of a table of V videos -> a packed mask on dev."""
+    if (keep is None) == (drop is None):
+        raise DrnError("%s: exactly one of keep= and drop= must be given" % what)
+    mask = np.zeros(V, dtype=np.bool_) if drop is None else np.ones(V, dtype=np.bool_)
+    where = None
+    for item in (keep if drop is None else drop):
+        if isinstance(item, str):
+            if names is None:
+                raise DrnError("%s: %r is a name and this table has no names" % (what, item))
+            if where is None:
+                where = {name: v for v, name in enumerate(names)}
+            if item not in where:
+                raise DrnError("%s: no video named %r in this table" % (what, item))
+            v = where[item]
+        elif isinstance(item, (numbers.Integral, np.integer)) and not isinstance(item, (bool, np.bool_)):
+            v = int(item)
+            if not 0 <= v < V:
+                raise DrnError("%s: position %d outside [0, %d)" % (what, v, V))
+        else:
+            raise DrnError("%s: an entry must be a name or a position, not %r" % (what, item))
+        mask[v] = drop is None
+    words = torch.from_numpy(pack_allow_reference(mask))
+    if dev.type != "cuda":                    # (a table that is not on a GPU can be asked for its mask, never for a shortlist)
+        return words
+    return words.pin_memory().to(dev, non_blocking=True)
+
+
+def _check_packed_allow(allow, S, V, dev):
+    """The refusals of shortlist(allow=) over V videos on dev, before the library is reached."""
+    W = ops.allow_words(V)
+    if not torch.is_tensor(allow):
+        raise DrnError("Shortlister.shortlist: allow must be a packed mask, a tensor (pack_allow or allow_of makes one)")
+    if allow.dtype == torch.bool:
+        raise DrnError("Shortlister.shortlist: allow is a bool tensor; pack it first -- allow=pack_allow(mask) -- into ceil(V / 32) "
+                       "int32 words a row")
+    if allow.dtype != torch.int32:
+        raise DrnError("Shortlister.shortlist: allow must be torch.int32 packed words (pack_allow makes them), not %s" % allow.dtype)
+    if not allow.is_cuda or allow.device != dev:
+        raise DrnError("Shortlister.shortlist: allow must be on the table's device %s, not %s" % (dev, allow.device))
+    if tuple(allow.shape) not in ((W,), (S, W)):
+        raise DrnError("Shortlister.shortlist: allow must be (%d,) -- one mask for all sentences -- or (%d, %d), ceil(V / 32) words a "
+                       "row for V = %d videos, not %s" % (W, S, W, V, tuple(allow.shape)))
+    if not allow.is_contiguous():
+        raise DrnError("Shortlister.shortlist: allow must be contiguous")
+
+
+def _check_list_out(what, out, S, n):
+    """out= of a method that returns a Shortlist: three buffers of its shapes and dtypes."""
+    if len(out) != 3:
+        raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
+    for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+
+
 def quantized_score_bound(embeddings, scales, queries):
     """How far a quantised table's score may lie from the float64 score of the ORIGINAL table -> (S, rows) float64.  embeddings (rows,
     E) is the table before quantising and scales (rows, E / 32) the scale bytes mx8_quantize gave it.  The format rounds an element to
@@ -570,51 +686,11 @@ class Shortlister(object):
         tombstone list of videos deleted since the table was built -- all the others.  An entry is a name, resolved through
         self.names, or a position in [0, V); an unknown name, a position outside the table or an entry that is neither raises.
         Packed on the host (pack_allow_reference) and put on the device in ONE upload from pinned memory."""
-        if (keep is None) == (drop is None):
-            raise DrnError("Shortlister.allow_of: exactly one of keep= and drop= must be given")
-        V = len(self)
-        mask = np.zeros(V, dtype=np.bool_) if drop is None else np.ones(V, dtype=np.bool_)
-        where = None
-        for item in (keep if drop is None else drop):
-            if isinstance(item, str):
-                if self.names is None:
-                    raise DrnError("Shortlister.allow_of: %r is a name and this table has no names" % (item,))
-                if where is None:
-                    where = {name: v for v, name in enumerate(self.names)}
-                if item not in where:
-                    raise DrnError("Shortlister.allow_of: no video named %r in this table" % (item,))
-                v = where[item]
-            elif isinstance(item, (numbers.Integral, np.integer)) and not isinstance(item, (bool, np.bool_)):
-                v = int(item)
-                if not 0 <= v < V:
-                    raise DrnError("Shortlister.allow_of: position %d outside [0, %d)" % (v, V))
-            else:
-                raise DrnError("Shortlister.allow_of: an entry must be a name or a position, not %r" % (item,))
-            mask[v] = drop is None
-        words = torch.from_numpy(pack_allow_reference(mask))
-        dev = self._table().device
-        if dev.type != "cuda":                    # (a table that is not on a GPU can be asked for its mask, never for a shortlist)
-            return words
-        return words.pin_memory().to(dev, non_blocking=True)
+        return _allow_of("Shortlister.allow_of", self.names, len(self), self._table().device, keep, drop)
 
     def _check_allow(self, allow, S):
         """The refusals of shortlist(allow=), before the library is reached."""
-        V, dev = len(self), self._table().device
-        W = ops.allow_words(V)
-        if not torch.is_tensor(allow):
-            raise DrnError("Shortlister.shortlist: allow must be a packed mask, a tensor (pack_allow or allow_of makes one)")
-        if allow.dtype == torch.bool:
-            raise DrnError("Shortlister.shortlist: allow is a bool tensor; pack it first -- allow=pack_allow(mask) -- into ceil(V / 32) "
-                           "int32 words a row")
-        if allow.dtype != torch.int32:
-            raise DrnError("Shortlister.shortlist: allow must be torch.int32 packed words (pack_allow makes them), not %s" % allow.dtype)
-        if not allow.is_cuda or allow.device != dev:
-            raise DrnError("Shortlister.shortlist: allow must be on the table's device %s, not %s" % (dev, allow.device))
-        if tuple(allow.shape) not in ((W,), (S, W)):
-            raise DrnError("Shortlister.shortlist: allow must be (%d,) -- one mask for all sentences -- or (%d, %d), ceil(V / 32) words a "
-                           "row for V = %d videos, not %s" % (W, S, W, V, tuple(allow.shape)))
-        if not allow.is_contiguous():
-            raise DrnError("Shortlister.shortlist: allow must be contiguous")
+        _check_packed_allow(allow, S, len(self), self._table().device)
 
     def _check(self, queries, n, out):
         """shortlist's refusals, before the library is reached -> (S, n)."""
@@ -726,11 +802,7 @@ class Shortlister(object):
         dev = self._table().device
         S, L, n = self._check_late(what, queries, lengths, n)
         if out is not None:
-            if len(out) != 3:
-                raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
-            for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
-                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+            _check_list_out(what, out, S, n)
         if allow is not None:
             self._check_allow(allow, S)
         if out is None:
@@ -798,11 +870,7 @@ class Shortlister(object):
         """What rerank and rerank_late share once their tensors are checked: out=, allow=, the workspace and the launch."""
         dev = self._table().device
         if out is not None:
-            if len(out) != 3:
-                raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
-            for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
-                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+            _check_list_out(what, out, S, n)
         if allow is not None:
             self._check_allow(allow, S)
         if out is None:
@@ -946,3 +1014,197 @@ class Shortlister(object):
         table = self.embeddings if self.quantize is None else (self.codes, self.scales)
         ops.shortlist_late_rank(table, queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
         return TargetRank(*out)
+
+
+class ShardedShortlister(object):
+    """ShardedShortlister(shards): a corpus kept as 1 to SHARDS_MAX Shortlister objects, held by reference; the video at position i of
+    shard k is the corpus's video bases[k] + i, bases being the running sums of len(shard).  The shards share the device, E, dtype (of
+    the queries) and the kind -- all plain or all with offsets=, because the result types differ; quantize may differ from shard to
+    shard (yesterday's rows in block-scaled FP8 beside today's in bfloat16), and the corpus holds fewer than 2^31 videos.  Anything
+    else is refused before any launch.
+
+    append(shard) is how a video ARRIVES: the new rows become one more shard -- its own constructor checks them, in its own one
+    synchronise -- and nothing that is resident is touched, copied or checked again.  (allow_of(drop=) is how a video leaves.)
+
+    shortlist() and shortlist_late() answer, field for field and bit for bit, what ONE Shortlister over the concatenated rows answers:
+    a score's bits do not depend on the table that holds the video, every shard cuts its list under the one total order (score
+    descending, then position ascending), and the best n of the corpus are among the best n of each shard, so merging the shards'
+    lists under the same order with positions shifted by bases (merge_shortlists_reference; drn_shortlist_merge_lists, ONE launch)
+    gives the corpus's list.  allow= takes a mask over the corpus, cut into the shards' own by one more launch (slice_allow_reference;
+    drn_allow_slices).
+
+    Attributes a caller may rely on: shards; bases (a host list of K + 1 integers) and bases_device (the same as int32 on the
+    device); names (the concatenation when every shard has names, else None); E, dtype, nbytes (the sum over the shards).
+
+    NOT here: rank / rerank over shards (a rank needs the target's key counted in the other shards); shards on several devices or
+    ranks (the stacked (K, S, n) lists are laid out so that lists gathered from other GPUs merge through the same entry); shards on
+    parallel streams (they run one after the other on the current stream); compacting shards; n above SHORTLIST_MAX."""
+
+    def __init__(self, shards):
+        try:
+            shards = list(shards)
+        except TypeError:
+            raise DrnError("ShardedShortlister: the shards must be a sequence of Shortlister objects")
+        if not 1 <= len(shards) <= SHARDS_MAX:
+            raise DrnError("ShardedShortlister: %d shards outside [1, %d]" % (len(shards), SHARDS_MAX))
+        self.shards, self.bases, self.names = [], [0], []
+        for shard in shards:
+            self._admit(shard)
+        self._placed()
+
+    def _admit(self, shard):
+        """The checks of one more shard, then its place: nothing is launched."""
+        if not isinstance(shard, Shortlister):
+            raise DrnError("ShardedShortlister: a shard must be a Shortlister, not %s" % type(shard).__name__)
+        if len(self.shards) >= SHARDS_MAX:
+            raise DrnError("ShardedShortlister: %d shards outside [1, %d]" % (len(self.shards) + 1, SHARDS_MAX))
+        if self.shards:
+            first = self.shards[0]
+            if shard._table().device != first._table().device:
+                raise DrnError("ShardedShortlister: shard %d is on %s, the others on %s" % (len(self.shards), shard._table().device,
+                                                                                           first._table().device))
+            if shard.E != first.E:
+                raise DrnError("ShardedShortlister: shard %d has E = %d columns, the others %d" % (len(self.shards), shard.E, first.E))
+            if shard.dtype != first.dtype:
+                raise DrnError("ShardedShortlister: shard %d takes %s queries, the others %s" % (len(self.shards), shard.dtype, first.dtype))
+            if (getattr(shard, "_seg", None) is None) != (getattr(first, "_seg", None) is None):
+                raise DrnError("ShardedShortlister: shard %d is %s, the others are not: the shards must all be plain or all have offsets= "
+                               "(the result types differ)" % (len(self.shards), "plain" if getattr(shard, "_seg", None) is None else "ragged"))
+        if self.bases[-1] + len(shard) >= 2 ** 31:
+            raise DrnError("ShardedShortlister: %d videos with shard %d, outside [1, 2^31)" % (self.bases[-1] + len(shard), len(self.shards)))
+        self.shards.append(shard)
+        self.bases.append(self.bases[-1] + len(shard))
+        if self.names is not None:
+            self.names = None if shard.names is None else self.names + list(shard.names)
+
+    def _placed(self):
+        """After the shards changed: the buffers kept for the old K are dropped and bases goes to the device (one upload from pinned
+        memory, no synchronise)."""
+        self._bufs = {}
+        bases = torch.tensor(self.bases, dtype=torch.int32)
+        dev = self.device
+        self.bases_device = bases if dev.type != "cuda" else bases.pin_memory().to(dev, non_blocking=True)
+
+    def append(self, shard):
+        """One more shard at the end of the corpus -- the same checks as the constructor, before anything changes -- at the positions
+        bases[K] .. bases[K] + len(shard) - 1.  The resident shards are not touched, nothing is copied and nothing synchronises (the
+        new shard's own constructor did, once, over its own rows); the stacked buffers kept for the old K are dropped, so warm a
+        shape again before capturing it in a graph.  -> self."""
+        self._admit(shard)
+        self._placed()
+        return self
+
+    @property
+    def device(self):
+        return self.shards[0]._table().device
+
+    @property
+    def E(self):
+        return self.shards[0].E
+
+    @property
+    def dtype(self):
+        """The dtype of the queries shortlist() takes (a quantised shard's recorded dtype)."""
+        return self.shards[0].dtype
+
+    @property
+    def nbytes(self):
+        """The bytes of the tables held, the sum over the shards."""
+        return sum(shard.nbytes for shard in self.shards)
+
+    def __len__(self):
+        return self.bases[-1]
+
+    def check(self, store):
+        """Raises unless the corpus's names are the store's (a FeatureStore or a SearchIndex), position by position."""
+        if self.names is None or self.names != list(store.names):
+            raise DrnError("ShardedShortlister: the corpus's names are not the store's (position v must belong to store position v)")
+
+    def allow_of(self, keep=None, drop=None):
+        """Shortlister.allow_of over the CORPUS: names (resolved through self.names) or corpus positions in [0, V) -> a packed mask
+        (W,) int32 over all V videos on the shards' device, what shortlist(allow=) takes here."""
+        return _allow_of("ShardedShortlister.allow_of", self.names, len(self), self.device, keep, drop)
+
+    def _lists(self, S, n):
+        """The stacked per-shard lists of this (K, S, n): slices along dim 0 are contiguous, legal out= buffers of the shards."""
+        K = len(self.shards)
+        bufs = self._bufs.get((K, S, n))
+        if bufs is None:
+            dev = self.device
+            bufs = (torch.empty((K, S, n), dtype=torch.int32, device=dev), torch.empty((K, S, n), dtype=torch.float32, device=dev),
+                    torch.empty((K, S), dtype=torch.int32, device=dev))
+            if getattr(self.shards[0], "_seg", None) is not None:
+                bufs += (torch.empty((K, S, n), dtype=torch.int32, device=dev),)
+            self._bufs[(K, S, n)] = bufs
+        return bufs
+
+    def _slices(self, allow):
+        """A mask over the corpus -> the K shards' own masks, views of one buffer kept per (K, rows): ONE launch."""
+        if allow is None:
+            return [None] * len(self.shards)
+        K, rows = len(self.shards), 1 if allow.dim() == 1 else int(allow.shape[0])
+        buf = self._bufs.get(("allow", K, rows))
+        if buf is None:
+            buf = self._bufs[("allow", K, rows)] = torch.empty(rows * ops.allow_slice_words(self.bases), dtype=torch.int32, device=self.device)
+        ops.allow_slices(allow, self.bases_device, self.bases, buf)
+        pieces, at = [], 0
+        for a, b in zip(self.bases[:-1], self.bases[1:]):
+            W = ops.allow_words(b - a)
+            piece = buf[at:at + rows * W]
+            pieces.append(piece if allow.dim() == 1 else piece.view(rows, W))
+            at += rows * W
+        return pieces
+
+    def shortlist(self, queries, n, out=None, allow=None):
+        """Shortlister.shortlist over the corpus -> Shortlist, or SegmentShortlist on ragged shards, with CORPUS positions in ids:
+        the arguments, the refusals, the padding (-1 / 0 / -1) and out= of the single table's method, and every field bit for bit what
+        one Shortlister over the concatenated rows returns (over the concatenation of dequantized() rows where shards are
+        quantised).  allow: a packed mask over the WHOLE corpus, (W,) or (S, W) with W = ceil(V / 32), from pack_allow or allow_of.
+        Each shard runs its own entry, unchanged, into slice [k] of buffers kept per (K, S, n); then ONE merge launch; with allow=,
+        one slicing launch first.  All on the current stream, without a host synchronisation, and it can be captured in a graph once
+        the shape is warmed, where the queries and the mask's contents may change in place between replays."""
+        first = self.shards[0]
+        S, n = first._check(queries, n, out)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        ragged = getattr(first, "_seg", None) is not None
+        dev = self.device
+        if out is None:
+            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
+                   torch.empty((S,), dtype=torch.int32, device=dev))
+            if ragged:
+                out += (torch.empty((S, n), dtype=torch.int32, device=dev),)
+        lists = self._lists(S, n)
+        queries = queries.contiguous()
+        for k, (shard, piece) in enumerate(zip(self.shards, self._slices(allow))):
+            shard.shortlist(queries, n, out=tuple(t[k] for t in lists), allow=piece)
+        if ragged:
+            ops.shortlist_merge_lists(lists[0], lists[1], lists[2], lists[3], self.bases_device, n, out[0], out[1], out[2], out[3])
+            return SegmentShortlist(*out)
+        ops.shortlist_merge_lists(lists[0], lists[1], lists[2], None, self.bases_device, n, out[0], out[1], out[2])
+        return Shortlist(*out)
+
+    def shortlist_late(self, queries, lengths, n, out=None, allow=None):
+        """Shortlister.shortlist_late over the corpus (ragged shards) -> Shortlist with CORPUS positions: arguments, refusals, padding
+        and out= as there, allow= over the whole corpus as in shortlist(), every field bit for bit the single table's.  Each shard
+        runs its own entry into slice [k] of the stacked buffers, then ONE merge launch; no host synchronisation, capturable once
+        warmed, where queries, lengths and the mask's contents may change in place between replays."""
+        what = "Shortlister.shortlist_late"
+        first = self.shards[0]
+        if getattr(first, "_seg", None) is None:
+            raise DrnError("%s: these tables have one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
+                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call shortlist()" % what)
+        S, L, n = first._check_late(what, queries, lengths, n)
+        if out is not None:
+            _check_list_out(what, out, S, n)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        dev = self.device
+        if out is None:
+            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
+                   torch.empty((S,), dtype=torch.int32, device=dev))
+        lists = self._lists(S, n)
+        for k, (shard, piece) in enumerate(zip(self.shards, self._slices(allow))):
+            shard.shortlist_late(queries, lengths, n, out=tuple(t[k] for t in lists[:3]), allow=piece)
+        ops.shortlist_merge_lists(lists[0], lists[1], lists[2], None, self.bases_device, n, out[0], out[1], out[2])
+        return Shortlist(*out)

@@ -782,6 +782,31 @@ int drn_shortlist_rerank(const void* table, const uint8_t* scales, const void* q
 /* mask [S][V], one byte a video (a torch.bool tensor: non-zero = allowed) -> words [S][ceil(V / 32)], the packed mask above: every
  * word written, bits at or past V zero.  S = 1 packs a mask shared by all sentences.  One launch, nothing read back. */
 int drn_pack_allow(const uint8_t* mask, int S, int V, int32_t* words, void* stream);
+/* A CORPUS KEPT AS K TABLES (drn_amd/csrc/retrieve_shard.hip): corpus position = bases[k] + position in shard k, bases [K + 1] int32 on
+ * the device, the running sums of the shards' videos from 0; 1 <= K <= DRN_SHARDS_MAX (a choice, not a measurement).  Each shard is
+ * ranked by its own *_topn entry; drn_shortlist_merge_lists merges the K lists of every sentence, stacked as in_ids, in_scores
+ * [K][S][n_in], in_counts [K][S] and -- the lists of ragged shards -- in_rows [K][S][n_in], into ids, scores [S][n], counts [S] and rows
+ * [S][n]; rows is given exactly when in_rows is (both NULL otherwise).  Entry (k, s, i) is a candidate iff i < min(in_counts[k][s],
+ * n_in), 0 <= in_ids[k][s][i] < bases[k + 1] - bases[k] and its score is finite; sentence s lists its candidates by score descending,
+ * then corpus position bases[k] + id ascending -- the total order of drn_shortlist_topn -- cut to n, a row travelling with its entry;
+ * past the list ids = -1, scores = 0, rows = -1.  A score's bits do not depend on the table it was computed in and every shard cuts
+ * its list under the same order, so with n_in >= n the result IS the list of the concatenated table, bit for bit.  Both n_in and n lie
+ * in [1, DRN_SHORTLIST_MAX].  PRECONDITION: the ids of one list are distinct, as every shipped entry writes them (sorted, too; the
+ * order of an input list is not relied on).  On other input the content of the list is unspecified; even then nothing outside the
+ * outputs is written, nothing past n_in is read, and an id out of range never becomes a position.  One launch, one wavefront per
+ * sentence; no atomics, no workspace, no host synchronisation; nothing is read on the host, so everything may change between replays
+ * of a captured graph.  Lists gathered from other devices merge through the same entry. */
+#define DRN_SHARDS_MAX 64
+int drn_shortlist_merge_lists(const int32_t* in_ids, const float* in_scores, const int32_t* in_counts, const int32_t* in_rows,
+                              const int32_t* bases, int K, int S, int n_in, int n, int32_t* ids, float* scores, int32_t* counts,
+                              int32_t* rows, void* stream);
+/* words [rows][ceil(V / 32)], a packed mask over the whole corpus (rows = 1: shared by all sentences) -> the K shards' own packed
+ * masks, back to back in out: piece k is [rows][W_k], W_k = ceil(V_k / 32), V_k = bases[k + 1] - bases[k], from word rows * (W_0 + ... +
+ * W_(k-1)); word w of a row holds the corpus bits bases[k] + 32 w .. + 31 (a base need not be a multiple of 32), the bits at or past
+ * V_k zero.  Each piece is a legal allow argument of its shard's *_allow entry, 4-byte aligned.  total_words = W_0 + ... + W_(K-1), the
+ * words a row `out` holds, computed by the caller from its host copy of bases; when the device's bases do not come to it nothing is
+ * written.  bases as in drn_shortlist_merge_lists, not read on the host.  One launch, nothing read back. */
+int drn_allow_slices(const int32_t* words, int rows, int V, const int32_t* bases, int K, int total_words, int32_t* out, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

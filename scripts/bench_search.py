@@ -116,7 +116,16 @@
            process, beside (A) what the parent offers for the same answer -- pack_allow of the candidates' mask + shortlist_late(allow=),
            the fields asserted equal before timing -- and (B) the unmasked shortlist_late; and rerank (one query row) beside pack_allow +
            shortlist(allow=).  One condition is derived, not measured, and reported holds / MISSED shape by shape: (R1) rerank_late
-           takes no longer than (A) beyond (A)'s max - min.  Random embeddings and candidates: nothing here says anything about recall."""
+           takes no longer than (A) beyond (A)'s max - min.  Random embeddings and candidates: nothing here says anything about recall.
+
+  --sharded-shortlist   instead of the above -> profiles/search_sharded_shortlist_bench.json: ShardedShortlister.shortlist (every shard's
+           entry, then drn_shortlist_merge_lists) on R = 65,536 rows x 512 in bf16 laid out as 65,536 x 1 and 4,096 x 16, cut into K = 1 /
+           4 / 16 equal shards, S in {1, 8, 64}, n in {16, 128}; launch-inclusive us, median [min, max] of 5 interleaved rounds in one
+           process, beside the single Shortlister over the same rows (every field asserted equal before timing) and the merge launch
+           alone; one mixed object (half FP8, half bf16) and shortlist_late at 16 tokens on K = 4, each beside its single table.  One
+           condition is derived, not measured, and reported HOLDS / MISSED shape by shape: (G1) adding 1,024 rows by append + shortlist
+           takes less than torch.cat + Shortlister + shortlist on the same tensors by more than the latter's max - min.  Random
+           embeddings: nothing here says anything about recall."""
 import argparse
 import json
 import os
@@ -1919,12 +1928,204 @@ def main_rerank(args):
     print("wrote", out)
 
 
+SHARD_COUNTS = (1, 4, 16)                                   # K equal shards of the 65,536 rows
+GROWTH_ROWS = 1024                                          # rows that arrive in (G1)
+
+
+def equal_shards(emb, lens, K, quantize=()):
+    """The table cut into K Shortlisters of R / K rows each over CLONED slices (V / K videos each; ragged when the layout is); the shards
+    whose number is in `quantize` are kept in block-scaled FP8."""
+    import numpy as np
+    from drn_amd import Shortlister
+    R, V = int(emb.shape[0]), len(lens)
+    assert V % K == 0 and R % K == 0
+    off = np.concatenate([[0], np.cumsum(lens)])
+    shards = []
+    for k in range(K):
+        a, b = k * V // K, (k + 1) * V // K
+        q8 = "mxfp8" if k in quantize else None
+        rows = emb[int(off[a]):int(off[b])].clone()
+        shards.append(Shortlister(rows, quantize=q8) if max(lens) == 1 else Shortlister(rows, offsets=off[a:b + 1] - off[a], quantize=q8))
+    return shards
+
+
+def same_fields(a, b, what):
+    for f in a._fields:
+        assert torch.equal(getattr(a, f), getattr(b, f)), (what, f)
+
+
+def bench_sharded_shortlist(name, lens, emb, single, sharded, S, n, rounds):
+    """ShardedShortlister.shortlist at K = 1 / 4 / 16 equal shards beside the single Shortlister over the same rows (the parent's code,
+    unchanged) and the merge launch alone on the lists the call left; every field asserted equal to the single table's before timing."""
+    from drn_amd import ops
+    g = torch.Generator(device="cuda:0").manual_seed(S + n)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    out_single = single.shortlist(q, n)
+    variants = {"single": lambda: single.shortlist(q, n, out=out_single)}
+    for K, sh in sharded.items():
+        out = sh.shortlist(q, n)
+        same_fields(out, out_single, (name, K, S, n))
+        lists = sh._lists(S, n)
+        rows = (lists[3], out[3]) if len(out) == 4 else (None, None)
+        variants["sharded_K%d" % K] = lambda sh=sh, out=out: sh.shortlist(q, n, out=out)
+        variants["merge_K%d" % K] = lambda sh=sh, out=out, lists=lists, rows=rows: ops.shortlist_merge_lists(
+            lists[0], lists[1], lists[2], rows[0], sh.bases_device, n, out[0], out[1], out[2], rows=rows[1])
+    times, reps = interleaved_windows(variants, rounds)
+    base = times["single"]
+    row = {"layout": name, "R": int(emb.shape[0]), "V": len(lens), "E": 512, "S": S, "n": n, "dtype": "bf16", "launches_per_window": reps,
+           "single_us": spread(base), "shards": []}
+    for K in sharded:
+        t, m = times["sharded_K%d" % K], times["merge_K%d" % K]
+        row["shards"].append({"K": K, "sharded_us": spread(t), "merge_alone_us": spread(m),
+                              "sharded_over_single": statistics.median(t) / statistics.median(base), "sharded_against_single": verdict(t, base),
+                              "merge_share_of_sharded": statistics.median(m) / statistics.median(t)})
+    row["note"] = ("launch-inclusive: K shards' entries one after the other on one stream (two launches each on the plain layout, three on the "
+                   "ragged one) and the merge launch; merge_alone is the merge launch on the stacked lists the call left")
+    return row
+
+
+def bench_sharded_other(name, lens, emb, S, n, rounds):
+    """A mixed object (half FP8, half bf16: K = 2) beside the single plain Shortlister over the same rows (the FP8 half dequantised), and
+    -- on the ragged layout -- shortlist_late at 16 tokens on K = 4 shards beside the single table."""
+    import numpy as np
+    from drn_amd import ShardedShortlister, Shortlister
+    g = torch.Generator(device="cuda:0").manual_seed(3 * S + n)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    ragged = max(lens) > 1
+    off = np.concatenate([[0], np.cumsum(lens)])
+    cold, hot = equal_shards(emb, lens, 2, quantize=(0,))
+    rows = torch.cat([cold.dequantized().embeddings, hot.embeddings]).contiguous()
+    single = Shortlister(rows, offsets=off) if ragged else Shortlister(rows)
+    mixed = ShardedShortlister([cold, hot])
+    out_s, out_m = single.shortlist(q, n), mixed.shortlist(q, n)
+    same_fields(out_m, out_s, (name, "mixed", S, n))
+    variants = {"single": lambda: single.shortlist(q, n, out=out_s), "mixed": lambda: mixed.shortlist(q, n, out=out_m)}
+    if ragged:
+        L = 16
+        tok = torch.randn(S, L, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+        lengths = torch.full((S,), L, dtype=torch.int32, device="cuda:0")
+        whole, four = Shortlister(emb, offsets=off), ShardedShortlister(equal_shards(emb, lens, 4))
+        out_w, out_f = whole.shortlist_late(tok, lengths, n), four.shortlist_late(tok, lengths, n)
+        same_fields(out_f, out_w, (name, "late", S, n))
+        variants["late_single"] = lambda: whole.shortlist_late(tok, lengths, n, out=out_w)
+        variants["late_K4"] = lambda: four.shortlist_late(tok, lengths, n, out=out_f)
+    times, reps = interleaved_windows(variants, rounds)
+    row = {"layout": name, "S": S, "n": n, "launches_per_window": reps, "table_bytes": {"single_bf16": single.nbytes, "mixed": mixed.nbytes},
+           "single_plain_us": spread(times["single"]), "mixed_fp8_bf16_K2_us": spread(times["mixed"]),
+           "mixed_over_single": statistics.median(times["mixed"]) / statistics.median(times["single"]),
+           "mixed_against_single": verdict(times["mixed"], times["single"])}
+    if ragged:
+        row.update({"L": 16, "late_single_us": spread(times["late_single"]), "late_K4_us": spread(times["late_K4"]),
+                    "late_K4_over_single": statistics.median(times["late_K4"]) / statistics.median(times["late_single"]),
+                    "late_K4_against_single": verdict(times["late_K4"], times["late_single"])})
+    return row
+
+
+def bench_growth(name, lens, emb, new_rows, new_lens, S, n, rounds, iters=10):
+    """(G1) two ways to add GROWTH_ROWS rows to the resident table and shortlist once: sharded.append(Shortlister(new_rows)) + shortlist
+    beside torch.cat + Shortlister(...) + shortlist on the same tensors, the parent's only way.  Host clock from before the first call to
+    after a device synchronise; the two take turns inside every round; a round is the mean of `iters` runs."""
+    import numpy as np
+    from drn_amd import ShardedShortlister, Shortlister
+    ragged = max(lens) > 1
+    off, new_off = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(new_lens)])
+    both_off = np.concatenate([off, off[-1] + new_off[1:]])
+    make = (lambda rows, o: Shortlister(rows, offsets=o)) if ragged else (lambda rows, o: Shortlister(rows))
+    base = make(emb, off)
+    g = torch.Generator(device="cuda:0").manual_seed(7 * S + n)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+
+    def append_way():
+        sh = ShardedShortlister([base])                      # (the resident object: not timed)
+        sh.shortlist(q, n)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = sh.append(make(new_rows, new_off)).shortlist(q, n)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6, got
+
+    def rebuild_way():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = make(torch.cat([emb, new_rows]), both_off).shortlist(q, n)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6, got
+    same_fields(append_way()[1], rebuild_way()[1], (name, "growth", S, n))
+    a, b = [], []
+    for _ in range(rounds):
+        a.append(statistics.mean(append_way()[0] for _ in range(iters)))
+        b.append(statistics.mean(rebuild_way()[0] for _ in range(iters)))
+    gain = statistics.median(b) - statistics.median(a)
+    return {"layout": name, "S": S, "n": n, "resident_rows": int(emb.shape[0]), "new_rows": int(new_rows.shape[0]), "runs_per_round": iters,
+            "append_plus_shortlist_us": spread(a), "cat_plus_rebuild_plus_shortlist_us": spread(b),
+            "append_over_rebuild": statistics.median(a) / statistics.median(b),
+            "G1": {"rebuild_minus_append_us": gain, "rebuild_max_minus_min_us": max(b) - min(b), "holds": gain > max(b) - min(b)}}
+
+
+def main_sharded_shortlist(args):
+    from drn_amd import ShardedShortlister, Shortlister
+    import numpy as np
+    out = args.out or os.path.join(ROOT, "profiles", "search_sharded_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the tables resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call; (G1): "
+                               "host clock from before the first call to after a device synchronise, a round = the mean of 10 runs",
+                      "baselines": "single: ONE Shortlister over the same rows, the parent's code unchanged, in the same process, every field "
+                                   "asserted equal before timing.  A difference inside the baseline's own max - min is NO DIFFERENCE",
+                      "condition": "derived, not measured: (G1) adding 1,024 rows by append + shortlist touches 1,024 new rows and launches K + 1 "
+                                   "shards' entries and a merge; torch.cat + Shortlister + shortlist copies the whole table, checks all of it "
+                                   "for finiteness with a synchronise and makes a new plan and workspaces, so the first must take less than "
+                                   "the second by more than the second's own max - min",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall; bf16 queries only; equal shards only "
+                                                "(a small hot shard beside a large cold one is measured in (G1) alone); shards run one after "
+                                                "the other on one stream: parallel streams are not tried; no kernel-only times (no profiler "
+                                                "run); K = 64 is not measured"},
+           "sharded_shortlist": [], "mixed_and_late": [], "growth": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    new_rows = torch.randn(GROWTH_ROWS, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+
+    def save():
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    for name, lens in SEGMENT_LAYOUTS[:2]:
+        off = np.concatenate([[0], np.cumsum(lens)])
+        single = Shortlister(emb) if max(lens) == 1 else Shortlister(emb, offsets=off)
+        sharded = {K: ShardedShortlister(equal_shards(emb, lens, K)) for K in SHARD_COUNTS}
+        for S in (1, 8, 64):
+            for n in (16, 128):
+                row = bench_sharded_shortlist(name, lens, emb, single, sharded, S, n, args.rounds)
+                res["sharded_shortlist"].append(row)
+                print(json.dumps({"sharded_shortlist": row}), flush=True)
+                for k in row["shards"]:
+                    print("%s S = %d n = %d K = %d: sharded / single = %.3f (%s), the merge alone %.1f us" % (
+                        name, S, n, k["K"], k["sharded_over_single"], k["sharded_against_single"], k["merge_alone_us"]["median"]), flush=True)
+                save()
+        del sharded
+        for S in (1, 8, 64):
+            row = bench_sharded_other(name, lens, emb, S, 16, args.rounds)
+            res["mixed_and_late"].append(row)
+            print(json.dumps({"mixed_and_late": row}), flush=True)
+            new_lens = [lens[0]] * (GROWTH_ROWS // lens[0])
+            row = bench_growth(name, lens, emb, new_rows, new_lens, S, 16, args.rounds)
+            res["growth"].append(row)
+            print(json.dumps({"growth": row}), flush=True)
+            print("G1 %s S = %d: %s (append / rebuild = %.3f)" % (name, S, "HOLDS" if row["G1"]["holds"] else "MISSED", row["append_over_rebuild"]),
+                  flush=True)
+            save()
+    save()
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
                                             "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
                                             "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
-                                            "--late-shortlist, search_rank_bench.json with --rank, search_rerank_bench.json with --rerank)")
+                                            "--late-shortlist, search_rank_bench.json with --rank, search_rerank_bench.json with --rerank, "
+                                            "search_sharded_shortlist_bench.json with --sharded-shortlist)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -1948,9 +2149,14 @@ def main():
                                                         "comparisons + sums, and evaluate_shortlist on planted queries, plain and FP8")
     ap.add_argument("--rerank", action="store_true", help="measure Shortlister.rerank_late / rerank on 128 and 32 candidates a sentence beside "
                                                           "pack_allow + the masked full shortlists and the unmasked late shortlist")
+    ap.add_argument("--sharded-shortlist", action="store_true", help="measure ShardedShortlister.shortlist on 1 / 4 / 16 equal shards beside the "
+                                                                     "single table, the merge launch alone, a mixed FP8 / bf16 object, "
+                                                                     "shortlist_late, and append beside torch.cat + rebuild")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.sharded_shortlist:
+        return main_sharded_shortlist(args)
     if args.rerank:
         return main_rerank(args)
     if args.rank:
