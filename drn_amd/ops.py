@@ -1493,134 +1493,21 @@ def shortlist_ws_keys(V, S, n):
     return int(S) * (-(-int(V) // _lib.SHORTLIST_BLOCK)) * min(int(n), _lib.SHORTLIST_BLOCK)
 
 
-def shortlist_topn(emb, queries, n, ws, ids, scores, counts):
-    """Each sentence's best n rows of `emb` (V, E) by dot product with its row of `queries` (S, E), both contiguous and of one dtype
-    (float32 / bfloat16), into ids (S, n) int32, scores (S, n) float32 and counts (S,) int32, all written in place
-    (drn_shortlist_topn; drn_amd.retrieve.shortlist_reference is the definition: finite scores only, score descending then position
-    ascending, -1 / 0 past the list).  ws: an int64 tensor of at least shortlist_ws_keys(V, S, n) elements.  Two launches on the
-    current stream behind one entry (one tag, shortlist_topn); no host synchronisation."""
-    _need_gpu(emb, queries, ws, ids, scores, counts)
-    n = int(n)
-    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
-            or emb.shape[1] != queries.shape[1]:
-        raise _lib.DrnError("shortlist_topn: emb (V, E) and queries (S, E) must be contiguous and of one dtype and width")
-    V, E = (int(x) for x in emb.shape)
-    S = int(queries.shape[0])
-    if not 1 <= n <= _lib.SHORTLIST_MAX:
-        raise _lib.DrnError("shortlist_topn: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
-    for name, t, dt, shape in (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)),
-                               ("counts", counts, torch.int32, (S,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.DrnError("shortlist_topn: %s must be a contiguous %s %s tensor" % (name, shape, dt))
-    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < shortlist_ws_keys(V, S, n):
-        raise _lib.DrnError("shortlist_topn: ws must be a contiguous int64 tensor of at least %d elements" % shortlist_ws_keys(V, S, n))
-    _timed("shortlist_topn", 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn(
-        _p(emb), _p(queries), V, E, S, n, dtype_code(emb), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts),
-        _stream()), "drn_shortlist_topn"))
-    return ids, scores, counts
-
-
 def shortlist_segments_ws_keys(nblocks, S, n):
     """The 8-byte keys of workspace drn_shortlist_segments_topn needs: K + ceil(K / 2), K = S * nblocks * min(n, SHORTLIST_SEG_BLOCK)."""
     K = int(S) * int(nblocks) * min(int(n), _lib.SHORTLIST_SEG_BLOCK)
     return K + (K + 1) // 2
 
 
-def shortlist_segments_topn(emb, queries, offsets, blk_vid, vid_blk, n, ws, ids, scores, counts, rows):
-    """Each sentence's best n videos of a RAGGED table by their best row: emb (R, E) and queries (S, E), contiguous and of one dtype
-    (float32 / bfloat16); offsets (V + 1,), blk_vid (nblocks + 1,) and vid_blk (V,) int32 on the device (the rows of each video and the
-    block plan, drn_amd.retrieve.plan_segment_blocks) -> ids, scores (S, n), counts (S,) and rows (S, n) int32, all written in place
-    (drn_shortlist_segments_topn; drn_amd.retrieve.segment_shortlist_reference is the definition).  ws: an int64 tensor of at least
-    shortlist_segments_ws_keys(nblocks, S, n) elements.  Three launches on the current stream behind one entry (one tag,
-    shortlist_segments_topn); the tables are not read on the host and nothing is synchronised."""
-    _need_gpu(emb, queries, offsets, blk_vid, vid_blk, ws, ids, scores, counts, rows)
-    n = int(n)
-    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
-            or emb.shape[1] != queries.shape[1]:
-        raise _lib.DrnError("shortlist_segments_topn: emb (R, E) and queries (S, E) must be contiguous and of one dtype and width")
-    R, E = (int(x) for x in emb.shape)
-    S = int(queries.shape[0])
-    if not 1 <= n <= _lib.SHORTLIST_MAX:
-        raise _lib.DrnError("shortlist_segments_topn: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
-    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
-        raise _lib.DrnError("shortlist_segments_topn: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1")
-    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
-    for name, t, dt, shape in (("offsets", offsets, torch.int32, (V + 1,)), ("blk_vid", blk_vid, torch.int32, (nblocks + 1,)),
-                               ("vid_blk", vid_blk, torch.int32, (V,)), ("ids", ids, torch.int32, (S, n)),
-                               ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)),
-                               ("rows", rows, torch.int32, (S, n))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.DrnError("shortlist_segments_topn: %s must be a contiguous %s %s tensor" % (name, shape, dt))
-    need = shortlist_segments_ws_keys(nblocks, S, n)
-    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < need:
-        raise _lib.DrnError("shortlist_segments_topn: ws must be a contiguous int64 tensor of at least %d elements" % need)
-    _timed("shortlist_segments_topn", 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn(
-        _p(emb), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), R, V, nblocks, E, S, n, dtype_code(emb), _p(ws),
-        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn"))
-    return ids, scores, counts, rows
-
-
 def _q8_table(what, codes, scales, queries):
     """The checks a block-scaled FP8 table shares between the two quantised shortlists -> (rows, E)."""
-    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2 or not codes.is_contiguous() \
-            or not scales.is_contiguous() or codes.shape[1] % 32 or tuple(scales.shape) != (int(codes.shape[0]), int(codes.shape[1]) // 32):
+    cs, qs = tuple(codes.shape), queries.shape
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or len(cs) != 2 or not codes.is_contiguous() or not scales.is_contiguous() \
+            or cs[1] % 32 or tuple(scales.shape) != (cs[0], cs[1] // 32):
         raise _lib.DrnError("%s: codes (rows, E) and scales (rows, E / 32) must be contiguous uint8 tensors with E a multiple of 32" % what)
-    if queries.dim() != 2 or not queries.is_contiguous() or queries.dtype not in (torch.float32, torch.bfloat16) \
-            or queries.shape[1] != codes.shape[1]:
-        raise _lib.DrnError("%s: queries must be a contiguous (S, %d) float32 / bfloat16 tensor" % (what, int(codes.shape[1])))
-    return int(codes.shape[0]), int(codes.shape[1])
-
-
-def shortlist_topn_q8(codes, scales, queries, n, ws, ids, scores, counts):
-    """shortlist_topn over a table kept in block-scaled FP8: codes (V, E) and scales (V, E / 32) uint8 as quantize_rows_mx8 writes them,
-    E % 32 == 0; queries (S, E) float32 / bfloat16, whose dtype chooses the MFMA chain (drn_shortlist_topn_q8).  The result is bit for
-    bit shortlist_topn over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype); ws, ids, scores and counts as there.  Two
-    launches on the current stream behind one entry (one tag, shortlist_topn_q8); no host synchronisation."""
-    _need_gpu(codes, scales, queries, ws, ids, scores, counts)
-    n = int(n)
-    V, E = _q8_table("shortlist_topn_q8", codes, scales, queries)
-    S = int(queries.shape[0])
-    if not 1 <= n <= _lib.SHORTLIST_MAX:
-        raise _lib.DrnError("shortlist_topn_q8: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
-    for name, t, dt, shape in (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)),
-                               ("counts", counts, torch.int32, (S,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.DrnError("shortlist_topn_q8: %s must be a contiguous %s %s tensor" % (name, shape, dt))
-    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < shortlist_ws_keys(V, S, n):
-        raise _lib.DrnError("shortlist_topn_q8: ws must be a contiguous int64 tensor of at least %d elements" % shortlist_ws_keys(V, S, n))
-    _timed("shortlist_topn_q8", 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_q8(
-        _p(codes), _p(scales), _p(queries), V, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores),
-        _p(counts), _stream()), "drn_shortlist_topn_q8"))
-    return ids, scores, counts
-
-
-def shortlist_segments_topn_q8(codes, scales, queries, offsets, blk_vid, vid_blk, n, ws, ids, scores, counts, rows):
-    """shortlist_segments_topn over a ragged table kept in block-scaled FP8: codes (R, E) and scales (R, E / 32) uint8, E % 32 == 0;
-    queries (S, E) float32 / bfloat16, whose dtype chooses the MFMA chain (drn_shortlist_segments_topn_q8).  The result is bit for bit
-    shortlist_segments_topn over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype); every other argument as there.  Three
-    launches on the current stream behind one entry (one tag, shortlist_segments_topn_q8); nothing is read on the host."""
-    _need_gpu(codes, scales, queries, offsets, blk_vid, vid_blk, ws, ids, scores, counts, rows)
-    n = int(n)
-    R, E = _q8_table("shortlist_segments_topn_q8", codes, scales, queries)
-    S = int(queries.shape[0])
-    if not 1 <= n <= _lib.SHORTLIST_MAX:
-        raise _lib.DrnError("shortlist_segments_topn_q8: n = %d outside [1, %d]" % (n, _lib.SHORTLIST_MAX))
-    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
-        raise _lib.DrnError("shortlist_segments_topn_q8: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1")
-    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
-    for name, t, dt, shape in (("offsets", offsets, torch.int32, (V + 1,)), ("blk_vid", blk_vid, torch.int32, (nblocks + 1,)),
-                               ("vid_blk", vid_blk, torch.int32, (V,)), ("ids", ids, torch.int32, (S, n)),
-                               ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)),
-                               ("rows", rows, torch.int32, (S, n))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.DrnError("shortlist_segments_topn_q8: %s must be a contiguous %s %s tensor" % (name, shape, dt))
-    need = shortlist_segments_ws_keys(nblocks, S, n)
-    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() < need:
-        raise _lib.DrnError("shortlist_segments_topn_q8: ws must be a contiguous int64 tensor of at least %d elements" % need)
-    _timed("shortlist_segments_topn_q8", 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_q8(
-        _p(codes), _p(scales), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), R, V, nblocks, E, S, n, dtype_code(queries), _p(ws),
-        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn_q8"))
-    return ids, scores, counts, rows
+    if len(qs) != 2 or not queries.is_contiguous() or queries.dtype not in (torch.float32, torch.bfloat16) or qs[1] != cs[1]:
+        raise _lib.DrnError("%s: queries must be a contiguous (S, %d) float32 / bfloat16 tensor" % (what, cs[1]))
+    return cs
 
 
 def allow_words(V):
@@ -1654,6 +1541,14 @@ def _allow_stride(what, allow, V, S):
     return 0 if allow.dim() == 1 else W
 
 
+def _allow_args(what, allow, V, S):
+    """An optional packed mask as the entries take it -> (mask pointer, allow_stride): (NULL, 0) without one, else _allow_stride's checks."""
+    if allow is None:
+        return None, 0
+    stride = _allow_stride(what, allow, V, S)
+    return _p(allow), stride
+
+
 def _shortlist_buffers(what, S, n, need, ws, ids, scores, counts, rows=None):
     """The checks the shortlist wrappers share: n, the output buffers and the workspace."""
     if not 1 <= n <= _lib.SHORTLIST_MAX:
@@ -1680,85 +1575,63 @@ def _segment_tables(what, offsets, blk_vid, vid_blk):
 
 
 def _plain_table(what, emb, queries):
-    """The checks a plain table shares between the two masked shortlists -> (rows, E)."""
-    if emb.dim() != 2 or queries.dim() != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype \
-            or emb.shape[1] != queries.shape[1]:
+    """The checks a plain table shares between the shortlist wrappers -> (rows, E)."""
+    es, qs = emb.shape, queries.shape
+    if len(es) != 2 or len(qs) != 2 or not emb.is_contiguous() or not queries.is_contiguous() or emb.dtype != queries.dtype or es[1] != qs[1]:
         raise _lib.DrnError("%s: emb (rows, E) and queries (S, E) must be contiguous and of one dtype and width" % what)
-    return int(emb.shape[0]), int(emb.shape[1])
+    return int(es[0]), int(es[1])
 
 
-def shortlist_topn_allow(emb, queries, allow, n, ws, ids, scores, counts):
-    """shortlist_topn over the videos a packed mask allows: allow (W,) -- one mask for every sentence -- or (S, W) int32 on the device,
-    W = allow_words(V), bit v & 31 of word v >> 5 set = video v may be listed, bits past V ignored (drn_shortlist_topn_allow;
-    drn_amd.retrieve.shortlist_reference(..., allow=) is the definition).  A listed score has shortlist_topn's bits; every other argument
-    as there.  Two launches behind one entry (one tag, shortlist_topn_allow); the mask is not read on the host."""
-    what = "shortlist_topn_allow"
-    _need_gpu(emb, queries, allow, ws, ids, scores, counts)
+def _shortlist_entry(table, queries, seg, n, ws, outs, allow):
+    """The eight entries behind shortlist_topn (seg = ()) and shortlist_segments_topn (seg = (offsets, blk_vid, vid_blk)).  ONE name --
+    shortlist[_segments]_topn[_q8][_allow], _q8 for a (codes, scales) pair and _allow for a mask -- is the prefix of every refusal, the
+    timer's tag and, behind drn_, the C symbol; the arguments follow include/drn_hip.h: table, queries, [the segment tables], [allow,
+    allow_stride], [R], V, [nblocks], E, S, n, dtype, ws, its keys, the outputs, the stream."""
+    q8 = isinstance(table, (tuple, list))
+    what = "shortlist%s_topn%s%s" % ("_segments" if seg else "", "_q8" if q8 else "", "" if allow is None else "_allow")
+    tensors = (tuple(table) if q8 else (table,)) + (queries,) + seg
+    _need_gpu(*(tensors + (allow, ws) + outs))
     n = int(n)
-    V, E = _plain_table(what, emb, queries)
+    rows, E = _q8_table(what, table[0], table[1], queries) if q8 else _plain_table(what, table, queries)
     S = int(queries.shape[0])
-    _shortlist_buffers(what, S, n, shortlist_ws_keys(V, S, n), ws, ids, scores, counts)
-    stride = _allow_stride(what, allow, V, S)
-    _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_allow(
-        _p(emb), _p(queries), _p(allow), stride, V, E, S, n, dtype_code(emb), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores),
-        _p(counts), _stream()), "drn_shortlist_topn_allow"))
-    return ids, scores, counts
+    if seg:
+        V, nblocks = _segment_tables(what, *seg)
+        need, sizes = shortlist_segments_ws_keys(nblocks, S, n), (rows, V, nblocks)
+    else:
+        V = rows
+        need, sizes = shortlist_ws_keys(V, S, n), (V,)
+    _shortlist_buffers(what, S, n, need, ws, *outs)
+    mask = () if allow is None else _allow_args(what, allow, V, S)
+    args = tuple(_p(t) for t in tensors) + mask + sizes + (E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff))) \
+        + tuple(_p(t) for t in outs)
+    _timed(what, 2.0 * S * rows * E, lambda: check(getattr(lib(), "drn_" + what)(*args, _stream()), "drn_" + what))
+    return outs
 
 
-def shortlist_segments_topn_allow(emb, queries, offsets, blk_vid, vid_blk, allow, n, ws, ids, scores, counts, rows):
-    """shortlist_segments_topn over the VIDEOS a packed mask allows (not rows): allow (W,) or (S, W) int32, W = allow_words(V), as in
-    shortlist_topn_allow (drn_shortlist_segments_topn_allow; drn_amd.retrieve.segment_shortlist_reference(..., allow=) is the
-    definition).  Every other argument as in shortlist_segments_topn.  Three launches behind one entry (one tag,
-    shortlist_segments_topn_allow); nothing is read on the host."""
-    what = "shortlist_segments_topn_allow"
-    _need_gpu(emb, queries, offsets, blk_vid, vid_blk, allow, ws, ids, scores, counts, rows)
-    n = int(n)
-    R, E = _plain_table(what, emb, queries)
-    S = int(queries.shape[0])
-    V, nblocks = _segment_tables(what, offsets, blk_vid, vid_blk)
-    _shortlist_buffers(what, S, n, shortlist_segments_ws_keys(nblocks, S, n), ws, ids, scores, counts, rows)
-    stride = _allow_stride(what, allow, V, S)
-    _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_allow(
-        _p(emb), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), _p(allow), stride, R, V, nblocks, E, S, n, dtype_code(emb), _p(ws),
-        int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()), "drn_shortlist_segments_topn_allow"))
-    return ids, scores, counts, rows
+def shortlist_topn(table, queries, n, ws, ids, scores, counts, allow=None):
+    """Each sentence's best n rows of a table by dot product with its row of `queries` (S, E), into ids (S, n) int32, scores (S, n)
+    float32 and counts (S,) int32, all written in place (drn_amd.retrieve.shortlist_reference is the definition: finite scores only, score
+    descending then position ascending, -1 / 0 past the list).  table: emb (V, E), contiguous like the queries and of their dtype
+    (float32 / bfloat16), or a pair (codes, scales) of a block-scaled FP8 table -- codes (V, E) and scales (V, E / 32) uint8 as
+    quantize_rows_mx8 writes them, E % 32 == 0 -- beside float32 / bfloat16 queries, whose dtype chooses the MFMA chain: the result is
+    then bit for bit that over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype).  allow: None, or a packed mask (W,) -- one
+    for every sentence -- or (S, W) int32 on the device, W = allow_words(V), bit v & 31 of word v >> 5 set = video v may be listed, bits
+    past V ignored (shortlist_reference(..., allow=) is the definition): a listed score has the unmasked bits, the mask is not read on
+    the host, and None reaches the unmasked entry, which takes no mask at all.  ws: an int64 tensor of at least
+    shortlist_ws_keys(V, S, n) elements.  One C entry and one tag per kind of call (drn_shortlist_topn[_q8][_allow]; the tag is the
+    name without drn_): two launches on the current stream, no host synchronisation."""
+    return _shortlist_entry(table, queries, (), n, ws, (ids, scores, counts), allow)
 
 
-def shortlist_topn_q8_allow(codes, scales, queries, allow, n, ws, ids, scores, counts):
-    """shortlist_topn_q8 over the videos a packed mask allows: allow as in shortlist_topn_allow (drn_shortlist_topn_q8_allow).  The
-    result is bit for bit shortlist_topn_allow over drn_amd.index.mx8_dequantize(codes, scales, queries.dtype).  Two launches behind one
-    entry (one tag, shortlist_topn_q8_allow); the mask is not read on the host."""
-    what = "shortlist_topn_q8_allow"
-    _need_gpu(codes, scales, queries, allow, ws, ids, scores, counts)
-    n = int(n)
-    V, E = _q8_table(what, codes, scales, queries)
-    S = int(queries.shape[0])
-    _shortlist_buffers(what, S, n, shortlist_ws_keys(V, S, n), ws, ids, scores, counts)
-    stride = _allow_stride(what, allow, V, S)
-    _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_topn_q8_allow(
-        _p(codes), _p(scales), _p(queries), _p(allow), stride, V, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)),
-        _p(ids), _p(scores), _p(counts), _stream()), "drn_shortlist_topn_q8_allow"))
-    return ids, scores, counts
-
-
-def shortlist_segments_topn_q8_allow(codes, scales, queries, offsets, blk_vid, vid_blk, allow, n, ws, ids, scores, counts, rows):
-    """shortlist_segments_topn_q8 over the VIDEOS a packed mask allows: allow as in shortlist_topn_allow
-    (drn_shortlist_segments_topn_q8_allow).  The result is bit for bit shortlist_segments_topn_allow over
-    drn_amd.index.mx8_dequantize(codes, scales, queries.dtype).  Three launches behind one entry (one tag,
-    shortlist_segments_topn_q8_allow); nothing is read on the host."""
-    what = "shortlist_segments_topn_q8_allow"
-    _need_gpu(codes, scales, queries, offsets, blk_vid, vid_blk, allow, ws, ids, scores, counts, rows)
-    n = int(n)
-    R, E = _q8_table(what, codes, scales, queries)
-    S = int(queries.shape[0])
-    V, nblocks = _segment_tables(what, offsets, blk_vid, vid_blk)
-    _shortlist_buffers(what, S, n, shortlist_segments_ws_keys(nblocks, S, n), ws, ids, scores, counts, rows)
-    stride = _allow_stride(what, allow, V, S)
-    _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_topn_q8_allow(
-        _p(codes), _p(scales), _p(queries), _p(offsets), _p(blk_vid), _p(vid_blk), _p(allow), stride, R, V, nblocks, E, S, n,
-        dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _p(rows), _stream()),
-        "drn_shortlist_segments_topn_q8_allow"))
-    return ids, scores, counts, rows
+def shortlist_segments_topn(table, queries, offsets, blk_vid, vid_blk, n, ws, ids, scores, counts, rows, allow=None):
+    """Each sentence's best n videos of a RAGGED table by their best row: table (R, E) or (codes, scales), queries (S, E) and allow --
+    over the V VIDEOS, not the rows -- as in shortlist_topn; offsets (V + 1,), blk_vid (nblocks + 1,) and vid_blk (V,) int32 on the device
+    (the rows of each video and the block plan, drn_amd.retrieve.plan_segment_blocks) -> ids, scores (S, n), counts (S,) and rows (S, n)
+    int32, all written in place (drn_amd.retrieve.segment_shortlist_reference is the definition, with allow= under a mask; a quantised
+    table answers bit for bit like its mx8_dequantize).  ws: an int64 tensor of at least shortlist_segments_ws_keys(nblocks, S, n)
+    elements.  One C entry and one tag per kind of call (drn_shortlist_segments_topn[_q8][_allow]): three launches on the current
+    stream; the tables and the mask are not read on the host and nothing is synchronised."""
+    return _shortlist_entry(table, queries, (offsets, blk_vid, vid_blk), n, ws, (ids, scores, counts, rows), allow)
 
 
 def shortlist_late_ws_keys(nblocks, S, n):
@@ -1773,7 +1646,7 @@ def shortlist_late_topn(table, queries, lengths, offsets, blk_vid, n, ws, ids, s
     [0, L] there; offsets (V + 1,) and blk_vid (nblocks + 1,) int32 on the device as in shortlist_segments_topn -> ids, scores (S, n)
     and counts (S,), written in place: each sentence's best n videos by the sum over its live tokens of the video's best row
     (drn_shortlist_late_topn / drn_shortlist_late_topn_q8; drn_amd.retrieve.late_shortlist_reference is the definition).  allow: None, or
-    a packed mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_late_ws_keys(nblocks, S, n) elements.  Two
+    a packed mask as in shortlist_topn.  ws: an int64 tensor of at least shortlist_late_ws_keys(nblocks, S, n) elements.  Two
     launches on the current stream behind one entry (one tag, shortlist_late_topn); nothing is read on the host."""
     what = "shortlist_late_topn"
     q8 = isinstance(table, (tuple, list))
@@ -1790,15 +1663,9 @@ def shortlist_late_topn(table, queries, lengths, offsets, blk_vid, n, ws, ids, s
         raise _lib.DrnError("%s: queries must hold a sentence at least, not %s" % (what, tuple(queries.shape)))
     if lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous():
         raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
-    if offsets.dim() != 1 or offsets.numel() < 2 or blk_vid.dim() != 1 or blk_vid.numel() < 2:
-        raise _lib.DrnError("%s: offsets must be (V + 1,) and blk_vid (nblocks + 1,), V >= 1 and nblocks >= 1" % what)
-    V, nblocks = int(offsets.numel()) - 1, int(blk_vid.numel()) - 1
-    for name, t in (("offsets", offsets), ("blk_vid", blk_vid)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise _lib.DrnError("%s: %s must be a contiguous torch.int32 tensor" % (what, name))
+    V, nblocks = _rank_plan(what, offsets, blk_vid)
     _shortlist_buffers(what, S, n, shortlist_late_ws_keys(nblocks, S, n), ws, ids, scores, counts)
-    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
-    mask = None if allow is None else _p(allow)
+    mask, stride = _allow_args(what, allow, V, S)
     tail = (_p(queries), _p(lengths), _p(offsets), _p(blk_vid), mask, stride, R, V, nblocks, E, S, L, n, dtype_code(queries), _p(ws),
             int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts), _stream())
     if q8:
@@ -1854,7 +1721,7 @@ def shortlist_rank(table, queries, targets, ws, rank, score, total, allow=None):
     block-scaled FP8 table; queries (S, E) of the table's dtype (float32 / bfloat16 beside codes); targets (S,) int32 ON THE DEVICE, a
     value outside [0, V) meaning "no target" -> rank (S,) int32 (-1: the target is no candidate), score (S,) float32 (the target's, with
     shortlist_topn's bits; 0 beside -1) and total (S,) int32 (the sentence's candidates), written in place.  allow: None, or a packed
-    mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_rank_ws_bytes(ceil(V / SHORTLIST_BLOCK), S) bytes.
+    mask as in shortlist_topn.  ws: an int64 tensor of at least shortlist_rank_ws_bytes(ceil(V / SHORTLIST_BLOCK), S) bytes.
     Three launches on the current stream behind one entry (one tag, shortlist_rank); nothing is read on the host."""
     what = "shortlist_rank"
     if queries.dim() != 2:
@@ -1863,8 +1730,7 @@ def shortlist_rank(table, queries, targets, ws, rank, score, total, allow=None):
     _need_gpu(*(tensors + (queries, targets, ws, rank, score, total) + (() if allow is None else (allow,))))
     S = int(queries.shape[0])
     have = _rank_buffers(what, S, shortlist_rank_ws_bytes(-(-V // _lib.SHORTLIST_BLOCK), S), targets, ws, rank, score, total)
-    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
-    mask = None if allow is None else _p(allow)
+    mask, stride = _allow_args(what, allow, V, S)
     _timed(what, 2.0 * S * V * E, lambda: check(lib().drn_shortlist_rank(
         tab, scl, _p(queries), _p(targets), mask, stride, V, E, S, dtype_code(queries), _p(ws), have, _p(rank), _p(score), _p(total),
         _stream()), "drn_shortlist_rank"))
@@ -1885,8 +1751,7 @@ def shortlist_segments_rank(table, queries, offsets, blk_vid, targets, ws, rank,
     S = int(queries.shape[0])
     V, nblocks = _rank_plan(what, offsets, blk_vid)
     have = _rank_buffers(what, S, shortlist_rank_ws_bytes(nblocks, S), targets, ws, rank, score, total)
-    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
-    mask = None if allow is None else _p(allow)
+    mask, stride = _allow_args(what, allow, V, S)
     _timed(what, 2.0 * S * R * E, lambda: check(lib().drn_shortlist_segments_rank(
         tab, scl, _p(queries), _p(offsets), _p(blk_vid), _p(targets), mask, stride, R, V, nblocks, E, S, dtype_code(queries), _p(ws), have,
         _p(rank), _p(score), _p(total), _stream()), "drn_shortlist_segments_rank"))
@@ -1909,8 +1774,7 @@ def shortlist_late_rank(table, queries, lengths, offsets, blk_vid, targets, ws, 
         raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
     V, nblocks = _rank_plan(what, offsets, blk_vid)
     have = _rank_buffers(what, S, shortlist_rank_ws_bytes(nblocks, S), targets, ws, rank, score, total)
-    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
-    mask = None if allow is None else _p(allow)
+    mask, stride = _allow_args(what, allow, V, S)
     _timed(what, 2.0 * S * L * R * E, lambda: check(lib().drn_shortlist_late_rank(
         tab, scl, _p(queries), _p(lengths), _p(offsets), _p(blk_vid), _p(targets), mask, stride, R, V, nblocks, E, S, L, dtype_code(queries),
         _p(ws), have, _p(rank), _p(score), _p(total), _stream()), "drn_shortlist_late_rank"))
@@ -1930,7 +1794,7 @@ def shortlist_rerank(table, queries, lengths, offsets, candidates, n, ws, ids, s
     in shortlist_segments_topn, or None: row v is video v; candidates (S, C) int32 ON THE DEVICE, 1 <= C <= RERANK_MAX_CANDIDATES, row
     s the set of positions sentence s may list -- an entry outside [0, V) means nothing, a repeat counts once -> ids, scores (S, n) and
     counts (S,), written in place, bit for bit what shortlist_late_topn gives under the mask "listed, and allowed".  allow: None, or a
-    packed mask as in shortlist_topn_allow.  ws: an int64 tensor of at least shortlist_rerank_ws_keys(C, S, n) elements.  Two launches
+    packed mask as in shortlist_topn.  ws: an int64 tensor of at least shortlist_rerank_ws_keys(C, S, n) elements.  Two launches
     on the current stream behind one entry (one tag, shortlist_rerank); nothing is read on the host -- so the flop figure handed to
     the timer is NOMINAL, 2 S L C (R / V) E: every slot a distinct valid video of the mean run, which the host cannot know."""
     what = "shortlist_rerank"
@@ -1956,8 +1820,7 @@ def shortlist_rerank(table, queries, lengths, offsets, candidates, n, ws, ids, s
                             % (what, S, _lib.RERANK_MAX_CANDIDATES, candidates.dtype, tuple(candidates.shape)))
     C = int(candidates.shape[1])
     _shortlist_buffers(what, S, n, shortlist_rerank_ws_keys(C, S, n), ws, ids, scores, counts)
-    stride = 0 if allow is None else _allow_stride(what, allow, V, S)
-    mask = None if allow is None else _p(allow)
+    mask, stride = _allow_args(what, allow, V, S)
     _timed(what, 2.0 * S * L * C * (float(R) / V) * E, lambda: check(lib().drn_shortlist_rerank(
         tab, scl, _p(queries), None if lengths is None else _p(lengths), None if offsets is None else _p(offsets), _p(candidates), mask,
         stride, R, V, E, S, L, C, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids), _p(scores), _p(counts),

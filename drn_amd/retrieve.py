@@ -483,13 +483,29 @@ def _check_packed_allow(allow, S, V, dev):
         raise DrnError("Shortlister.shortlist: allow must be contiguous")
 
 
-def _check_list_out(what, out, S, n):
-    """out= of a method that returns a Shortlist: three buffers of its shapes and dtypes."""
-    if len(out) != 3:
+def _check_list_out(what, out, S, n, rows=False):
+    """out= of a method that returns a Shortlist -- with rows, a SegmentShortlist: the buffers of its shapes and dtypes."""
+    if rows and len(out) != 4:
+        raise DrnError("%s: out must hold the four buffers of a SegmentShortlist (ids, scores, n, rows), not %d" % (what, len(out)))
+    if not rows and len(out) != 3:
         raise DrnError("%s: out must hold the three buffers of a Shortlist (ids, scores, n), not %d" % (what, len(out)))
-    for name, t, dt, shape in zip(Shortlist._fields, out, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))):
+    for name, t, dt, shape in zip(SegmentShortlist._fields, out, (torch.int32, torch.float32, torch.int32, torch.int32),
+                                  ((S, n), (S, n), (S,), (S, n))):
         if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+
+
+def _list_buffers(dev, S, n, rows=False):
+    """The result buffers (ids, scores, n[, rows]) of lists of n a sentence, made on dev."""
+    out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
+           torch.empty((S,), dtype=torch.int32, device=dev))
+    return out + (torch.empty((S, n), dtype=torch.int32, device=dev),) if rows else out
+
+
+def _refuse_late(what, instead, whose="this table has"):
+    """The refusal of late interaction over one row per video; `instead` is the method that answers there."""
+    raise DrnError("%s: %s one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . emb_v = "
+                   "(sum_t q_t) . emb_v: add each sentence's live token vectors and call %s()" % (what, whose, instead))
 
 
 def quantized_score_bound(embeddings, scales, queries):
@@ -529,7 +545,7 @@ class Shortlister(object):
     E; embeddings (the table, None on a quantised object); codes and scales (None on a plain one); names; offsets and plan on a ragged
     table; nbytes, the bytes of the table held (= bytes_of(rows, E, dtype, quantize))."""
 
-    quantize = codes = scales = _dtype = None     # (what a plain table has; also for an object made without the constructor)
+    quantize = codes = scales = _dtype = _seg = None     # (what a plain table has; also for an object made without the constructor)
 
     def __init__(self, embeddings, names=None, offsets=None, quantize=None):
         if quantize not in QUANTIZE:
@@ -600,7 +616,6 @@ class Shortlister(object):
         """What every way of building shares: names, offsets and the block plan, and the ONE synchronise that brings sound() -- a
         device boolean, launched here after the host-side refusals -- to the host."""
         self.names = None if names is None else list(names)
-        self._seg = None
         self._ws = {}
         if offsets is not None:
             self._init_segments(rows, dev, offsets, sound, unsound)
@@ -633,6 +648,21 @@ class Shortlister(object):
     def _table(self):
         """The tensor that has the table's rows, columns and device: the embeddings, or the codes of a quantised table."""
         return self.embeddings if self.quantize is None else self.codes
+
+    def _operand(self):
+        """The table as the ops wrappers take it: the embeddings, or the pair (codes, scales) of a quantised table."""
+        return self.embeddings if self.quantize is None else (self.codes, self.scales)
+
+    def _nblocks(self):
+        """The blocks a sentence's first launch ranks: ceil(V / SHORTLIST_BLOCK) on a plain table, the plan's on a ragged one."""
+        return -(-len(self) // SHORTLIST_BLOCK) if self._seg is None else int(self._seg[1].shape[0]) - 1
+
+    def _workspace(self, key, keys):
+        """The int64 workspace kept as self._ws[key]; keys() is its size in elements, asked for when it has to be made."""
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.empty(keys(), dtype=torch.int64, device=self._table().device)
+        return ws
 
     @property
     def dtype(self):
@@ -668,12 +698,11 @@ class Shortlister(object):
         really holds, and the oracle shortlist() answers bit for bit like.  (On a plain table: itself.)"""
         if self.quantize is None:
             return self
-        seg = getattr(self, "_seg", None)
-        return Shortlister(mx8_dequantize(self.codes, self.scales, self._dtype), names=self.names, offsets=None if seg is None else seg[0])
+        return Shortlister(mx8_dequantize(self.codes, self.scales, self._dtype), names=self.names,
+                           offsets=None if self._seg is None else self._seg[0])
 
     def __len__(self):
-        seg = getattr(self, "_seg", None)
-        return int(self._table().shape[0]) if seg is None else int(seg[0].shape[0]) - 1
+        return int(self._table().shape[0]) if self._seg is None else int(self._seg[0].shape[0]) - 1
 
     def check(self, store):
         """Raises unless this table's names are the store's (a FeatureStore or a SearchIndex), position by position."""
@@ -692,33 +721,35 @@ class Shortlister(object):
         """The refusals of shortlist(allow=), before the library is reached."""
         _check_packed_allow(allow, S, len(self), self._table().device)
 
-    def _check(self, queries, n, out):
-        """shortlist's refusals, before the library is reached -> (S, n)."""
+    def _check_queries(self, what, queries, S=None, n=None, on_table=True):
+        """What shortlist, rank and rerank refuse about queries of one vector a sentence and (where given) n -> (S, n).  S: the rows
+        they must have (rerank: one per row of candidates), None for any S >= 1.  on_table: rank and rerank ask for the table's
+        device, shortlist for the GPU."""
         E, dtype = self.E, self.dtype
         if not torch.is_tensor(queries):
-            raise DrnError("Shortlister.shortlist: the queries must be a tensor")
-        if queries.dim() != 2 or queries.shape[0] < 1 or queries.shape[1] != E:
-            raise DrnError("Shortlister.shortlist: the queries must be (S, %d), not %s" % (E, tuple(queries.shape)))
+            raise DrnError("%s: the queries must be a tensor" % what)
+        shape = tuple(queries.shape)
+        if len(shape) != 2 or shape[1] != E or (shape[0] < 1 if S is None else shape[0] != S):
+            want = "(S, %d)" % E if S is None else "(%d, %d), a row per row of candidates" % (S, E)
+            raise DrnError("%s: the queries must be %s, not %s" % (what, want, shape))
         if queries.dtype != dtype:
-            raise DrnError("Shortlister.shortlist: the queries are %s, the table is %s" % (queries.dtype, dtype))
-        n = int(n)
-        if not 1 <= n <= SHORTLIST_MAX:
-            raise DrnError("Shortlister.shortlist: n = %d outside [1, %d]" % (n, SHORTLIST_MAX))
-        if not queries.is_cuda:
-            raise DrnError("Shortlister.shortlist: the queries must be on the GPU; there is no CPU fallback")
-        S = int(queries.shape[0])
+            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
+        if n is not None:
+            n = int(n)
+            if not 1 <= n <= SHORTLIST_MAX:
+                raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
+        if not on_table:
+            if not queries.is_cuda:
+                raise DrnError("%s: the queries must be on the GPU; there is no CPU fallback" % what)
+        elif not queries.is_cuda or queries.device != self._table().device:
+            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, self._table().device))
+        return shape[0], n
+
+    def _check(self, queries, n, out):
+        """shortlist's refusals, before the library is reached -> (S, n)."""
+        S, n = self._check_queries("Shortlister.shortlist", queries, n=n, on_table=False)
         if out is not None:
-            if getattr(self, "_seg", None) is None:
-                fields, dtypes, shapes = Shortlist._fields, (torch.int32, torch.float32, torch.int32), ((S, n), (S, n), (S,))
-            else:
-                fields, dtypes = SegmentShortlist._fields, (torch.int32, torch.float32, torch.int32, torch.int32)
-                shapes = ((S, n), (S, n), (S,), (S, n))
-                if len(out) != 4:
-                    raise DrnError("Shortlister.shortlist: out must hold the four buffers of a SegmentShortlist (ids, scores, n, rows), "
-                                   "not %d" % len(out))
-            for name, t, dt, shape in zip(fields, out, dtypes, shapes):
-                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise DrnError("Shortlister.shortlist: out.%s must be a contiguous %s %s tensor on the GPU" % (name, shape, dt))
+            _check_list_out("Shortlister.shortlist", out, S, n, rows=self._seg is not None)
         return S, n
 
     def shortlist(self, queries, n, out=None, allow=None):
@@ -747,39 +778,16 @@ class Shortlister(object):
         S, n = self._check(queries, n, out)
         if allow is not None:
             self._check_allow(allow, S)
-        dev = self._table().device
-        q8 = self.quantize is not None
-        seg = getattr(self, "_seg", None)
+        seg = self._seg
         if out is None:
-            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
-            if seg is not None:
-                out += (torch.empty((S, n), dtype=torch.int32, device=dev),)
-        ws = self._ws.get((S, n))
-        if seg is not None:
-            if ws is None:
-                keys = ops.shortlist_segments_ws_keys(int(seg[1].shape[0]) - 1, S, n)
-                ws = self._ws[(S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
-            if allow is not None and q8:
-                ops.shortlist_segments_topn_q8_allow(self.codes, self.scales, queries.contiguous(), seg[0], seg[1], seg[2], allow, n, ws, *out)
-            elif allow is not None:
-                ops.shortlist_segments_topn_allow(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], allow, n, ws, *out)
-            elif q8:
-                ops.shortlist_segments_topn_q8(self.codes, self.scales, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
-            else:
-                ops.shortlist_segments_topn(self.embeddings, queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out)
-            return SegmentShortlist(*out)
-        if ws is None:
-            ws = self._ws[(S, n)] = torch.empty(ops.shortlist_ws_keys(len(self), S, n), dtype=torch.int64, device=dev)
-        if allow is not None and q8:
-            ops.shortlist_topn_q8_allow(self.codes, self.scales, queries.contiguous(), allow, n, ws, *out)
-        elif allow is not None:
-            ops.shortlist_topn_allow(self.embeddings, queries.contiguous(), allow, n, ws, *out)
-        elif q8:
-            ops.shortlist_topn_q8(self.codes, self.scales, queries.contiguous(), n, ws, *out)
-        else:
-            ops.shortlist_topn(self.embeddings, queries.contiguous(), n, ws, *out)
-        return Shortlist(*out)
+            out = _list_buffers(self._table().device, S, n, rows=seg is not None)
+        if seg is None:
+            ws = self._workspace((S, n), lambda: ops.shortlist_ws_keys(len(self), S, n))
+            ops.shortlist_topn(self._operand(), queries.contiguous(), n, ws, *out, allow=allow)
+            return Shortlist(*out)
+        ws = self._workspace((S, n), lambda: ops.shortlist_segments_ws_keys(self._nblocks(), S, n))
+        ops.shortlist_segments_topn(self._operand(), queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out, allow=allow)
+        return SegmentShortlist(*out)
 
     def shortlist_late(self, queries, lengths, n, out=None, allow=None):
         """The shortlist by LATE INTERACTION (late_shortlist_reference defines it) -> Shortlist, on the device.  queries: contiguous
@@ -795,25 +803,18 @@ class Shortlister(object):
         quantised.  A table without offsets is refused: with one row per video the sum over the tokens of q_t . emb_v is (the sum of
         q_t) . emb_v, so the caller adds the live tokens and calls shortlist()."""
         what = "Shortlister.shortlist_late"
-        seg = getattr(self, "_seg", None)
+        seg = self._seg
         if seg is None:
-            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
-                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call shortlist()" % what)
-        dev = self._table().device
+            _refuse_late(what, "shortlist")
         S, L, n = self._check_late(what, queries, lengths, n)
         if out is not None:
             _check_list_out(what, out, S, n)
         if allow is not None:
             self._check_allow(allow, S)
         if out is None:
-            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
-        ws = self._ws.get(("late", S, n))
-        if ws is None:
-            keys = ops.shortlist_late_ws_keys(int(seg[1].shape[0]) - 1, S, n)
-            ws = self._ws[("late", S, n)] = torch.empty(keys, dtype=torch.int64, device=dev)
-        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
-        ops.shortlist_late_topn(table, queries, lengths, seg[0], seg[1], n, ws, *out, allow=allow)
+            out = _list_buffers(self._table().device, S, n)
+        ws = self._workspace(("late", S, n), lambda: ops.shortlist_late_ws_keys(self._nblocks(), S, n))
+        ops.shortlist_late_topn(self._operand(), queries, lengths, seg[0], seg[1], n, ws, *out, allow=allow)
         return Shortlist(*out)
 
     def _check_late(self, what, queries, lengths, n=None):
@@ -868,20 +869,15 @@ class Shortlister(object):
 
     def _rerank(self, what, S, C, n, candidates, queries, lengths, out, allow):
         """What rerank and rerank_late share once their tensors are checked: out=, allow=, the workspace and the launch."""
-        dev = self._table().device
         if out is not None:
             _check_list_out(what, out, S, n)
         if allow is not None:
             self._check_allow(allow, S)
         if out is None:
-            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
-        ws = self._ws.get(("rerank", S, C, n))
-        if ws is None:
-            ws = self._ws[("rerank", S, C, n)] = torch.empty(ops.shortlist_rerank_ws_keys(C, S, n), dtype=torch.int64, device=dev)
-        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
-        seg = getattr(self, "_seg", None)
-        ops.shortlist_rerank(table, queries, lengths, None if seg is None else seg[0], candidates, n, ws, *out, allow=allow)
+            out = _list_buffers(self._table().device, S, n)
+        ws = self._workspace(("rerank", S, C, n), lambda: ops.shortlist_rerank_ws_keys(C, S, n))
+        offsets = None if self._seg is None else self._seg[0]
+        ops.shortlist_rerank(self._operand(), queries, lengths, offsets, candidates, n, ws, *out, allow=allow)
         return Shortlist(*out)
 
     def rerank(self, candidates, queries, n=None, out=None, allow=None):
@@ -905,16 +901,8 @@ class Shortlister(object):
         in place between replays."""
         what = "Shortlister.rerank"
         S, C, n = self._check_candidates(what, candidates, n)
-        E, dtype, dev = self.E, self.dtype, self._table().device
-        if not torch.is_tensor(queries):
-            raise DrnError("%s: the queries must be a tensor" % what)
-        if queries.dim() != 2 or queries.shape[0] != S or queries.shape[1] != E:
-            raise DrnError("%s: the queries must be (%d, %d), a row per row of candidates, not %s" % (what, S, E, tuple(queries.shape)))
-        if queries.dtype != dtype:
-            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
-        if not queries.is_cuda or queries.device != dev:
-            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
-        return self._rerank(what, S, C, n, candidates, queries.contiguous().view(S, 1, E), None, out, allow)
+        self._check_queries(what, queries, S)
+        return self._rerank(what, S, C, n, candidates, queries.contiguous().view(S, 1, -1), None, out, allow)
 
     def rerank_late(self, candidates, queries, lengths, n=None, out=None, allow=None):
         """rerank() by LATE INTERACTION -> Shortlist (late_rerank_reference defines it), on the device: candidates and n as in
@@ -926,9 +914,8 @@ class Shortlister(object):
         per ("rerank", S, C, n)), where candidates, queries, lengths and the mask's contents may change in place between replays.  A
         table without offsets is refused as in shortlist_late()."""
         what = "Shortlister.rerank_late"
-        if getattr(self, "_seg", None) is None:
-            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
-                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call rerank()" % what)
+        if self._seg is None:
+            _refuse_late(what, "rerank")
         S, C, n = self._check_candidates(what, candidates, n)
         Sq, _, _ = self._check_late(what, queries, lengths)
         if Sq != S:
@@ -955,12 +942,6 @@ class Shortlister(object):
                    torch.empty((S,), dtype=torch.int32, device=dev))
         return tuple(out)
 
-    def _rank_ws(self, key, nblocks, S):
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = self._ws[key] = torch.empty(ops.shortlist_rank_ws_bytes(nblocks, S) // 8, dtype=torch.int64, device=self._table().device)
-        return ws
-
     def rank(self, queries, targets, out=None, allow=None):
         """The place of each sentence's TARGET video in its full shortlist order -> TargetRank (rank_reference defines it; on a ragged
         table segment_rank_reference), on the device.  queries as in shortlist(); targets: contiguous int32 (S,) on the table's device,
@@ -974,25 +955,14 @@ class Shortlister(object):
         no host synchronisation, and it can be captured in a graph (the workspace is kept per S: warm the shape once), where queries,
         targets and the mask's contents may change in place between replays."""
         what = "Shortlister.rank"
-        E, dtype, dev = self.E, self.dtype, self._table().device
-        if not torch.is_tensor(queries):
-            raise DrnError("%s: the queries must be a tensor" % what)
-        if queries.dim() != 2 or queries.shape[0] < 1 or queries.shape[1] != E:
-            raise DrnError("%s: the queries must be (S, %d), not %s" % (what, E, tuple(queries.shape)))
-        if queries.dtype != dtype:
-            raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
-        if not queries.is_cuda or queries.device != dev:
-            raise DrnError("%s: the queries must be on the table's device %s; there is no CPU fallback" % (what, dev))
-        S = int(queries.shape[0])
+        S, _ = self._check_queries(what, queries)
         out = self._check_rank(what, S, targets, out, allow)
-        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
-        seg = getattr(self, "_seg", None)
+        ws = self._workspace(("rank", S), lambda: ops.shortlist_rank_ws_bytes(self._nblocks(), S) // 8)
+        seg = self._seg
         if seg is None:
-            ws = self._rank_ws(("rank", S), -(-len(self) // SHORTLIST_BLOCK), S)
-            ops.shortlist_rank(table, queries.contiguous(), targets, ws, *out, allow=allow)
+            ops.shortlist_rank(self._operand(), queries.contiguous(), targets, ws, *out, allow=allow)
         else:
-            ws = self._rank_ws(("rank", S), int(seg[1].shape[0]) - 1, S)
-            ops.shortlist_segments_rank(table, queries.contiguous(), seg[0], seg[1], targets, ws, *out, allow=allow)
+            ops.shortlist_segments_rank(self._operand(), queries.contiguous(), seg[0], seg[1], targets, ws, *out, allow=allow)
         return TargetRank(*out)
 
     def rank_late(self, queries, lengths, targets, out=None, allow=None):
@@ -1004,15 +974,13 @@ class Shortlister(object):
         (the workspace is kept per S), where queries, lengths, targets and the mask's contents may change in place between replays.
         A table without offsets is refused as in shortlist_late()."""
         what = "Shortlister.rank_late"
-        seg = getattr(self, "_seg", None)
+        seg = self._seg
         if seg is None:
-            raise DrnError("%s: this table has one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
-                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call rank()" % what)
+            _refuse_late(what, "rank")
         S, L, _ = self._check_late(what, queries, lengths)
         out = self._check_rank(what, S, targets, out, allow)
-        ws = self._rank_ws(("rank_late", S), int(seg[1].shape[0]) - 1, S)
-        table = self.embeddings if self.quantize is None else (self.codes, self.scales)
-        ops.shortlist_late_rank(table, queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
+        ws = self._workspace(("rank_late", S), lambda: ops.shortlist_rank_ws_bytes(self._nblocks(), S) // 8)
+        ops.shortlist_late_rank(self._operand(), queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
         return TargetRank(*out)
 
 
@@ -1067,9 +1035,9 @@ class ShardedShortlister(object):
                 raise DrnError("ShardedShortlister: shard %d has E = %d columns, the others %d" % (len(self.shards), shard.E, first.E))
             if shard.dtype != first.dtype:
                 raise DrnError("ShardedShortlister: shard %d takes %s queries, the others %s" % (len(self.shards), shard.dtype, first.dtype))
-            if (getattr(shard, "_seg", None) is None) != (getattr(first, "_seg", None) is None):
+            if (shard._seg is None) != (first._seg is None):
                 raise DrnError("ShardedShortlister: shard %d is %s, the others are not: the shards must all be plain or all have offsets= "
-                               "(the result types differ)" % (len(self.shards), "plain" if getattr(shard, "_seg", None) is None else "ragged"))
+                               "(the result types differ)" % (len(self.shards), "plain" if shard._seg is None else "ragged"))
         if self.bases[-1] + len(shard) >= 2 ** 31:
             raise DrnError("ShardedShortlister: %d videos with shard %d, outside [1, 2^31)" % (self.bases[-1] + len(shard), len(self.shards)))
         self.shards.append(shard)
@@ -1133,7 +1101,7 @@ class ShardedShortlister(object):
             dev = self.device
             bufs = (torch.empty((K, S, n), dtype=torch.int32, device=dev), torch.empty((K, S, n), dtype=torch.float32, device=dev),
                     torch.empty((K, S), dtype=torch.int32, device=dev))
-            if getattr(self.shards[0], "_seg", None) is not None:
+            if self.shards[0]._seg is not None:
                 bufs += (torch.empty((K, S, n), dtype=torch.int32, device=dev),)
             self._bufs[(K, S, n)] = bufs
         return bufs
@@ -1167,13 +1135,9 @@ class ShardedShortlister(object):
         S, n = first._check(queries, n, out)
         if allow is not None:
             _check_packed_allow(allow, S, len(self), self.device)
-        ragged = getattr(first, "_seg", None) is not None
-        dev = self.device
+        ragged = first._seg is not None
         if out is None:
-            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
-            if ragged:
-                out += (torch.empty((S, n), dtype=torch.int32, device=dev),)
+            out = _list_buffers(self.device, S, n, rows=ragged)
         lists = self._lists(S, n)
         queries = queries.contiguous()
         for k, (shard, piece) in enumerate(zip(self.shards, self._slices(allow))):
@@ -1191,18 +1155,15 @@ class ShardedShortlister(object):
         warmed, where queries, lengths and the mask's contents may change in place between replays."""
         what = "Shortlister.shortlist_late"
         first = self.shards[0]
-        if getattr(first, "_seg", None) is None:
-            raise DrnError("%s: these tables have one row per video (no offsets=), where late interaction is no new ranking -- sum_t q_t . "
-                           "emb_v = (sum_t q_t) . emb_v: add each sentence's live token vectors and call shortlist()" % what)
+        if first._seg is None:
+            _refuse_late(what, "shortlist", whose="these tables have")
         S, L, n = first._check_late(what, queries, lengths, n)
         if out is not None:
             _check_list_out(what, out, S, n)
         if allow is not None:
             _check_packed_allow(allow, S, len(self), self.device)
-        dev = self.device
         if out is None:
-            out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
+            out = _list_buffers(self.device, S, n)
         lists = self._lists(S, n)
         for k, (shard, piece) in enumerate(zip(self.shards, self._slices(allow))):
             shard.shortlist_late(queries, lengths, n, out=tuple(t[k] for t in lists[:3]), allow=piece)

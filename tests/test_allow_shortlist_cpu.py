@@ -255,10 +255,10 @@ def test_pack_allow_and_the_wrappers_refuse_before_the_library_is_reached(monkey
     outs = (i32(3, 2), resident(torch.zeros(3, 2)), i32(3))
     seg = (i32(4), i32(2), i32(3))                                              # offsets (V = 3), blk_vid (one block), vid_blk
     calls = {
-        "shortlist_topn_allow": (lambda a: ops.shortlist_topn_allow(emb, q, a, 2, ws, *outs), 2),
-        "shortlist_segments_topn_allow": (lambda a: ops.shortlist_segments_topn_allow(emb, q, *seg, a, 2, ws, *outs, i32(3, 2)), 1),
-        "shortlist_topn_q8_allow": (lambda a: ops.shortlist_topn_q8_allow(codes, scales, q, a, 2, ws, *outs), 2),
-        "shortlist_segments_topn_q8_allow": (lambda a: ops.shortlist_segments_topn_q8_allow(codes, scales, q, *seg, a, 2, ws, *outs, i32(3, 2)), 1),
+        "shortlist_topn_allow": (lambda a: ops.shortlist_topn(emb, q, 2, ws, *outs, allow=a), 2),
+        "shortlist_segments_topn_allow": (lambda a: ops.shortlist_segments_topn(emb, q, *seg, 2, ws, *outs, i32(3, 2), allow=a), 1),
+        "shortlist_topn_q8_allow": (lambda a: ops.shortlist_topn((codes, scales), q, 2, ws, *outs, allow=a), 2),
+        "shortlist_segments_topn_q8_allow": (lambda a: ops.shortlist_segments_topn((codes, scales), q, *seg, 2, ws, *outs, i32(3, 2), allow=a), 1),
     }
     for name, (call, W) in calls.items():
         with pytest.raises(_lib.DrnError, match="GPU only"):
@@ -271,11 +271,11 @@ def test_pack_allow_and_the_wrappers_refuse_before_the_library_is_reached(monkey
             with pytest.raises(AssertionError, match="the library was reached"):
                 call(good)
     with pytest.raises(_lib.DrnError, match=r"shortlist_topn_allow: n = 129 outside \[1, 128\]"):
-        ops.shortlist_topn_allow(emb, q, i32(2), 129, ws, *outs)
+        ops.shortlist_topn(emb, q, 129, ws, *outs, allow=i32(2))
     with pytest.raises(_lib.DrnError, match="shortlist_topn_allow: ws must be"):
-        ops.shortlist_topn_allow(emb, q, i32(2), 2, ws[:5], *outs)
+        ops.shortlist_topn(emb, q, 2, ws[:5], *outs, allow=i32(2))
     with pytest.raises(_lib.DrnError, match="shortlist_segments_topn_allow: vid_blk must be"):
-        ops.shortlist_segments_topn_allow(emb, q, seg[0], seg[1], i32(4), i32(1), 2, ws, *outs, i32(3, 2))
+        ops.shortlist_segments_topn(emb, q, seg[0], seg[1], i32(4), 2, ws, *outs, i32(3, 2), allow=i32(1))
 
 
 def test_library_exports_the_five_entries_at_abi_9():
@@ -290,7 +290,8 @@ def test_library_exports_the_five_entries_at_abi_9():
         for p, t in zip(params, sig):
             assert t is (ctypes.c_void_p if "*" in p else ctypes.c_int), (name, p, t)
         assert list(getattr(lib, name).argtypes) == list(sig)
-        assert callable(getattr(ops, name[len("drn_"):]))
+        wrapper = name[len("drn_"):]                                         # a masked entry is its twin's wrapper with allow=
+        assert callable(getattr(ops, wrapper[:wrapper.index("_topn") + len("_topn")] if name in MASKED else wrapper))
     # each masked entry is its twin plus (allow, allow_stride), in front of the sizes
     for name in MASKED:
         twin, mine = _header_params(name[:-len("_allow")]), _header_params(name)

@@ -139,9 +139,9 @@ def test_shortlist_on_a_quantised_table_refuses_before_the_library_is_reached(mo
     # the wrappers themselves refuse host tensors, and widths the format does not have, before the library
     from drn_amd import ops
     with pytest.raises(_lib.DrnError):
-        ops.shortlist_topn_q8(codes.as_subclass(torch.Tensor), scales.as_subclass(torch.Tensor), torch.zeros(2, 64), 2,
-                              torch.zeros(8, dtype=torch.int64), torch.zeros((2, 2), dtype=torch.int32), torch.zeros((2, 2)),
-                              torch.zeros(2, dtype=torch.int32))
+        ops.shortlist_topn((codes.as_subclass(torch.Tensor), scales.as_subclass(torch.Tensor)), torch.zeros(2, 64), 2,
+                           torch.zeros(8, dtype=torch.int64), torch.zeros((2, 2), dtype=torch.int32), torch.zeros((2, 2)),
+                           torch.zeros(2, dtype=torch.int32))
     with pytest.raises(_lib.DrnError, match="E a multiple of 32"):
         ops._q8_table("shortlist_topn_q8", torch.zeros((4, 48), dtype=torch.uint8), torch.zeros((4, 1), dtype=torch.uint8), torch.zeros(2, 48))
 
@@ -204,7 +204,7 @@ def test_library_exports_the_two_q8_entries_at_abi_9():
         for p, t in zip(params, sig):
             assert t is (ctypes.c_void_p if "*" in p else ctypes.c_int), (name, p, t)
         assert list(getattr(lib, name).argtypes) == list(sig)
-    assert callable(ops.shortlist_topn_q8) and callable(ops.shortlist_segments_topn_q8)
+    assert callable(ops.shortlist_topn) and callable(ops.shortlist_segments_topn)
     src = open(os.path.join(ROOT, "drn_amd", "csrc", "retrieve_q8.hip")).read()
     assert int(re.search(r"#define SQ_BLOCK\s+(\d+)", src).group(1)) == _lib.SHORTLIST_BLOCK == _lib.SHORTLIST_SEG_BLOCK
 
