@@ -210,6 +210,15 @@ SIGNATURES = {
     "drn_shortlist_merge_lists": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p],
     "drn_allow_slices": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "drn_shortlist_rank_phase": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p],
+    "drn_shortlist_segments_rank_phase": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "drn_shortlist_late_rank_phase": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "drn_shard_positions": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "drn_shortlist_rank_thresholds": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_rank_reduce_shards": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

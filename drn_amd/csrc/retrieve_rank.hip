@@ -5,6 +5,8 @@
 //   drn_shortlist_segments_rank    the ragged table  (drn_shortlist_segments_topn: a video's best row);
 //   drn_shortlist_late_rank        late interaction  (drn_shortlist_late_topn: the sum over the live tokens of the video's best row).
 // Each takes the table plain (scales == NULL) or in block-scaled FP8 (codes and scales), and a nullable packed allow mask.
+//   drn_shortlist_rank_phase, drn_shortlist_segments_rank_phase, drn_shortlist_late_rank_phase run launch 1 or launch 2 below alone:
+//   the pieces a corpus of several tables ranks with (retrieve_shard_rank.hip).  Same kernels, same bits.
 #include "common.h"
 #include "shortlist.h"
 #include "../../include/drn_hip.h"
@@ -475,13 +477,18 @@ struct RkArgs {
   int32_t* rank;
   float* score;
   int32_t* total;
+  // the phases alone (the *_phase entries; 0 = the three launches above).  1: the target kernel writes S keys to `keys`; 2: the
+  // counting kernel reads S THRESHOLDS from `keys` where it reads tkey, and writes cnt [S][blocks] pairs.  ws and the results are unused.
+  int phase;
+  sl_key_t* keys;
+  int2* cnt;
+  int cnt_bytes;
 };
 
 static int rk_check(const char* what, const RkArgs& a) {
   const bool ragged = a.shape != RK_PLAIN, late = a.shape == RK_LATE;
-  DRN_CHECK_ARG(a.table && a.queries && a.targets && a.ws && a.rank && a.score && a.total && (!ragged || (a.offsets && a.blk_vid)) &&
-                    (!late || a.lengths),
-                "%s: null pointer", what);
+  const bool mine = a.phase == 0 ? a.targets && a.ws && a.rank && a.score && a.total : a.phase == 1 ? a.targets && a.keys : a.keys && a.cnt;
+  DRN_CHECK_ARG(a.table && a.queries && mine && (!ragged || (a.offsets && a.blk_vid)) && (!late || a.lengths), "%s: null pointer", what);
   if (ragged)
     DRN_CHECK_ARG(a.R >= 1 && a.V >= 1 && a.E >= 1 && a.S >= 1, "%s: bad args (R = %d rows, V = %d videos, E = %d columns, S = %d sentences)",
                   what, a.R, a.V, a.E, a.S);
@@ -493,7 +500,7 @@ static int rk_check(const char* what, const RkArgs& a) {
     DRN_CHECK_ARG(a.nblocks >= 1 && a.nblocks <= a.V && (long)a.nblocks * RK_BLOCK >= a.V, "%s: %d blocks outside [ceil(V / %d), V] for V = %d videos",
                   what, a.nblocks, RK_BLOCK, a.V);
   DRN_CHECK_ARG(a.dtype == DRN_F32 || a.dtype == DRN_BF16, "%s: dtype %d (float32 / bfloat16 only)", what, a.dtype);
-  DRN_CHECK_ARG(((uintptr_t)a.table & 15) == 0 && ((uintptr_t)a.queries & 15) == 0 && ((uintptr_t)a.ws & 7) == 0,
+  DRN_CHECK_ARG(((uintptr_t)a.table & 15) == 0 && ((uintptr_t)a.queries & 15) == 0 && (((uintptr_t)a.ws | (uintptr_t)a.keys | (uintptr_t)a.cnt) & 7) == 0,
                 "%s: the table and the queries must be 16-byte aligned, the workspace 8-byte aligned", what);
   DRN_CHECK_ARG(((uintptr_t)a.targets & 3) == 0 && ((uintptr_t)a.lengths & 3) == 0, "%s: targets and lengths must be 4-byte aligned", what);
   if (a.allow) {
@@ -502,37 +509,46 @@ static int rk_check(const char* what, const RkArgs& a) {
                   a.allow_stride, cdiv(a.V, 32));
     DRN_CHECK_ARG(((uintptr_t)a.allow & 3) == 0, "%s: the mask must be 4-byte aligned", what);
   }
-  const long nblocks = ragged ? a.nblocks : cdiv(a.V, RK_BLOCK), need = 8L * a.S * (1 + nblocks);
-  DRN_CHECK_ARG(need <= 0x7fffffffL && a.ws_bytes >= need, "%s: the workspace holds %d bytes, %ld are needed (8 * S * (1 + blocks))", what,
-                a.ws_bytes, need);
+  const long nblocks = ragged ? a.nblocks : cdiv(a.V, RK_BLOCK), need = 8L * a.S * (1 + nblocks), pairs = 8L * a.S * nblocks;
+  if (a.phase == 0)
+    DRN_CHECK_ARG(need <= 0x7fffffffL && a.ws_bytes >= need, "%s: the workspace holds %d bytes, %ld are needed (8 * S * (1 + blocks))", what,
+                  a.ws_bytes, need);
+  if (a.phase == 2)
+    DRN_CHECK_ARG(pairs <= 0x7fffffffL && a.cnt_bytes >= pairs, "%s: the counts hold %d bytes, %ld are needed (8 * S * blocks)", what,
+                  a.cnt_bytes, pairs);
   if (late) DRN_CHECK_ARG(a.S <= 65535, "%s: S = %d, more than 65535 sentences", what, a.S);
   else DRN_CHECK_ARG(cdiv(a.S, 16) <= 65535, "%s: S = %d, more than 65535 tiles of 16 sentences", what, a.S);
   return DRN_OK;
 }
 
-// the three launches with the operand Op.  SHAPE is a compile-time switch: an operand instantiates only the kernels it is launched on
+// the three launches with the operand Op -- of a phase, its one.  SHAPE is a compile-time switch: an operand instantiates only the
+// kernels it is launched on
 template <RkShape SHAPE, typename Op>
 static void rk_launch(const Op op, const RkArgs& a, hipStream_t stream) {
   typedef typename Op::Q Q;
   const Q* q = (const Q*)a.queries;
   const int stride = a.allow ? a.allow_stride : 0;
-  sl_key_t* tkey = (sl_key_t*)a.ws;
-  int2* cnt = (int2*)(tkey + a.S);
+  sl_key_t* tkey = a.phase ? a.keys : (sl_key_t*)a.ws;
+  int2* cnt = a.phase ? a.cnt : (int2*)(tkey + a.S);
+  const bool one = a.phase != 2, two = a.phase != 1;
   int nblocks = a.nblocks;
   if constexpr (SHAPE == RK_PLAIN) {
     nblocks = cdiv(a.V, RK_BLOCK);
-    rank_target_kernel<Op><<<cdiv(a.S, 16), 64, 0, stream>>>(op, q, a.targets, a.allow, stride, a.V, a.E, a.S, tkey);
-    rank_block_kernel<Op><<<dim3(nblocks, cdiv(a.S, 16)), 256, 0, stream>>>(op, q, a.allow, stride, a.V, a.E, a.S, nblocks, tkey, cnt);
+    if (one) rank_target_kernel<Op><<<cdiv(a.S, 16), 64, 0, stream>>>(op, q, a.targets, a.allow, stride, a.V, a.E, a.S, tkey);
+    if (two) rank_block_kernel<Op><<<dim3(nblocks, cdiv(a.S, 16)), 256, 0, stream>>>(op, q, a.allow, stride, a.V, a.E, a.S, nblocks, tkey, cnt);
   } else if constexpr (SHAPE == RK_RAGGED) {
-    rank_target_rows_kernel<Op><<<a.S, 256, 0, stream>>>(op, q, nullptr, a.offsets, a.targets, a.allow, stride, a.R, a.V, a.E, 1, tkey);
-    rank_segments_kernel<Op><<<dim3(nblocks, cdiv(a.S, 16)), 256, 0, stream>>>(op, q, a.offsets, a.blk_vid, a.allow, stride, a.R, a.V, a.E,
-                                                                                a.S, nblocks, tkey, cnt);
+    if (one) rank_target_rows_kernel<Op><<<a.S, 256, 0, stream>>>(op, q, nullptr, a.offsets, a.targets, a.allow, stride, a.R, a.V, a.E, 1, tkey);
+    if (two)
+      rank_segments_kernel<Op><<<dim3(nblocks, cdiv(a.S, 16)), 256, 0, stream>>>(op, q, a.offsets, a.blk_vid, a.allow, stride, a.R, a.V, a.E,
+                                                                                  a.S, nblocks, tkey, cnt);
   } else {
-    rank_target_rows_kernel<Op><<<a.S, 256, 0, stream>>>(op, q, a.lengths, a.offsets, a.targets, a.allow, stride, a.R, a.V, a.E, a.L, tkey);
-    rank_late_kernel<Op><<<dim3(nblocks, a.S), 256, 0, stream>>>(op, q, a.lengths, a.offsets, a.blk_vid, a.allow, stride, a.R, a.V, a.E, a.L,
-                                                                  nblocks, tkey, cnt);
+    if (one)
+      rank_target_rows_kernel<Op><<<a.S, 256, 0, stream>>>(op, q, a.lengths, a.offsets, a.targets, a.allow, stride, a.R, a.V, a.E, a.L, tkey);
+    if (two)
+      rank_late_kernel<Op><<<dim3(nblocks, a.S), 256, 0, stream>>>(op, q, a.lengths, a.offsets, a.blk_vid, a.allow, stride, a.R, a.V, a.E, a.L,
+                                                                    nblocks, tkey, cnt);
   }
-  rank_reduce_kernel<<<cdiv(a.S, 4), 256, 0, stream>>>(tkey, cnt, a.S, nblocks, a.rank, a.score, a.total);
+  if (a.phase == 0) rank_reduce_kernel<<<cdiv(a.S, 4), 256, 0, stream>>>(tkey, cnt, a.S, nblocks, a.rank, a.score, a.total);
 }
 
 template <RkShape SHAPE>
@@ -573,4 +589,46 @@ extern "C" int drn_shortlist_late_rank(const void* table, const uint8_t* scales,
   const RkArgs a = {RK_LATE, table, scales, queries, lengths, offsets, blk_vid, targets, allow, allow_stride, R, V, nblocks, E, S, L, dtype,
                     ws, ws_bytes, rank, score, total};
   return rk_run<RK_LATE>("drn_shortlist_late_rank", a, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The phases alone, for a corpus kept as several tables (retrieve_shard_rank.hip says why a shard's counting kernel gives the corpus's
+// count when it is handed a per-shard threshold in the place of tkey[s]).  phase 1: the target kernel of the matching entry above
+// writes keys [S] (cnt is not used and may be null); phase 2: its counting kernel reads keys [S] as THRESHOLDS and writes cnt [S][blocks]
+// pairs, cnt_bytes >= 8 S blocks (targets is not used and may be null).  One launch each; the kernels and their bits are the entries'.
+// In a phase the record's slots from ws on hold: no workspace and no results (the reduce does not run), the phase, keys, cnt, cnt_bytes.
+
+extern "C" int drn_shortlist_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* targets,
+                                        const int32_t* allow, int allow_stride, int V, int E, int S, int dtype, int phase, void* keys,
+                                        void* cnt, int cnt_bytes, void* stream) {
+  const char* what = "drn_shortlist_rank_phase";
+  drn_clear_status();
+  DRN_CHECK_ARG(phase == 1 || phase == 2, "%s: phase = %d is neither 1 (the target keys) nor 2 (the block counts)", what, phase);
+  const RkArgs a = {RK_PLAIN, table, scales, queries, nullptr, nullptr, nullptr, targets, allow, allow_stride, 0, V, 0, E, S, 1, dtype, nullptr,
+                    0, nullptr, nullptr, nullptr, phase, (sl_key_t*)keys, (int2*)cnt, cnt_bytes};
+  return rk_run<RK_PLAIN>(what, a, stream);
+}
+
+extern "C" int drn_shortlist_segments_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                                 const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride,
+                                                 int R, int V, int nblocks, int E, int S, int dtype, int phase, void* keys, void* cnt,
+                                                 int cnt_bytes, void* stream) {
+  const char* what = "drn_shortlist_segments_rank_phase";
+  drn_clear_status();
+  DRN_CHECK_ARG(phase == 1 || phase == 2, "%s: phase = %d is neither 1 (the target keys) nor 2 (the block counts)", what, phase);
+  const RkArgs a = {RK_RAGGED, table, scales, queries, nullptr, offsets, blk_vid, targets, allow, allow_stride, R, V, nblocks, E, S, 1, dtype,
+                    nullptr, 0, nullptr, nullptr, nullptr, phase, (sl_key_t*)keys, (int2*)cnt, cnt_bytes};
+  return rk_run<RK_RAGGED>(what, a, stream);
+}
+
+extern "C" int drn_shortlist_late_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths,
+                                             const int32_t* offsets, const int32_t* blk_vid, const int32_t* targets, const int32_t* allow,
+                                             int allow_stride, int R, int V, int nblocks, int E, int S, int L, int dtype, int phase,
+                                             void* keys, void* cnt, int cnt_bytes, void* stream) {
+  const char* what = "drn_shortlist_late_rank_phase";
+  drn_clear_status();
+  DRN_CHECK_ARG(phase == 1 || phase == 2, "%s: phase = %d is neither 1 (the target keys) nor 2 (the block counts)", what, phase);
+  const RkArgs a = {RK_LATE, table, scales, queries, lengths, offsets, blk_vid, targets, allow, allow_stride, R, V, nblocks, E, S, L, dtype,
+                    nullptr, 0, nullptr, nullptr, nullptr, phase, (sl_key_t*)keys, (int2*)cnt, cnt_bytes};
+  return rk_run<RK_LATE>(what, a, stream);
 }

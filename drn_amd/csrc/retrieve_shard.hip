@@ -1,6 +1,7 @@
 // A corpus kept as several tables (drn_amd/retrieve.py, ShardedShortlister): every shard ranks itself with its own entry, unchanged, and
 //   drn_shortlist_merge_lists   merges the K per-shard lists of each sentence into the list of the whole corpus, one launch;
 //   drn_allow_slices            cuts a packed allow mask over the whole corpus into the K shards' own packed masks, one launch.
+// (Rank and rerank over the shards -- local positions, counting thresholds, the sum of the shards' counts -- are retrieve_shard_rank.hip.)
 #include "common.h"
 #include "shortlist.h"
 #include "../../include/drn_hip.h"

@@ -1781,6 +1781,72 @@ def shortlist_late_rank(table, queries, lengths, offsets, blk_vid, targets, ws, 
     return rank, score, total
 
 
+def _rank_phase(what, table, queries, lengths, plan, phase, targets, keys, cnt, allow):
+    """What the three *_rank_phase wrappers share.  plan: () on a plain table, (offsets, blk_vid) on a ragged one; lengths: None unless
+    late.  phase 1: targets (S,) int32 -> keys (S,) int64 (cnt must be None); phase 2: keys (S,) int64, read as thresholds -> cnt, a
+    contiguous int64 tensor of at least S * blocks elements (targets must be None)."""
+    phase = int(phase)
+    if phase not in (1, 2):
+        raise _lib.DrnError("%s: phase = %d is neither 1 (the target keys) nor 2 (the block counts)" % (what, phase))
+    late = lengths is not None
+    if late:
+        if queries.dim() != 3 or not queries.is_contiguous() or not 1 <= queries.shape[1] <= _lib.LATE_MAX_TOKENS or queries.shape[0] < 1:
+            raise _lib.DrnError("%s: queries must be a contiguous (S, L, E) tensor with S >= 1 and 1 <= L <= %d, not %s"
+                                % (what, _lib.LATE_MAX_TOKENS, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), int(queries.shape[1])
+    else:
+        if queries.dim() != 2:
+            raise _lib.DrnError("%s: queries must be a contiguous (S, E) tensor, not %s" % (what, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), 1
+    tensors, tab, scl, R, E = _rank_table(what, table, queries.view(S * L, -1) if late else queries)
+    _need_gpu(*(tensors + (queries, keys) + tuple(plan) + tuple(t for t in (lengths, targets, cnt, allow) if t is not None)))
+    if late and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous()):
+        raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
+    V, nblocks = _rank_plan(what, *plan) if plan else (R, -(-R // _lib.SHORTLIST_BLOCK))
+    if keys.dtype != torch.int64 or tuple(keys.shape) != (S,) or not keys.is_contiguous():
+        raise _lib.DrnError("%s: keys must be a contiguous (%d,) torch.int64 tensor" % (what, S))
+    if phase == 1:
+        if cnt is not None or targets is None or targets.dtype != torch.int32 or tuple(targets.shape) != (S,) or not targets.is_contiguous():
+            raise _lib.DrnError("%s: phase 1 takes targets, a contiguous (%d,) torch.int32 tensor, and no cnt" % (what, S))
+        have = 0
+    else:
+        if targets is not None or cnt is None or cnt.dtype != torch.int64 or not cnt.is_contiguous() or cnt.numel() < S * nblocks:
+            raise _lib.DrnError("%s: phase 2 takes cnt, a contiguous torch.int64 tensor of at least %d elements (S * blocks), and no "
+                                "targets" % (what, S * nblocks))
+        have = int(min(cnt.numel() * 8, 0x7fffffff))
+    mask, stride = _allow_args(what, allow, V, S)
+    head = (tab, scl, _p(queries)) + ((_p(lengths),) if late else ()) + tuple(_p(t) for t in plan) + (_p(targets), mask, stride)
+    sizes = ((R, V, nblocks) if plan else (V,)) + (E, S) + ((L,) if late else ())
+    args = head + sizes + (dtype_code(queries), phase, _p(keys), _p(cnt), have)
+    # (the flop figure handed to the timer: the whole table in phase 2; phase 1 scores the targets' rows alone, which the host cannot count)
+    _timed(what, 2.0 * S * L * R * E if phase == 2 else 0.0, lambda: check(getattr(lib(), "drn_" + what)(*args, _stream()), "drn_" + what))
+    return keys if phase == 1 else cnt
+
+
+def shortlist_rank_phase(table, queries, phase, targets, keys, cnt, allow=None):
+    """ONE PHASE of shortlist_rank over a plain table (drn_shortlist_rank_phase), for a corpus kept as several tables: table, queries and
+    allow as there.  phase 1: targets (S,) int32 on the device -> keys (S,) int64, the 64-bit key of each sentence's target in THIS
+    table, 0 where it is no candidate (cnt = None).  phase 2: keys (S,) int64, read as THRESHOLDS in the place of the target keys ->
+    cnt, a contiguous int64 tensor of at least S * ceil(V / SHORTLIST_BLOCK) elements, each two int32 counts of a (sentence, block):
+    the candidates above the threshold, and the candidates (targets = None).  One launch (tag shortlist_rank_phase), the kernel and
+    the bits of shortlist_rank's launch of that number; nothing is read on the host."""
+    return _rank_phase("shortlist_rank_phase", table, queries, None, (), phase, targets, keys, cnt, allow)
+
+
+def shortlist_segments_rank_phase(table, queries, offsets, blk_vid, phase, targets, keys, cnt, allow=None):
+    """shortlist_rank_phase over a RAGGED table (drn_shortlist_segments_rank_phase): offsets (V + 1,) and blk_vid (nblocks + 1,) as in
+    shortlist_segments_rank; cnt holds at least S * nblocks elements.  One launch (tag shortlist_segments_rank_phase)."""
+    return _rank_phase("shortlist_segments_rank_phase", table, queries, None, (offsets, blk_vid), phase, targets, keys, cnt, allow)
+
+
+def shortlist_late_rank_phase(table, queries, lengths, offsets, blk_vid, phase, targets, keys, cnt, allow=None):
+    """shortlist_rank_phase by LATE INTERACTION (drn_shortlist_late_rank_phase): queries (S, L, E) and lengths (S,) as in
+    shortlist_late_rank, the rest as in shortlist_segments_rank_phase.  One launch (tag shortlist_late_rank_phase)."""
+    if lengths is None:
+        raise _lib.DrnError("shortlist_late_rank_phase: lengths must be a contiguous (S,) torch.int32 tensor")
+    return _rank_phase("shortlist_late_rank_phase", table, queries, lengths, (offsets, blk_vid), phase, targets, keys, cnt, allow)
+
+
 def shortlist_rerank_ws_keys(C, S, n):
     """The 8-byte keys of workspace drn_shortlist_rerank needs: S * ceil(C / RERANK_GROUP) * min(n, RERANK_GROUP)."""
     return int(S) * (-(-int(C) // _lib.RERANK_GROUP)) * min(int(n), _lib.RERANK_GROUP)
@@ -1889,6 +1955,80 @@ def allow_slices(words, bases, host_bases, out):
         raise _lib.DrnError("%s: out must be a contiguous (%d,) torch.int32 tensor (%d rows of %d words)" % (what, rows * total, rows, total))
     _timed(what, 0.0, lambda: check(lib().drn_allow_slices(_p(words), rows, V, _p(bases), K, total, _p(out), _stream()), "drn_allow_slices"))
     return out
+
+
+def shard_positions(positions, bases, out):
+    """Corpus positions -> every shard's local positions: positions (S,) or (S, C) int32 ON THE DEVICE (targets; candidate lists, C <=
+    RERANK_MAX_CANDIDATES), bases (K + 1,) int32 on the device -> out (K, S) / (K, S, C) int32, written in place, every element:
+    out[k] = positions - bases[k] where bases[k] <= positions < bases[k + 1], else -1 (drn_shard_positions;
+    drn_amd.retrieve.shard_positions_reference is the definition).  Slice [k] is what shard k's rank and rerank take.  One launch (tag
+    shard_positions); nothing is read on the host."""
+    what = "shard_positions"
+    _need_gpu(positions, bases, out)
+    if positions.dtype != torch.int32 or positions.dim() not in (1, 2) or not positions.is_contiguous() or positions.shape[0] < 1 \
+            or (positions.dim() == 2 and not 1 <= positions.shape[1] <= _lib.RERANK_MAX_CANDIDATES):
+        raise _lib.DrnError("%s: positions must be a contiguous torch.int32 tensor (S,) or (S, C) with S >= 1 and 1 <= C <= %d, not %s %s"
+                            % (what, _lib.RERANK_MAX_CANDIDATES, positions.dtype, tuple(positions.shape)))
+    if bases.dtype != torch.int32 or bases.dim() != 1 or not 2 <= bases.numel() <= _lib.SHARDS_MAX + 1 or not bases.is_contiguous():
+        raise _lib.DrnError("%s: bases must be a contiguous (K + 1,) torch.int32 tensor with 1 <= K <= %d" % (what, _lib.SHARDS_MAX))
+    K = int(bases.numel()) - 1
+    shape = (K,) + tuple(positions.shape)
+    if out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.DrnError("%s: out must be a contiguous %s torch.int32 tensor" % (what, shape))
+    S, C = int(positions.shape[0]), 1 if positions.dim() == 1 else int(positions.shape[1])
+    _timed(what, 0.0, lambda: check(lib().drn_shard_positions(_p(positions), _p(bases), K, S, C, _p(out), _stream()), "drn_shard_positions"))
+    return out
+
+
+def shortlist_sharded_rank_ws_keys(blocks, S):
+    """The int64 elements of the stacked workspace of a rank over K shards, from the shards' block counts (HOST integers): K * S keys,
+    K * S thresholds, then the K count regions of S * blocks[k] elements each."""
+    return int(S) * (2 * len(blocks) + sum(int(b) for b in blocks))
+
+
+def shortlist_rank_thresholds(keys, thresholds, key):
+    """The K shards' target keys -> their counting thresholds and the target's key: keys (K, S) int64 as phase 1 of the *_rank_phase
+    wrappers wrote them for the local targets of shard_positions (at most one per column is not 0) -> thresholds (K, S) int64 for phase
+    2 and key (S,) int64, written in place (drn_shortlist_rank_thresholds; drn_amd.retrieve.rank_thresholds_reference is the
+    definition).  One launch (tag shortlist_rank_thresholds)."""
+    what = "shortlist_rank_thresholds"
+    _need_gpu(keys, thresholds, key)
+    if keys.dtype != torch.int64 or keys.dim() != 2 or not 1 <= keys.shape[0] <= _lib.SHARDS_MAX or keys.shape[1] < 1 or not keys.is_contiguous():
+        raise _lib.DrnError("%s: keys must be a contiguous (K, S) torch.int64 tensor with 1 <= K <= %d and S >= 1, not %s %s"
+                            % (what, _lib.SHARDS_MAX, keys.dtype, tuple(keys.shape)))
+    K, S = (int(x) for x in keys.shape)
+    for name, t, shape in (("thresholds", thresholds, (K, S)), ("key", key, (S,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous %s torch.int64 tensor" % (what, name, shape))
+    _timed(what, 0.0, lambda: check(lib().drn_shortlist_rank_thresholds(_p(keys), K, S, _p(thresholds), _p(key), _stream()),
+                                    "drn_shortlist_rank_thresholds"))
+    return thresholds, key
+
+
+def shortlist_rank_reduce_shards(key, cnt, blk_off, blocks, rank, score, total):
+    """The K shards' block counts -> the corpus's TargetRank fields: key (S,) int64 from shortlist_rank_thresholds; cnt, a contiguous
+    int64 tensor holding the K regions back to back, region k (S, blocks of shard k) from element S * blk_off[k]; blk_off (K + 1,) int32
+    ON THE DEVICE, the running sums of the shards' blocks, and blocks = blk_off[K] as the host knows it -> rank, score, total (S,),
+    written in place (drn_shortlist_rank_reduce_shards): the sums over all blocks, rank -1 and score 0 where key == 0.  One launch (tag
+    shortlist_rank_reduce_shards); nothing is read on the host."""
+    what = "shortlist_rank_reduce_shards"
+    _need_gpu(key, cnt, blk_off, rank, score, total)
+    if key.dtype != torch.int64 or key.dim() != 1 or key.numel() < 1 or not key.is_contiguous():
+        raise _lib.DrnError("%s: key must be a contiguous (S,) torch.int64 tensor" % what)
+    S, blocks = int(key.numel()), int(blocks)
+    if blk_off.dtype != torch.int32 or blk_off.dim() != 1 or not 2 <= blk_off.numel() <= _lib.SHARDS_MAX + 1 or not blk_off.is_contiguous():
+        raise _lib.DrnError("%s: blk_off must be a contiguous (K + 1,) torch.int32 tensor with 1 <= K <= %d" % (what, _lib.SHARDS_MAX))
+    K = int(blk_off.numel()) - 1
+    if blocks < K or cnt.dtype != torch.int64 or not cnt.is_contiguous() or cnt.numel() < S * blocks:
+        raise _lib.DrnError("%s: cnt must be a contiguous torch.int64 tensor of at least %d elements (S * blocks), blocks = %d >= K = %d"
+                            % (what, S * max(blocks, K), blocks, K))
+    for name, t, dt in (("rank", rank, torch.int32), ("score", score, torch.float32), ("total", total, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous (%d,) %s tensor" % (what, name, S, dt))
+    _timed(what, 0.0, lambda: check(lib().drn_shortlist_rank_reduce_shards(
+        _p(key), _p(cnt), int(min(cnt.numel() * 8, 0x7fffffff)), _p(blk_off), K, S, blocks, _p(rank), _p(score), _p(total), _stream()),
+        "drn_shortlist_rank_reduce_shards"))
+    return rank, score, total
 
 
 def plan_candidates(cand, num_videos, Sc, Nc, pairs, steps, table):

@@ -47,7 +47,15 @@ ShardedShortlister keeps a corpus as SEVERAL Shortlisters -- appended without a 
 corpus positions bases[k] + position in shard k.  Each shard ranks itself with its own entry; drn_shortlist_merge_lists
 (csrc/retrieve_shard.hip) merges the per-shard lists under the one total order and drn_allow_slices cuts a mask over the corpus into
 the shards' own.  A score's bits do not depend on the table that holds the video and the best n of a set are among the best n of each
-part, so the answer is the single table's, bit for bit: merge_shortlists_reference and slice_allow_reference are the definitions."""
+part, so the answer is the single table's, bit for bit: merge_shortlists_reference and slice_allow_reference are the definitions.
+
+ShardedShortlister.rank / rank_late / rerank / rerank_late answer over the shards what the single table's methods answer over the
+concatenated rows, bit for bit, and need NO new definition of the answer: rank_reference, segment_rank_reference, late_rank_reference and
+the three *_rerank_reference functions over the concatenated rows are it.  drn_shard_positions turns corpus positions into each shard's
+local ones (shard_positions_reference).  A rank runs each shard's target kernel, turns the one key that is not 0 into a threshold per
+shard (rank_thresholds_reference, drn_shortlist_rank_thresholds: an equal score precedes the target in an earlier shard and follows it
+in a later one), runs each shard's counting kernel against its threshold and sums the counts (drn_shortlist_rank_reduce_shards).  A
+rerank is each shard's rerank of the candidates that fall inside it, merged by drn_shortlist_merge_lists."""
 import collections
 import numbers
 
@@ -139,7 +147,9 @@ def rank_reference(embeddings, queries, targets, allow=None):
     with t = targets[s], total[s] = the candidates of s; where 0 <= t < V and t is a candidate, rank[s] = the candidates u with
     score[s, u] > score[s, t], or score[s, u] == score[s, t] and u < t, and score[s] = t's score rounded to float32; otherwise
     rank[s] = -1 and score[s] = 0 (a value outside [0, V) is legal and means "no target").  So rank[s] = k >= 0 exactly when
-    shortlist_reference(..., n).ids[s, k] == t for every n > k.  -> TargetRank on the inputs' device."""
+    shortlist_reference(..., n).ids[s, k] == t for every n > k.  Over the concatenated (dequantised) rows of its shards this IS the
+    definition of ShardedShortlister.rank too; so are segment_rank_reference and late_rank_reference with the offsets of each shard
+    shifted by the running row count.  -> TargetRank on the inputs' device."""
     return _ranked(*_plain_scores(embeddings, queries, allow), targets)
 
 
@@ -186,7 +196,10 @@ def rerank_reference(embeddings, candidates, queries, n, allow=None):
     """THE DEFINITION of a reranked list on a table of one row per video, in float64 (usable on the CPU): shortlist_reference with
     allow replaced by candidates_mask(candidates, V) & allow.  Score, candidate-hood (finite score, listed, allowed) and the total
     order (score descending, then store position ascending) are shortlist_reference's: the order of the input list means nothing, and
-    ties fall by store position, not by place in the list.  n > C is legal: past the list ids = -1 and scores = 0.  -> Shortlist."""
+    ties fall by store position, not by place in the list.  n > C is legal: past the list ids = -1 and scores = 0.  Over the
+    concatenated (dequantised) rows of its shards, with CORPUS positions in candidates, this IS the definition of
+    ShardedShortlister.rerank too; so are segment_rerank_reference and late_rerank_reference with the offsets of each shard shifted
+    by the running row count.  -> Shortlist."""
     V, S = int(embeddings.shape[0]), int(queries.shape[0])
     return shortlist_reference(embeddings, queries, n, allow=_listed_and_allowed(candidates, S, V, allow, embeddings.device))
 
@@ -436,6 +449,63 @@ def merge_shortlists_reference(lists, bases, n):
     return SegmentShortlist(ids, scores, count, segs)
 
 
+def shard_positions_reference(positions, bases):
+    """THE DEFINITION of a shard's local positions, in plain torch (usable on the CPU): positions, an integer tensor (S,) or (S, C) of
+    CORPUS positions (targets; candidate lists), and bases, K + 1 integers, shard k holding the corpus positions bases[k] ..
+    bases[k + 1] - 1 -> int32 (K, S) / (K, S, C) on its device: out[k] = positions - bases[k] where bases[k] <= positions <
+    bases[k + 1], else -1.  Computed in 64 bits, without wrap-around: INT_MIN, INT_MAX, -1 and V land in no shard.  Slice [k] is what
+    shard k's rank and rerank take, where -1 means "no target" / "no candidate"."""
+    if not torch.is_tensor(positions) or positions.dim() not in (1, 2) or positions.is_floating_point() or positions.is_complex() \
+            or positions.dtype == torch.bool:
+        raise DrnError("shard_positions_reference: positions must be an integer tensor (S,) or (S, C)")
+    bases = [int(b) for b in bases]
+    if len(bases) < 2:
+        raise DrnError("shard_positions_reference: K + 1 bases with K >= 1, not %d" % len(bases))
+    p = positions.to(torch.int64)
+    return torch.stack([torch.where((p >= a) & (p < b), p - a, torch.full_like(p, -1)) for a, b in zip(bases[:-1], bases[1:])]).to(torch.int32)
+
+
+def rank_thresholds_reference(keys):
+    """THE DEFINITION of the per-shard counting thresholds of a rank over K shards, in numpy (usable on the CPU).  keys (K, S): each
+    shard's 64-bit key of sentence s's target at its LOCAL position -- (word of the score << 32) | ~position, 0 where the shard does
+    not hold a candidate target -- as integers that hold 64 bits: a numpy uint64 array, or a torch.int64 tensor holding the same bits;
+    at most one key per column is not 0 (refused otherwise).  -> (thresholds (K, S), key (S,)) of the input's kind.  With kt the shard
+    whose key tk is not 0 and tw = tk >> 32 (>= 1: a finite score's word is never 0): thresholds[k, s] = (tw << 32) - 1 for k < kt --
+    an equal score in an earlier shard lies at a lower corpus position, so it precedes: every key of word >= tw counts --, tk for
+    k == kt, (tw << 32) | 0xffffffff for k > kt -- an equal score in a later shard follows: only the words > tw count --, and
+    key[s] = tk.  Where every key of the column is 0, thresholds = all ones (nothing counts as above) and key[s] = 0.  The rank of
+    the target over the concatenated table is then the sum over the shards of their keys > thresholds[k, s]: rank_reference,
+    segment_rank_reference and late_rank_reference over the concatenated rows stay THE definition of the answer."""
+    tensor = torch.is_tensor(keys)
+    if tensor:
+        if keys.dtype != torch.int64 or keys.dim() != 2:
+            raise DrnError("rank_thresholds_reference: keys must be (K, S) torch.int64 (or a numpy uint64 array), not %s %s"
+                           % (keys.dtype, tuple(keys.shape)))
+        k = keys.detach().cpu().contiguous().numpy().view(np.uint64)
+    else:
+        k = np.ascontiguousarray(keys)
+        if k.dtype != np.uint64 or k.ndim != 2:
+            raise DrnError("rank_thresholds_reference: keys must be a (K, S) numpy uint64 array (or a torch.int64 tensor), not %s %s"
+                           % (k.dtype, k.shape))
+    K, S = k.shape
+    if K < 1:
+        raise DrnError("rank_thresholds_reference: K >= 1 rows of keys, not %d" % K)
+    nz = k != 0
+    if bool((nz.sum(axis=0) > 1).any()):
+        raise DrnError("rank_thresholds_reference: sentence %d has a target key in more than one shard" % int(np.argmax(nz.sum(axis=0) > 1)))
+    has, kt = nz.any(axis=0), nz.argmax(axis=0)
+    tk = k[kt, np.arange(S)]
+    top = (tk >> np.uint64(32)) << np.uint64(32)
+    at = np.arange(K)[:, None]
+    ones = np.uint64(0xffffffffffffffff)
+    thr = np.where(at < kt[None, :], (top - np.uint64(1))[None, :], np.where(at == kt[None, :], tk[None, :], (top | np.uint64(0xffffffff))[None, :]))
+    thr = np.where(has[None, :], thr, ones).astype(np.uint64)
+    key = np.where(has, tk, np.uint64(0)).astype(np.uint64)
+    if tensor:
+        return torch.from_numpy(thr.view(np.int64).copy()).to(keys.device), torch.from_numpy(key.view(np.int64).copy()).to(keys.device)
+    return thr, key
+
+
 def _allow_of(what, names, V, dev, keep, drop):
     """Shortlister.allow_of and ShardedShortlister.allow_of: HOST names or positions of a table of V videos -> a packed mask on dev."""
     if (keep is None) == (drop is None):
@@ -663,6 +733,11 @@ class Shortlister(object):
         if ws is None:
             ws = self._ws[key] = torch.empty(keys(), dtype=torch.int64, device=self._table().device)
         return ws
+
+    @property
+    def device(self):
+        """The device of the table (ShardedShortlister.device is the same accessor)."""
+        return self._table().device
 
     @property
     def dtype(self):
@@ -922,13 +997,18 @@ class Shortlister(object):
             raise DrnError("%s: the queries hold %d sentences, candidates has %d rows" % (what, Sq, S))
         return self._rerank(what, S, C, n, candidates, queries, lengths, out, allow)
 
-    def _check_rank(self, what, S, targets, out, allow):
-        """What rank() and rank_late() refuse about targets, out= and allow=, before the library is reached -> out, made where None."""
+    def _check_targets(self, what, S, targets):
+        """What every rank refuses about targets, before the library is reached."""
         dev = self._table().device
         if not torch.is_tensor(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (S,) or not targets.is_contiguous():
             raise DrnError("%s: targets must be a contiguous (%d,) torch.int32 tensor, the store position of each sentence's video" % (what, S))
         if not targets.is_cuda or targets.device != dev:
             raise DrnError("%s: targets must be on the table's device %s (they are never read on the host)" % (what, dev))
+
+    def _check_rank(self, what, S, targets, out, allow):
+        """What rank() and rank_late() refuse about targets, out= and allow=, before the library is reached -> out, made where None."""
+        dev = self._table().device
+        self._check_targets(what, S, targets)
         if out is not None:
             if len(out) != 3:
                 raise DrnError("%s: out must hold the three buffers of a TargetRank (rank, score, total), not %d" % (what, len(out)))
@@ -983,6 +1063,40 @@ class Shortlister(object):
         ops.shortlist_late_rank(self._operand(), queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
         return TargetRank(*out)
 
+    def _rank_keys(self, what, queries, lengths, targets, keys, allow=None):
+        """PHASE 1 of rank() (lengths=None) or rank_late() alone, for ShardedShortlister: each sentence's target key in THIS table ->
+        keys, a contiguous (S,) int64 tensor written in place (0 where the target is no candidate here).  The refusals are the public
+        methods', under the name `what`; one launch."""
+        self._check_rank_queries(what, queries, lengths)
+        self._check_targets(what, int(queries.shape[0]), targets)
+        return self._rank_phase(1, queries, lengths, targets, keys, None, allow)
+
+    def _rank_counts(self, what, queries, lengths, thresholds, cnt, allow=None):
+        """PHASE 2 of rank() (lengths=None) or rank_late() alone, for ShardedShortlister: the block counts against thresholds, a
+        contiguous (S,) int64 tensor read in the place of the target keys -> cnt, a contiguous int64 tensor of S * _nblocks() elements
+        written in place.  The refusals are the public methods', under the name `what`; one launch."""
+        self._check_rank_queries(what, queries, lengths)
+        return self._rank_phase(2, queries, lengths, None, thresholds, cnt, allow)
+
+    def _check_rank_queries(self, what, queries, lengths):
+        """rank()'s refusals about queries (lengths=None), rank_late()'s about queries and lengths -> S."""
+        if lengths is None:
+            return self._check_queries(what, queries)[0]
+        if self._seg is None:
+            _refuse_late(what, "rank")
+        return self._check_late(what, queries, lengths)[0]
+
+    def _rank_phase(self, phase, queries, lengths, targets, keys, cnt, allow):
+        """The one launch of _rank_keys / _rank_counts, by the table's shape."""
+        if allow is not None:
+            self._check_allow(allow, int(queries.shape[0]))
+        seg = self._seg
+        if seg is None:
+            return ops.shortlist_rank_phase(self._operand(), queries.contiguous(), phase, targets, keys, cnt, allow=allow)
+        if lengths is None:
+            return ops.shortlist_segments_rank_phase(self._operand(), queries.contiguous(), seg[0], seg[1], phase, targets, keys, cnt, allow=allow)
+        return ops.shortlist_late_rank_phase(self._operand(), queries, lengths, seg[0], seg[1], phase, targets, keys, cnt, allow=allow)
+
 
 class ShardedShortlister(object):
     """ShardedShortlister(shards): a corpus kept as 1 to SHARDS_MAX Shortlister objects, held by reference; the video at position i of
@@ -1001,12 +1115,20 @@ class ShardedShortlister(object):
     gives the corpus's list.  allow= takes a mask over the corpus, cut into the shards' own by one more launch (slice_allow_reference;
     drn_allow_slices).
 
-    Attributes a caller may rely on: shards; bases (a host list of K + 1 integers) and bases_device (the same as int32 on the
-    device); names (the concatenation when every shard has names, else None); E, dtype, nbytes (the sum over the shards).
+    rank() / rank_late() and rerank() / rerank_late() answer likewise, field for field and bit for bit, what ONE Shortlister over the
+    concatenated rows answers, with positions and masks over the CORPUS.  A rank: drn_shard_positions gives every shard its local
+    target (-1 where it lies elsewhere), each shard's own target kernel makes its key, ONE launch turns the one key that is not 0
+    into a counting threshold per shard -- an equal score precedes the target in an earlier shard and follows it in a later one
+    (rank_thresholds_reference) --, each shard's own counting kernel counts against its threshold, and ONE launch sums: 2 K + 3
+    launches, one more under a mask.  A rerank: drn_shard_positions on the candidate lists, each shard's own rerank of the
+    candidates that fall inside it, and the merge of shortlist(): a shard's rerank is its filtered shortlist.
 
-    NOT here: rank / rerank over shards (a rank needs the target's key counted in the other shards); shards on several devices or
-    ranks (the stacked (K, S, n) lists are laid out so that lists gathered from other GPUs merge through the same entry); shards on
-    parallel streams (they run one after the other on the current stream); compacting shards; n above SHORTLIST_MAX."""
+    Attributes a caller may rely on: shards; bases (a host list of K + 1 integers) and bases_device (the same as int32 on the
+    device); names (the concatenation when every shard has names, else None); device, E, dtype, nbytes (the sum over the shards).
+
+    NOT here: one grouped launch over all shards in the place of K; the winning segment (rows) from a rerank; shards on several
+    devices or ranks (the stacked (K, S, n) lists are laid out so that lists gathered from other GPUs merge through the same entry);
+    shards on parallel streams (they run one after the other on the current stream); compacting shards; n above SHORTLIST_MAX."""
 
     def __init__(self, shards):
         try:
@@ -1046,12 +1168,16 @@ class ShardedShortlister(object):
             self.names = None if shard.names is None else self.names + list(shard.names)
 
     def _placed(self):
-        """After the shards changed: the buffers kept for the old K are dropped and bases goes to the device (one upload from pinned
-        memory, no synchronise)."""
+        """After the shards changed: the buffers kept for the old K are dropped, and bases and blk_off go to the device (uploads from
+        pinned memory, no synchronise)."""
         self._bufs = {}
-        bases = torch.tensor(self.bases, dtype=torch.int32)
+        self.blk_off = [0]                       # the running sums of the shards' counting blocks: where each count region starts
+        for shard in self.shards:
+            self.blk_off.append(self.blk_off[-1] + shard._nblocks())
+        bases, blk_off = torch.tensor(self.bases, dtype=torch.int32), torch.tensor(self.blk_off, dtype=torch.int32)
         dev = self.device
         self.bases_device = bases if dev.type != "cuda" else bases.pin_memory().to(dev, non_blocking=True)
+        self.blk_off_device = blk_off if dev.type != "cuda" else blk_off.pin_memory().to(dev, non_blocking=True)
 
     def append(self, shard):
         """One more shard at the end of the corpus -- the same checks as the constructor, before anything changes -- at the positions
@@ -1169,3 +1295,106 @@ class ShardedShortlister(object):
             shard.shortlist_late(queries, lengths, n, out=tuple(t[k] for t in lists[:3]), allow=piece)
         ops.shortlist_merge_lists(lists[0], lists[1], lists[2], None, self.bases_device, n, out[0], out[1], out[2])
         return Shortlist(*out)
+
+    def _rank(self, what, queries, lengths, targets, out, allow):
+        """What rank (lengths=None) and rank_late share: the refusals of the single table's method, then 2 K + 3 launches."""
+        first = self.shards[0]
+        if lengths is not None and first._seg is None:
+            _refuse_late(what, "rank", whose="these tables have")
+        S = first._check_rank_queries(what, queries, lengths)
+        out = first._check_rank(what, S, targets, out, None)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        if lengths is None:
+            queries = queries.contiguous()
+        K, blocks = len(self.shards), [b - a for a, b in zip(self.blk_off[:-1], self.blk_off[1:])]
+        bufs = self._bufs.get(("rank", K, S))
+        if bufs is None:
+            dev = self.device
+            bufs = self._bufs[("rank", K, S)] = (torch.empty((K, S), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.int64, device=dev),
+                                                 torch.empty(ops.shortlist_sharded_rank_ws_keys(blocks, S), dtype=torch.int64, device=dev))
+        local, key, ws = bufs
+        keys, thresholds, cnt = ws[:K * S].view(K, S), ws[K * S:2 * K * S].view(K, S), ws[2 * K * S:]
+        ops.shard_positions(targets, self.bases_device, local)
+        pieces = self._slices(allow)
+        for k, (shard, piece) in enumerate(zip(self.shards, pieces)):
+            shard._rank_keys(what, queries, lengths, local[k], keys[k], piece)
+        ops.shortlist_rank_thresholds(keys, thresholds, key)
+        for k, (shard, piece) in enumerate(zip(self.shards, pieces)):
+            shard._rank_counts(what, queries, lengths, thresholds[k], cnt[S * self.blk_off[k]:S * self.blk_off[k + 1]], piece)
+        ops.shortlist_rank_reduce_shards(key, cnt, self.blk_off_device, self.blk_off[-1], *out)
+        return TargetRank(*out)
+
+    def rank(self, queries, targets, out=None, allow=None):
+        """Shortlister.rank over the corpus -> TargetRank: targets are CORPUS positions (a value outside [0, V) means "no target"),
+        allow a packed mask over the whole corpus; the arguments, the refusals, out= and every field bit for bit what one Shortlister
+        over the concatenated rows returns (rank_reference over them -- segment_rank_reference on ragged shards -- is the
+        definition).  The launches, in order: drn_shard_positions; with allow=, drn_allow_slices; K target-key launches, each shard's
+        own; one thresholds launch; K counting launches, each shard's own; one reduce.  All on the current stream, without a host
+        synchronisation, and capturable in a graph once the shape is warmed (the buffers are kept per (K, S)), where queries, targets
+        and the mask's contents may change in place between replays."""
+        return self._rank("Shortlister.rank", queries, None, targets, out, allow)
+
+    def rank_late(self, queries, lengths, targets, out=None, allow=None):
+        """Shortlister.rank_late over the corpus (ragged shards) -> TargetRank, as rank(): every field bit for bit the single table's
+        (late_rank_reference over the concatenated rows is the definition); queries, lengths, targets and the mask's contents may
+        change in place between replays of a captured graph.  Shards without offsets are refused as in shortlist_late()."""
+        what = "Shortlister.rank_late"
+        if not torch.is_tensor(lengths):
+            raise DrnError("%s: lengths must be a contiguous torch.int32 tensor on the device, the live tokens of each sentence" % what)
+        return self._rank(what, queries, lengths, targets, out, allow)
+
+    def _rerank(self, what, candidates, queries, lengths, n, out, allow):
+        """What rerank (lengths=None) and rerank_late share: the refusals of the single table's method, then K + 2 launch groups."""
+        first = self.shards[0]
+        late = lengths is not None
+        if late and first._seg is None:
+            _refuse_late(what, "rerank", whose="these tables have")
+        S, C, n = first._check_candidates(what, candidates, n)
+        if late:
+            Sq, _, _ = first._check_late(what, queries, lengths)
+            if Sq != S:
+                raise DrnError("%s: the queries hold %d sentences, candidates has %d rows" % (what, Sq, S))
+        else:
+            first._check_queries(what, queries, S)
+        if out is not None:
+            _check_list_out(what, out, S, n)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        if out is None:
+            out = _list_buffers(self.device, S, n)
+        K = len(self.shards)
+        local = self._bufs.get(("positions", K, S, C))
+        if local is None:
+            local = self._bufs[("positions", K, S, C)] = torch.empty((K, S, C), dtype=torch.int32, device=self.device)
+        ops.shard_positions(candidates, self.bases_device, local)
+        lists = self._lists(S, n)[:3]
+        for k, (shard, piece) in enumerate(zip(self.shards, self._slices(allow))):
+            into = tuple(t[k] for t in lists)
+            if late:
+                shard.rerank_late(local[k], queries, lengths, n, out=into, allow=piece)
+            else:
+                shard.rerank(local[k], queries, n, out=into, allow=piece)
+        ops.shortlist_merge_lists(lists[0], lists[1], lists[2], None, self.bases_device, n, out[0], out[1], out[2])
+        return Shortlist(*out)
+
+    def rerank(self, candidates, queries, n=None, out=None, allow=None):
+        """Shortlister.rerank over the corpus -> Shortlist with CORPUS positions: candidates (S, C) hold corpus positions -- the ids
+        of any shortlist over the same corpus, sharded or not, as they are --, allow is a packed mask over the whole corpus; the
+        arguments, the refusals, the padding and out= of the single table's method, and every field bit for bit what one Shortlister
+        over the concatenated rows returns (rerank_reference over them -- segment_rerank_reference on ragged shards -- is the
+        definition).  The launches, in order: drn_shard_positions into a (K, S, C) buffer (a candidate that lies in another shard
+        becomes -1, which means nothing); with allow=, drn_allow_slices; each shard's own rerank, unchanged, on slice [k] into slice
+        [k] of the stacked lists; drn_shortlist_merge_lists.  A shard's rerank of the candidates inside it is its filtered shortlist,
+        so the merge is shortlist()'s.  All on the current stream, without a host synchronisation, capturable once warmed (buffers
+        per (K, S, C) and (K, S, n)), where candidates, queries and the mask's contents may change in place between replays."""
+        return self._rerank("Shortlister.rerank", candidates, queries, None, n, out, allow)
+
+    def rerank_late(self, candidates, queries, lengths, n=None, out=None, allow=None):
+        """Shortlister.rerank_late over the corpus (ragged shards) -> Shortlist with CORPUS positions, as rerank(): every field bit
+        for bit the single table's (late_rerank_reference over the concatenated rows is the definition).  Shards without offsets are
+        refused as in shortlist_late()."""
+        what = "Shortlister.rerank_late"
+        if not torch.is_tensor(lengths):
+            raise DrnError("%s: lengths must be a contiguous torch.int32 tensor on the device, the live tokens of each sentence" % what)
+        return self._rerank(what, candidates, queries, lengths, n, out, allow)

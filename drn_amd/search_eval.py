@@ -30,7 +30,8 @@ seen."""
 
 @torch.no_grad()
 def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=False, allow=None):
-    """How deep must a shortlist be?  batches: an iterable of (names, queries) -- names[q] the video sentence q is annotated in, queries
+    """How deep must a shortlist be?  shortlister: a Shortlister, or a ShardedShortlister (names and targets are then over the corpus).
+    batches: an iterable of (names, queries) -- names[q] the video sentence q is annotated in, queries
     (S, E) what shortlister.rank takes -- or, with late=True, (names, queries, lengths) for shortlister.rank_late; the embeddings come
     from the CALLER's encoder (this project has none).  Every batch's names are resolved through shortlister.names on the host before
     anything of that batch is launched (an unknown name raises), the positions go up through one pinned non-blocking copy, and ONE
@@ -43,7 +44,7 @@ def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=Fals
     if shortlister.names is None:
         raise DrnError("evaluate_shortlist: the shortlister has no names to resolve the annotated videos through")
     where = {name: v for v, name in enumerate(shortlister.names)}
-    dev, ranks = shortlister._table().device, []
+    dev, ranks = shortlister.device, []
     for batch in batches:
         names = batch[0]
         ids = []
@@ -62,8 +63,8 @@ def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=Fals
 
 @torch.no_grad()
 def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=False, allow=None):
-    """How deep must the COARSE stage of a cascade be?  coarse and fine: two Shortlisters over the same store positions
-    (coarse.names == fine.names, refused otherwise) -- a cheap table, pooled or quantised, and the table the second stage reranks.
+    """How deep must the COARSE stage of a cascade be?  coarse and fine: two Shortlisters over the same store positions -- either
+    may be a ShardedShortlister, whose names and positions are the corpus's -- (coarse.names == fine.names, refused otherwise) -- a cheap table, pooled or quantised, and the table the second stage reranks.
     batches: an iterable of (names, coarse_queries, fine_queries) -- names[q] the video sentence q is annotated in -- or, with
     late=True, (names, coarse_queries, fine_queries, lengths) for fine.rerank_late; the embeddings come from the CALLER's encoders.
     Per batch: coarse.shortlist(coarse_queries, depth).ids, then fine.rerank / rerank_late(ids, ..., n=depth), and the target's rank
@@ -80,7 +81,7 @@ def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=Fals
     if not 1 <= depth <= SHORTLIST_MAX:
         raise DrnError("evaluate_cascade: depth = %d outside [1, %d]" % (depth, SHORTLIST_MAX))
     where = {name: v for v, name in enumerate(fine.names)}
-    dev, ranks = fine._table().device, []
+    dev, ranks = fine.device, []
     for batch in batches:
         ids = []
         for name in batch[0]:

@@ -757,6 +757,22 @@ int drn_shortlist_late_rank(const void* table, const uint8_t* scales, const void
                             const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride, int R, int V,
                             int nblocks, int E, int S, int L, int dtype, void* ws, int ws_bytes, int32_t* rank, float* score,
                             int32_t* total, void* stream);
+/* The rank entries OPENED INTO THEIR PHASES, for a corpus kept as several tables (below): the arguments of the matching entry above up
+ * to dtype, then phase, keys, cnt, cnt_bytes.  phase 1 runs the entry's first launch alone: keys [S] = the 64-bit key of (s, targets[s])
+ * in THIS table, 0 where the target is no candidate (cnt is not used and may be NULL).  phase 2 runs its second launch alone, reading
+ * keys [S] as THRESHOLDS in the place of the target keys: cnt [S][blocks] pairs of int32 -- the candidates of the block whose key is
+ * above keys[s], and its candidates -- blocks as in the entry's ws, cnt_bytes >= 8 * S * blocks (targets is not used and may be NULL).
+ * keys and cnt are 8-byte aligned.  Any other phase is refused.  One launch; the kernels, and so every bit, are the entries' own. */
+int drn_shortlist_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* targets, const int32_t* allow,
+                             int allow_stride, int V, int E, int S, int dtype, int phase, void* keys, void* cnt, int cnt_bytes,
+                             void* stream);
+int drn_shortlist_segments_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                      const int32_t* blk_vid, const int32_t* targets, const int32_t* allow, int allow_stride, int R, int V,
+                                      int nblocks, int E, int S, int dtype, int phase, void* keys, void* cnt, int cnt_bytes, void* stream);
+int drn_shortlist_late_rank_phase(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths,
+                                  const int32_t* offsets, const int32_t* blk_vid, const int32_t* targets, const int32_t* allow,
+                                  int allow_stride, int R, int V, int nblocks, int E, int S, int L, int dtype, int phase, void* keys,
+                                  void* cnt, int cnt_bytes, void* stream);
 /* RERANK A CANDIDATE LIST (drn_amd/csrc/retrieve_rerank.hip): candidates [S][C] int32 on the device, never read on the host, row s =
  * sentence s's SET of store positions: an entry outside [0, V) is no candidate (the -1 padding of a shortlist is one), and of a position
  * repeated in a row the first occurrence counts, across the whole row.  Only the listed (sentence, video) pairs are scored -- the rows
@@ -807,6 +823,26 @@ int drn_shortlist_merge_lists(const int32_t* in_ids, const float* in_scores, con
  * words a row `out` holds, computed by the caller from its host copy of bases; when the device's bases do not come to it nothing is
  * written.  bases as in drn_shortlist_merge_lists, not read on the host.  One launch, nothing read back. */
 int drn_allow_slices(const int32_t* words, int rows, int V, const int32_t* bases, int K, int total_words, int32_t* out, void* stream);
+/* RANK AND RERANK OVER THE K TABLES (drn_amd/csrc/retrieve_shard_rank.hip), every field bit for bit the single table's.
+ * drn_shard_positions: positions [S][C] int32 on the device, corpus positions (targets: C = 1; candidate lists: C <=
+ * DRN_RERANK_MAX_CANDIDATES) -> out [K][S][C]: out[k] = positions - bases[k] where bases[k] <= positions < bases[k + 1], else -1,
+ * compared and subtracted in 64 bits (INT_MIN and INT_MAX land in no shard); every value read from bases is clamped at 0.  Slice [k] is
+ * a legal targets / candidates argument of shard k's entries.  A rerank is then each shard's drn_shortlist_rerank on its slice and
+ * drn_shortlist_merge_lists. */
+int drn_shard_positions(const int32_t* positions, const int32_t* bases, int K, int S, int C, int32_t* out, void* stream);
+/* keys [K][S], the target keys phase 1 of the *_rank_phase entries wrote in each shard for the local targets of drn_shard_positions
+ * (at most one per column is not 0) -> thresholds [K][S] for phase 2 and key [S].  With kt the LOWEST shard whose key tk is not 0 and
+ * tw = tk >> 32: thresholds[k][s] = (tw << 32) - 1 for k < kt (an equal score there lies at a lower corpus position and precedes), tk
+ * for k == kt, (tw << 32) | 0xffffffff for k > kt (an equal score there follows), and key[s] = tk; where every key is 0 the
+ * thresholds are all ones and key[s] = 0.  All 8-byte aligned.  One launch, one wavefront per sentence. */
+int drn_shortlist_rank_thresholds(const void* keys, int K, int S, void* thresholds, void* key, void* stream);
+/* key [S] and the K shards' phase-2 counts back to back in cnt -- region k is [S][blk_off[k + 1] - blk_off[k]] pairs from pair
+ * S * blk_off[k]; blk_off [K + 1] int32 on the device, the running sums of the shards' blocks from 0, blocks = blk_off[K] as the host
+ * knows it (every value read from blk_off is clamped into [0, blocks]), cnt_bytes >= 8 * S * blocks -> rank, score, total [S] as in
+ * drn_shortlist_rank: the sums over all blocks, rank = -1 and score = 0 where key[s] == 0, else score = the key's.  One launch, one
+ * wavefront per sentence.  All three: no atomics, no workspace beyond what is passed, nothing read on the host. */
+int drn_shortlist_rank_reduce_shards(const void* key, const void* cnt, int cnt_bytes, const int32_t* blk_off, int K, int S, int blocks,
+                                     int32_t* rank, float* score, int32_t* total, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

@@ -125,7 +125,13 @@
            alone; one mixed object (half FP8, half bf16) and shortlist_late at 16 tokens on K = 4, each beside its single table.  One
            condition is derived, not measured, and reported HOLDS / MISSED shape by shape: (G1) adding 1,024 rows by append + shortlist
            takes less than torch.cat + Shortlister + shortlist on the same tensors by more than the latter's max - min.  Random
-           embeddings: nothing here says anything about recall."""
+           embeddings: nothing here says anything about recall.
+
+  --sharded-rank   instead of the above -> profiles/search_sharded_rank_bench.json: ShardedShortlister.rank, rerank (C = 128, n = 16) and --
+           on the ragged layout -- rank_late (16 tokens) on the same two layouts and K = 1 / 4 / 16 equal shards, S in {1, 8, 64}, by the
+           protocol of --sharded-shortlist, beside the single Shortlister over the same rows (every field asserted equal before timing);
+           and append + rank beside torch.cat + Shortlister + rank on the same tensors, the gain judged against the latter's own
+           max - min.  No time is required of the sharded calls (2 K + 3 launches against 3): the ratios are what is reported."""
 import argparse
 import json
 import os
@@ -2119,13 +2125,140 @@ def main_sharded_shortlist(args):
     print("wrote", out)
 
 
+def bench_sharded_rank(name, lens, emb, single, sharded, S, rounds):
+    """ShardedShortlister.rank, rerank (C = 128, n = 16) and -- on the ragged layout -- rank_late (16 tokens) at K = 1 / 4 / 16 equal
+    shards beside the single Shortlister over the same rows (the parent's code, unchanged); every field asserted equal to the single
+    table's before timing."""
+    g = torch.Generator(device="cuda:0").manual_seed(11 * S)
+    V, ragged = len(lens), max(lens) > 1
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    targets = torch.randint(0, V, (S,), generator=g, device="cuda:0").to(torch.int32)
+    cands = torch.randint(0, V, (S, 128), generator=g, device="cuda:0").to(torch.int32)
+    calls = {"rank": lambda o, out=None: o.rank(q, targets, out=out), "rerank": lambda o, out=None: o.rerank(cands, q, 16, out=out)}
+    if ragged:
+        tok = torch.randn(S, 16, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+        lengths = torch.full((S,), 16, dtype=torch.int32, device="cuda:0")
+        calls["rank_late"] = lambda o, out=None: o.rank_late(tok, lengths, targets, out=out)
+    row = {"layout": name, "R": int(emb.shape[0]), "V": V, "E": 512, "S": S, "dtype": "bf16", "C": 128, "n": 16, "L_late": 16, "methods": {}}
+    for method, call in calls.items():
+        out_single = call(single)
+        variants = {"single": lambda call=call, out=out_single: call(single, out)}
+        for K, sh in sharded.items():
+            out = call(sh)
+            same_fields(out, out_single, (name, method, K, S))
+            variants["sharded_K%d" % K] = lambda call=call, sh=sh, out=out: call(sh, out)
+        times, reps = interleaved_windows(variants, rounds)
+        base = times["single"]
+        row["methods"][method] = {"launches_per_window": reps, "single_us": spread(base), "shards": [
+            {"K": K, "sharded_us": spread(times["sharded_K%d" % K]),
+             "sharded_over_single": statistics.median(times["sharded_K%d" % K]) / statistics.median(base),
+             "sharded_against_single": verdict(times["sharded_K%d" % K], base)} for K in sharded]}
+    row["note"] = ("launch-inclusive: a sharded rank is 2 K + 3 launches on one stream against the single table's 3, a sharded rerank "
+                   "2 K + 2 against 2")
+    return row
+
+
+def bench_rank_growth(name, lens, emb, new_rows, new_lens, S, rounds, iters=10):
+    """Two ways to add GROWTH_ROWS rows to the resident table and rank once: sharded.append(Shortlister(new_rows)) + rank beside torch.cat
+    + Shortlister(...) + rank on the same tensors.  Host clock from before the first call to after a device synchronise; the two take
+    turns inside every round; a round is the mean of `iters` runs."""
+    import numpy as np
+    from drn_amd import ShardedShortlister, Shortlister
+    ragged = max(lens) > 1
+    off, new_off = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(new_lens)])
+    both_off = np.concatenate([off, off[-1] + new_off[1:]])
+    make = (lambda rows, o: Shortlister(rows, offsets=o)) if ragged else (lambda rows, o: Shortlister(rows))
+    base = make(emb, off)
+    g = torch.Generator(device="cuda:0").manual_seed(13 * S)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    targets = torch.randint(0, len(lens) + len(new_lens), (S,), generator=g, device="cuda:0").to(torch.int32)
+
+    def append_way():
+        sh = ShardedShortlister([base])                      # (the resident object: not timed)
+        sh.rank(q, targets)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = sh.append(make(new_rows, new_off)).rank(q, targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6, got
+
+    def rebuild_way():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = make(torch.cat([emb, new_rows]), both_off).rank(q, targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6, got
+    same_fields(append_way()[1], rebuild_way()[1], (name, "growth", S))
+    a, b = [], []
+    for _ in range(rounds):
+        a.append(statistics.mean(append_way()[0] for _ in range(iters)))
+        b.append(statistics.mean(rebuild_way()[0] for _ in range(iters)))
+    gain = statistics.median(b) - statistics.median(a)
+    return {"layout": name, "S": S, "resident_rows": int(emb.shape[0]), "new_rows": int(new_rows.shape[0]), "runs_per_round": iters,
+            "append_plus_rank_us": spread(a), "cat_plus_rebuild_plus_rank_us": spread(b), "append_over_rebuild": statistics.median(a) / statistics.median(b),
+            "gain": {"rebuild_minus_append_us": gain, "rebuild_max_minus_min_us": max(b) - min(b), "beyond_the_baselines_spread": gain > max(b) - min(b)}}
+
+
+def main_sharded_rank(args):
+    from drn_amd import ShardedShortlister, Shortlister
+    import numpy as np
+    out = args.out or os.path.join(ROOT, "profiles", "search_sharded_rank_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the tables resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call; growth: "
+                               "host clock from before the first call to after a device synchronise, a round = the mean of 10 runs",
+                      "baselines": "single: ONE Shortlister over the same rows, the parent's code unchanged, in the same process, every field "
+                                   "asserted equal before timing.  A difference inside the baseline's own max - min is NO DIFFERENCE",
+                      "what_this_does_not_say": "no time is required of the sharded calls: 2 K + 3 launches stand against 3.  Random embeddings: "
+                                                "nothing here says anything about recall; bf16 queries only; equal shards only (a small new "
+                                                "shard beside a large resident one in growth alone); no mask; shards run one after the other "
+                                                "on one stream; no kernel-only times (no profiler run); K = 64 and FP8 shards are not "
+                                                "measured"},
+           "sharded_rank": [], "growth": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    new_rows = torch.randn(GROWTH_ROWS, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+
+    def save():
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    for name, lens in SEGMENT_LAYOUTS[:2]:
+        off = np.concatenate([[0], np.cumsum(lens)])
+        single = Shortlister(emb) if max(lens) == 1 else Shortlister(emb, offsets=off)
+        sharded = {K: ShardedShortlister(equal_shards(emb, lens, K)) for K in SHARD_COUNTS}
+        for S in (1, 8, 64):
+            row = bench_sharded_rank(name, lens, emb, single, sharded, S, args.rounds)
+            res["sharded_rank"].append(row)
+            print(json.dumps({"sharded_rank": row}), flush=True)
+            for method, m in row["methods"].items():
+                for k in m["shards"]:
+                    print("%s %s S = %d K = %d: sharded / single = %.3f (%s), %.1f against %.1f us" % (
+                        name, method, S, k["K"], k["sharded_over_single"], k["sharded_against_single"], k["sharded_us"]["median"],
+                        m["single_us"]["median"]), flush=True)
+            save()
+        del sharded
+        for S in (1, 8, 64):
+            new_lens = [lens[0]] * (GROWTH_ROWS // lens[0])
+            row = bench_rank_growth(name, lens, emb, new_rows, new_lens, S, args.rounds)
+            res["growth"].append(row)
+            print(json.dumps({"growth": row}), flush=True)
+            print("growth %s S = %d: append / rebuild = %.3f (%s the rebuild's own spread)" % (
+                name, S, row["append_over_rebuild"], "BEYOND" if row["gain"]["beyond_the_baselines_spread"] else "INSIDE"), flush=True)
+            save()
+    save()
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
                                             "search_q8_bench.json with --quantized, search_q8_shortlist_bench.json with --quantized-shortlist, "
                                             "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
                                             "--late-shortlist, search_rank_bench.json with --rank, search_rerank_bench.json with --rerank, "
-                                            "search_sharded_shortlist_bench.json with --sharded-shortlist)")
+                                            "search_sharded_shortlist_bench.json with --sharded-shortlist, search_sharded_rank_bench.json with "
+                                            "--sharded-rank)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -2152,9 +2285,13 @@ def main():
     ap.add_argument("--sharded-shortlist", action="store_true", help="measure ShardedShortlister.shortlist on 1 / 4 / 16 equal shards beside the "
                                                                      "single table, the merge launch alone, a mixed FP8 / bf16 object, "
                                                                      "shortlist_late, and append beside torch.cat + rebuild")
+    ap.add_argument("--sharded-rank", action="store_true", help="measure ShardedShortlister.rank, rank_late and rerank on 1 / 4 / 16 equal shards "
+                                                                "beside the single table, and append + rank beside torch.cat + rebuild + rank")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.sharded_rank:
+        return main_sharded_rank(args)
     if args.sharded_shortlist:
         return main_sharded_shortlist(args)
     if args.rerank:
