@@ -219,6 +219,9 @@ SIGNATURES = {
     "drn_shard_positions": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "drn_shortlist_rank_thresholds": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_rank_reduce_shards": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_compact_plan": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_compact_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                         c_void_p, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

@@ -1980,6 +1980,102 @@ def shard_positions(positions, bases, out):
     return out
 
 
+def compact_plan(keep, offsets, k, carry, positions, new_offsets=None):
+    """Shard k's step of a compaction's plan: keep, the shard's own piece of the packed mask (allow_words(V) int32 words, as
+    allow_slices cuts it) or None for "every video kept"; offsets (V + 1,) int32 of a ragged shard or None; carry (K + 1, 2) int32,
+    (videos kept, rows kept) before each shard -- row k is read (row 0 is written, zeros, by k = 0) and row k + 1 written;
+    positions (V,) int32, the shard's slice of the corpus's map, written in place, every element: the new position, -1 where
+    dropped; new_offsets, given exactly when offsets is: a 1-D int32 buffer that gets the rows kept before every kept video at its
+    new position and is closed after every shard (drn_compact_plan; drn_amd.retrieve.compact_reference is the definition).  The K
+    launches go in stream order, k = 0 first.  One launch (tag compact_plan), one workgroup; nothing is read on the host."""
+    what = "compact_plan"
+    _need_gpu(keep, offsets, carry, positions, new_offsets)
+    if positions.dtype != torch.int32 or positions.dim() != 1 or positions.numel() < 1 or not positions.is_contiguous():
+        raise _lib.DrnError("%s: positions must be a contiguous (V,) torch.int32 tensor with V >= 1" % what)
+    V = int(positions.numel())
+    if carry.dtype != torch.int32 or carry.dim() != 2 or carry.shape[1] != 2 or not 2 <= carry.shape[0] <= _lib.SHARDS_MAX + 1 \
+            or not carry.is_contiguous():
+        raise _lib.DrnError("%s: carry must be a contiguous (K + 1, 2) torch.int32 tensor with 1 <= K <= %d" % (what, _lib.SHARDS_MAX))
+    K, k = int(carry.shape[0]) - 1, int(k)
+    if not 0 <= k < K:
+        raise _lib.DrnError("%s: shard k = %d outside [0, %d)" % (what, k, K))
+    if keep is not None and (keep.dtype != torch.int32 or tuple(keep.shape) != (allow_words(V),) or not keep.is_contiguous()):
+        raise _lib.DrnError("%s: keep must be a contiguous (%d,) torch.int32 tensor, the shard's piece of the packed mask" % (what, allow_words(V)))
+    if (offsets is None) != (new_offsets is None):
+        raise _lib.DrnError("%s: offsets and new_offsets must both be given (a ragged shard) or neither" % what)
+    cap = 0
+    if offsets is not None:
+        if offsets.dtype != torch.int32 or tuple(offsets.shape) != (V + 1,) or not offsets.is_contiguous():
+            raise _lib.DrnError("%s: offsets must be a contiguous (%d,) torch.int32 tensor" % (what, V + 1))
+        if new_offsets.dtype != torch.int32 or new_offsets.dim() != 1 or new_offsets.numel() < 2 or not new_offsets.is_contiguous():
+            raise _lib.DrnError("%s: new_offsets must be a contiguous 1-D torch.int32 tensor of at least 2 entries" % what)
+        cap = int(new_offsets.numel())
+    _timed(what, 0.0, lambda: check(lib().drn_compact_plan(_p(keep), _p(offsets), V, k, K, cap, _p(carry), _p(positions), _p(new_offsets),
+                                                           _stream()), "drn_compact_plan"))
+    return positions
+
+
+def _compact_side(what, name, table):
+    """One side of compact_rows, a plain tensor or a (codes, scales) pair -> (tensor of the rows, scales or None, rows, E)."""
+    t, scales = table if isinstance(table, tuple) else (table, None)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or not t.is_contiguous():
+        raise _lib.DrnError("%s: %s must be a contiguous (rows, E) tensor with rows >= 1 and E >= 1, not %s" % (what, name, tuple(t.shape)))
+    rows, E = (int(x) for x in t.shape)
+    if scales is None:
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.DrnError("%s: a plain %s must be float32 or bfloat16, not %s" % (what, name, t.dtype))
+    elif t.dtype != torch.uint8 or scales.dtype != torch.uint8 or E % 32 or tuple(scales.shape) != (rows, E // 32) or not scales.is_contiguous():
+        raise _lib.DrnError("%s: a quantised %s is codes (rows, E) and scales (rows, E / 32), contiguous uint8 tensors with E a multiple "
+                            "of 32" % (what, name))
+    return t, scales, rows, E
+
+
+def compact_rows(src, src_offsets, positions, dst_offsets, dst_videos, dst, dst_row0=0, dtype=None):
+    """The kept rows of ONE shard to their places in the new table.  src: the shard's table, a plain (rows, E) tensor or the pair
+    (codes, scales); src_offsets (V + 1,) int32 of a ragged shard or None; positions (V,) int32, the shard's slice as compact_plan
+    wrote it; dst_offsets, given exactly when src_offsets is: the new table's offsets on the device, at least dst_videos + 1 int32
+    entries; dst_videos = V', the videos of the new table; dst: the rows [dst_row0, dst_row0 + len(dst)) of the new table -- the whole
+    table, a row slice, or a staging buffer standing for one --, plain or a pair: a row outside it is not written
+    (drn_compact_rows).  plain -> plain copies, pair -> pair copies codes and scale bytes, pair -> plain dequantises exactly; plain ->
+    pair is REFUSED (stage the rows and run quantize_rows_mx8).  dtype: of the queries, needed only when both sides are pairs.  One
+    launch (tag compact_rows); nothing is read on the host."""
+    what = "compact_rows"
+    s, s_scales, src_rows, E = _compact_side(what, "src", src)
+    d, d_scales, dst_rows, Ed = _compact_side(what, "dst", dst)
+    _need_gpu(s, s_scales, src_offsets, positions, dst_offsets, d, d_scales)
+    if Ed != E:
+        raise _lib.DrnError("%s: src has E = %d columns, dst %d" % (what, E, Ed))
+    if s_scales is None and d_scales is not None:
+        raise _lib.DrnError("%s: plain -> mxfp8 is not taken here (there is one quantiser): move the plain rows into a staging buffer and "
+                            "run quantize_rows_mx8 on it" % what)
+    if s_scales is None and d.dtype != s.dtype:
+        raise _lib.DrnError("%s: src is %s, dst %s" % (what, s.dtype, d.dtype))
+    plain = s if s_scales is None else d if d_scales is None else None
+    if plain is None and dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.DrnError("%s: dtype (of the queries) must be float32 or bfloat16 between two quantised tables, not %s" % (what, dtype))
+    code = dtype_code(plain) if plain is not None else (F32 if dtype == torch.float32 else BF16)
+    if positions.dtype != torch.int32 or positions.dim() != 1 or positions.numel() < 1 or not positions.is_contiguous():
+        raise _lib.DrnError("%s: positions must be a contiguous (V,) torch.int32 tensor with V >= 1" % what)
+    V, dst_videos, dst_row0 = int(positions.numel()), int(dst_videos), int(dst_row0)
+    if (src_offsets is None) != (dst_offsets is None):
+        raise _lib.DrnError("%s: src_offsets and dst_offsets must both be given (ragged tables) or neither" % what)
+    if dst_videos < 1 or dst_row0 < 0:
+        raise _lib.DrnError("%s: dst_videos = %d below 1 or dst_row0 = %d below 0" % (what, dst_videos, dst_row0))
+    if src_offsets is None:
+        if src_rows != V:
+            raise _lib.DrnError("%s: a table of one row a video has %d rows for %d positions" % (what, src_rows, V))
+    else:
+        if src_offsets.dtype != torch.int32 or tuple(src_offsets.shape) != (V + 1,) or not src_offsets.is_contiguous():
+            raise _lib.DrnError("%s: src_offsets must be a contiguous (%d,) torch.int32 tensor" % (what, V + 1))
+        if dst_offsets.dtype != torch.int32 or dst_offsets.dim() != 1 or dst_offsets.numel() < dst_videos + 1 or not dst_offsets.is_contiguous():
+            raise _lib.DrnError("%s: dst_offsets must be a contiguous 1-D torch.int32 tensor of at least dst_videos + 1 = %d entries"
+                                % (what, dst_videos + 1))
+    _timed(what, 0.0, lambda: check(lib().drn_compact_rows(
+        _p(s), _p(s_scales), _p(src_offsets), _p(positions), _p(dst_offsets), V, src_rows, E, int(s_scales is not None), int(d_scales is not None),
+        code, dst_videos, dst_row0, dst_rows, _p(d), _p(d_scales), _stream()), "drn_compact_rows"))
+    return dst
+
+
 def shortlist_sharded_rank_ws_keys(blocks, S):
     """The int64 elements of the stacked workspace of a rank over K shards, from the shards' block counts (HOST integers): K * S keys,
     K * S thresholds, then the K count regions of S * blocks[k] elements each."""

@@ -55,7 +55,16 @@ the three *_rerank_reference functions over the concatenated rows are it.  drn_s
 local ones (shard_positions_reference).  A rank runs each shard's target kernel, turns the one key that is not 0 into a threshold per
 shard (rank_thresholds_reference, drn_shortlist_rank_thresholds: an equal score precedes the target in an earlier shard and follows it
 in a later one), runs each shard's counting kernel against its threshold and sums the counts (drn_shortlist_rank_reduce_shards).  A
-rerank is each shard's rerank of the candidates that fall inside it, merged by drn_shortlist_merge_lists."""
+rerank is each shard's rerank of the candidates that fall inside it, merged by drn_shortlist_merge_lists.
+
+ShardedShortlister.compact is the third verb of a corpus that changes, beside append() and allow_of(drop=): ONE new table over the
+videos a packed mask keeps, in corpus order, the dropped ones gone, with the map from old positions to new ones.  compact_reference is
+the definition.  drn_compact_plan (csrc/retrieve_compact.hip), once per shard, scans the mask -- and a ragged shard's offsets -- into
+new positions and new offsets with a carry that runs from shard to shard; after ONE synchronise (the carry, the mask words for the
+names, the new offsets for the block plan: no table data) drn_compact_rows, once per shard, moves the kept rows: plain rows and FP8
+codes and scales as they are, FP8 rows dequantised exactly where the target is plain; plain rows on their way to FP8 cross a bounded
+staging buffer into ops.quantize_rows_mx8, the one quantiser.  Where nothing is quantised the new table answers every method bit for
+bit as the shards do under allow=keep, positions mapped."""
 import collections
 import numbers
 
@@ -64,7 +73,7 @@ import torch
 
 from . import ops
 from ._lib import LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
-from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize
+from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize, mx8_quantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
 Shortlist.__doc__ = """ids (S, n) int32 store positions, best first, -1 past the list; scores (S, n) float32, 0 past the list; n (S,) int32 the
@@ -1098,6 +1107,118 @@ class Shortlister(object):
         return ops.shortlist_late_rank_phase(self._operand(), queries, lengths, seg[0], seg[1], phase, targets, keys, cnt, allow=allow)
 
 
+Compacted = collections.namedtuple("Compacted", "table positions kept")
+Compacted.__doc__ = """table: ONE new Shortlister over the surviving videos, in corpus order; positions (V,) int32 on the tables' device: the new
+position of corpus position v, -1 where v was dropped (monotone over the survivors: what remaps stored ids, targets and masks); kept:
+the host integer V' = len(table)."""
+
+COMPACT_STAGE_ELEMS = 1 << 26   # elements of the staging buffer plain rows cross on their way to FP8 (128 MiB in bfloat16): a CHOICE, not a measurement
+
+
+def _trusted_table(rows, dtype, names, offsets):
+    """A Shortlister over tables that NEED NO CHECK: rows is a plain (R, E) tensor or the pair (codes, scales) in the format, every
+    value copied or exactly dequantised from tables whose own constructors checked them (or written by the one quantiser from such
+    rows), so nothing is read again for finiteness and nothing synchronises.  offsets: host integers (V + 1) or None; the block plan
+    is made here as the constructor makes it."""
+    self = Shortlister.__new__(Shortlister)
+    self.names, self._ws = names, {}
+    if isinstance(rows, tuple):
+        self.embeddings, self.quantize, self._dtype, self.codes, self.scales = None, "mxfp8", dtype, rows[0], rows[1]
+    else:
+        self.embeddings = rows
+    if offsets is not None:
+        table = self._table()
+        off = check_segment_offsets(offsets, int(table.shape[0]), names)
+        plan = plan_segment_blocks(off)
+        put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(table.device)
+        self.plan = plan
+        self._seg = (put(off), put(plan.blk_vid), put(plan.vid_blk))
+        self.offsets = self._seg[0]
+    return self
+
+
+def _compact_target(what, shards, quantize, E):
+    """quantize= of a compaction -> the format of the result, None or "mxfp8"; "same" takes the shards' common one and refuses mixed
+    shards: doubling or halving a table's bytes is never silent."""
+    if isinstance(quantize, str) and quantize == "same":
+        formats = sorted(set(str(shard.quantize) for shard in shards))
+        if len(formats) > 1:
+            raise DrnError("%s: quantize=\"same\" needs shards of one format and these are mixed (%s): pass quantize=None for a plain "
+                           "table or quantize=\"mxfp8\" for block-scaled FP8" % (what, ", ".join(formats)))
+        return shards[0].quantize
+    if quantize not in QUANTIZE:
+        raise DrnError("%s: quantize must be \"same\" or one of %s, not %r" % (what, QUANTIZE, quantize))
+    if quantize is not None and E % MX8_BLOCK:
+        raise DrnError("%s: quantize=%r needs E to be a multiple of %d, not E = %d" % (what, quantize, MX8_BLOCK, E))
+    return quantize
+
+
+def compact_reference(shards, keep=None, quantize="same"):
+    """THE DEFINITION of ShardedShortlister.compact, in plain torch and numpy (usable on the CPU) -> Compacted.  shards: a
+    ShardedShortlister or a sequence of Shortlister objects, wherever their tensors live (an object that only stands in for a
+    resident table will do: its embeddings or codes and scales, quantize, dtype, names and offsets are all that is read).  keep: None
+    -- every video survives -- or a mask over the corpus, a bool (V,) tensor / array or the packed (W,) int32 words of pack_allow.
+    quantize: "same", None or "mxfp8", as in compact().
+
+    positions[v] = the number of kept videos before v, -1 where v is dropped; the surviving videos keep their corpus order and
+    their rows, in order; names are filtered; on ragged shards the new offsets are the running sums of the survivors' row counts (a
+    kept video without rows stays one).  Per row, by source -> target format: plain -> plain the values as they are; mxfp8 -> mxfp8
+    codes and scale bytes as they are (NOT requantised); mxfp8 -> plain mx8_dequantize(codes, scales, dtype); plain -> mxfp8
+    mx8_quantize(rows).  V' = 0, or R' = 0 on ragged shards, raises.  table is built without the constructor's checks and holds its
+    tensors on the shards' device."""
+    what = "compact_reference"
+    if isinstance(shards, ShardedShortlister):
+        sh = shards
+    else:
+        sh = ShardedShortlister.__new__(ShardedShortlister)
+        sh.shards, sh.bases, sh.names = [], [0], []
+        for shard in shards:
+            sh._admit(shard)
+        if not sh.shards:
+            raise DrnError("%s: at least one shard" % what)
+    V, E, dtype, dev = len(sh), sh.E, sh.dtype, sh.device
+    target = _compact_target(what, sh.shards, quantize, E)
+    ragged = sh.shards[0]._seg is not None
+    if keep is None:
+        mask = np.ones(V, dtype=np.bool_)
+    else:
+        m = np.asarray(keep.detach().cpu().numpy() if torch.is_tensor(keep) else keep)
+        if m.dtype == np.bool_ and m.shape == (V,):
+            mask = m.copy()
+        elif m.dtype == np.int32 and m.shape == (ops.allow_words(V),):
+            mask = np.unpackbits(np.ascontiguousarray(m).view(np.uint8), bitorder="little").astype(np.bool_)[:V]
+        else:
+            raise DrnError("%s: keep must be a bool mask (%d,) or its packed int32 words (%d,), one mask for the corpus, not %s %s"
+                           % (what, V, ops.allow_words(V), m.dtype, m.shape))
+    kept = int(mask.sum())
+    positions = np.where(mask, np.cumsum(mask) - mask, -1).astype(np.int32)
+    parts, lens = [], []
+    for shard, a, b in zip(sh.shards, sh.bases[:-1], sh.bases[1:]):
+        live = torch.from_numpy(mask[a:b])
+        if ragged:
+            n = (shard._seg[0][1:] - shard._seg[0][:-1]).cpu().to(torch.int64)
+            lens.append(n[live])
+            live = torch.repeat_interleave(live, n)
+        live = live.to(dev)
+        if shard.quantize is None:
+            rows = shard.embeddings[live]
+            parts.append(rows if target is None else mx8_quantize(rows))
+        elif target is None:
+            parts.append(mx8_dequantize(shard.codes[live], shard.scales[live], dtype))
+        else:
+            parts.append((shard.codes[live], shard.scales[live]))
+    rows = torch.cat(parts).contiguous() if target is None else (torch.cat([p[0] for p in parts]).contiguous(),
+                                                                  torch.cat([p[1] for p in parts]).contiguous())
+    R = int((rows if target is None else rows[0]).shape[0])
+    if kept == 0:
+        raise DrnError("%s: the mask keeps no video: a table needs one" % what)
+    if R == 0:
+        raise DrnError("%s: the %d videos the mask keeps own no row: a table needs one" % (what, kept))
+    offsets = np.concatenate([[0], np.cumsum(torch.cat(lens).numpy())]).astype(np.int64) if ragged else None
+    names = None if sh.names is None else [name for name, live in zip(sh.names, mask) if live]
+    return Compacted(_trusted_table(rows, dtype, names, offsets), torch.from_numpy(positions).to(dev), kept)
+
+
 class ShardedShortlister(object):
     """ShardedShortlister(shards): a corpus kept as 1 to SHARDS_MAX Shortlister objects, held by reference; the video at position i of
     shard k is the corpus's video bases[k] + i, bases being the running sums of len(shard).  The shards share the device, E, dtype (of
@@ -1128,7 +1249,10 @@ class ShardedShortlister(object):
 
     NOT here: one grouped launch over all shards in the place of K; the winning segment (rows) from a rerank; shards on several
     devices or ranks (the stacked (K, S, n) lists are laid out so that lists gathered from other GPUs merge through the same entry);
-    shards on parallel streams (they run one after the other on the current stream); compacting shards; n above SHORTLIST_MAX."""
+    shards on parallel streams (they run one after the other on the current stream); n above SHORTLIST_MAX.
+
+    compact(keep) is the third verb beside append() and allow_of(drop=): ONE new table over the videos a mask keeps, built on the
+    device, for when the shard count or the tombstone list has grown (a single table is the faster one to query)."""
 
     def __init__(self, shards):
         try:
@@ -1218,6 +1342,110 @@ class ShardedShortlister(object):
         """Shortlister.allow_of over the CORPUS: names (resolved through self.names) or corpus positions in [0, V) -> a packed mask
         (W,) int32 over all V videos on the shards' device, what shortlist(allow=) takes here."""
         return _allow_of("ShardedShortlister.allow_of", self.names, len(self), self.device, keep, drop)
+
+    def compact(self, keep=None, quantize="same", stage_elems=None):
+        """COMPACT the corpus: ONE new Shortlister over the videos `keep` keeps, in corpus order, built on the device -> Compacted(table,
+        positions, kept); compact_reference is the definition, field for field and byte for byte.  keep: None -- every video survives,
+        the shards are only joined -- or a packed mask over the corpus, contiguous int32 (W,) on the shards' device, W = ceil(V / 32):
+        what pack_allow and allow_of(drop=[...]) return (a per-sentence (S, W) mask is refused: a video is in the table or it is
+        not).  quantize: the format of the result, None for plain in self.dtype, "mxfp8", or "same" (the default), the shards'
+        common format; "same" on mixed shards raises before any launch and says to pass one.
+
+        table is plain or ragged as the shards are and owns its memory (no view of a shard); names are filtered when the corpus has
+        names; a ragged result has new offsets and a new block plan, and a kept video that owns no row stays one.  positions (V,) int32
+        on the device: the new position of corpus position v, -1 where v was dropped; kept: the host integer V'.  The shards are not
+        modified.  V' = 0 raises, and so does a ragged result without a row: a table needs one; nothing half-built is left behind.
+        ShardedShortlister([one_table]).compact(keep) drops videos from a single table.
+
+        Per row, by source -> target format: plain -> plain, the values as they are; mxfp8 -> mxfp8, codes and scale bytes COPIED byte
+        for byte (a dequantised row is never requantised: mx8_quantize(mx8_dequantize(.)) is not promised to be the identity);
+        mxfp8 -> plain, mx8_dequantize(codes, scales, dtype), exact; plain -> mxfp8, mx8_quantize(rows) byte for byte, what
+        Shortlister(rows, quantize="mxfp8") writes.  Two consequences:
+        1. Where no row goes plain -> mxfp8 (the target is plain, or every shard is FP8 already), table answers shortlist,
+           shortlist_late, rank, rank_late, rerank and rerank_late bit for bit as this object does under allow=keep, with ids,
+           targets and candidates mapped through positions: a score's bits depend on the sentence and the video's rows alone, and the
+           map is monotone, so ties fall the same way.
+        2. Where a plain shard is quantised the result equals Shortlister(those rows, quantize="mxfp8"): lossy against the shard,
+           exactly as the constructor is.
+
+        The launches, in order: with keep=, drn_allow_slices; K plan launches (drn_compact_plan, one workgroup each, a running carry
+        from shard to shard); then the host synchronises ONCE -- one transfer brings the carry (V', R' and each shard's share), the mask
+        words for names and, on ragged shards, the new offsets for plan_segment_blocks; no table data crosses to the host --, the
+        destination is allocated, and every shard's kept rows are moved by one drn_compact_rows launch.  A plain shard on its way to
+        FP8 goes through a staging buffer of at most stage_elems elements (COMPACT_STAGE_ELEMS when None, a choice): per chunk of
+        stage_elems // E destination rows one rows launch and one ops.quantize_rows_mx8, the one quantiser, and none where the shard
+        keeps no row.  The result is built WITHOUT reading the table again for finiteness: every value is a copy or an exact
+        dequantisation of one its shard's constructor checked.  Out of place: peak memory is the sources plus the destination (plus
+        the staging buffer).  It synchronises by design and cannot be captured in a graph."""
+        what = "ShardedShortlister.compact"
+        K, V, E, dev, dtype = len(self.shards), len(self), self.E, self.device, self.dtype
+        target = _compact_target(what, self.shards, quantize, E)
+        W = ops.allow_words(V)
+        if keep is not None:
+            if not torch.is_tensor(keep) or keep.dtype != torch.int32:
+                raise DrnError("%s: keep must be a packed mask, a torch.int32 tensor (pack_allow or allow_of makes one), not %s"
+                               % (what, keep.dtype if torch.is_tensor(keep) else type(keep).__name__))
+            if keep.dim() == 2:
+                raise DrnError("%s: keep is a per-sentence mask %s; a compaction takes ONE mask (%d,) over the corpus: a video is in the "
+                               "table or it is not" % (what, tuple(keep.shape), W))
+            if tuple(keep.shape) != (W,) or not keep.is_contiguous():
+                raise DrnError("%s: keep must be a contiguous (%d,) tensor, ceil(V / 32) words for V = %d videos, not %s"
+                               % (what, W, V, tuple(keep.shape)))
+            if not keep.is_cuda or keep.device != dev:
+                raise DrnError("%s: keep must be on the shards' device %s, not %s" % (what, dev, keep.device))
+        if not self.shards[0]._table().is_cuda:
+            raise DrnError("%s: the shards must be on the GPU; there is no CPU fallback (compact_reference is the definition)" % what)
+        stage_elems = COMPACT_STAGE_ELEMS if stage_elems is None else int(stage_elems)
+        if stage_elems < 1:
+            raise DrnError("%s: stage_elems = %d below 1" % (what, stage_elems))
+        if sum(int(shard._table().shape[0]) for shard in self.shards) >= 2 ** 31:
+            raise DrnError("%s: the shards hold 2^31 rows or more; one table holds fewer" % what)
+        ragged = self.shards[0]._seg is not None
+        words = keep is not None and self.names is not None
+        # ONE buffer for everything the host needs: the carry (K + 1, 2), the mask words (for names), the new offsets (V + 1)
+        head = torch.empty(2 * (K + 1) + (W if words else 0) + (V + 1 if ragged else 0), dtype=torch.int32, device=dev)
+        carry, at = head[:2 * (K + 1)].view(K + 1, 2), 2 * (K + 1)
+        if words:
+            head[at:at + W].copy_(keep)
+            at += W
+        new_off = head[at:] if ragged else None
+        positions = torch.empty(V, dtype=torch.int32, device=dev)
+        spans = list(zip(self.bases[:-1], self.bases[1:]))
+        for k, (shard, piece, (a, b)) in enumerate(zip(self.shards, self._slices(keep), spans)):
+            ops.compact_plan(piece, shard._seg[0] if ragged else None, k, carry, positions[a:b], new_off)
+        host = head.cpu()                        # THE one synchronise
+        cum = host[:2 * (K + 1)].view(K + 1, 2).tolist()
+        kept, R = cum[K]
+        if kept < 1:
+            raise DrnError("%s: the mask keeps no video: a table needs one" % what)
+        if R < 1:
+            raise DrnError("%s: the %d videos the mask keeps own no row: a table needs one" % (what, kept))
+        names = None
+        if self.names is not None:
+            names = list(self.names)
+            if words:
+                live = np.unpackbits(host[at - W:at].numpy().view(np.uint8), bitorder="little")[:V]
+                names = [name for name, bit in zip(names, live) if bit]
+        offsets = host[at:at + kept + 1].numpy().astype(np.int64) if ragged else None
+        if target is None:
+            dst = torch.empty((R, E), dtype=dtype, device=dev)
+        else:
+            dst = (torch.empty((R, E), dtype=torch.uint8, device=dev), torch.empty((R, E // MX8_BLOCK), dtype=torch.uint8, device=dev))
+        staged = [cum[k + 1][1] - cum[k][1] for k, shard in enumerate(self.shards) if shard.quantize is None and target is not None]
+        step = max(1, stage_elems // E)
+        stage = torch.empty((min(step, max(staged)), E), dtype=dtype, device=dev) if staged and max(staged) else None
+        for k, (shard, (a, b)) in enumerate(zip(self.shards, spans)):
+            src, src_off = shard._operand(), shard._seg[0] if ragged else None
+            if int(shard._table().shape[0]) == 0:     # (a shard that holds no row -- no constructor makes one -- has none to move)
+                continue
+            if shard.quantize is None and target is not None:
+                for r0 in range(cum[k][1], cum[k + 1][1], step):
+                    r1 = min(r0 + step, cum[k + 1][1])
+                    ops.compact_rows(src, src_off, positions[a:b], new_off, kept, stage[:r1 - r0], dst_row0=r0)
+                    ops.quantize_rows_mx8(stage[:r1 - r0], dst[0][r0:r1], dst[1][r0:r1])
+            else:
+                ops.compact_rows(src, src_off, positions[a:b], new_off, kept, dst, dtype=dtype)
+        return Compacted(_trusted_table(dst, dtype, names, offsets), positions, kept)
 
     def _lists(self, S, n):
         """The stacked per-shard lists of this (K, S, n): slices along dim 0 are contiguous, legal out= buffers of the shards."""

@@ -843,6 +843,34 @@ int drn_shortlist_rank_thresholds(const void* keys, int K, int S, void* threshol
  * wavefront per sentence.  All three: no atomics, no workspace beyond what is passed, nothing read on the host. */
 int drn_shortlist_rank_reduce_shards(const void* key, const void* cnt, int cnt_bytes, const int32_t* blk_off, int K, int S, int blocks,
                                      int32_t* rank, float* score, int32_t* total, void* stream);
+/* COMPACTING THE K TABLES INTO ONE (drn_amd/csrc/retrieve_compact.hip; drn_amd.retrieve.compact_reference is the definition): the
+ * videos a packed mask keeps, in corpus order, in a new table.  drn_compact_plan is launched once per shard, k = 0 .. K - 1, IN STREAM
+ * ORDER: keep [ceil(V / 32)] is the shard's own piece of the mask as drn_allow_slices cuts it (NULL: every video is kept), offsets
+ * [V + 1] the shard's own on a ragged shard (NULL: one row a video), V the shard's videos.  carry [K + 1][2] int32 holds (videos kept,
+ * rows kept) BEFORE each shard: launch k reads carry[k] -- launch 0 writes it, zeros -- and writes carry[k + 1], so carry[K] is (V',
+ * R') of the new table and the launches need nothing else from each other.  positions [V] is the SHARD'S slice of the corpus's map:
+ * the new position of each video, -1 where it is dropped.  new_offsets [cap] (given exactly when offsets is) gets, at the new position
+ * of every kept video, the rows kept before it, and at carry[k + 1].videos the rows kept so far: after launch K - 1 its first V' + 1
+ * entries are the new table's offsets; an index at or past cap is never written (cap = the corpus's videos + 1 is always enough).  An
+ * exclusive scan by ONE workgroup a launch: no workgroup waits on another, no flag, no atomics, no workspace, nothing read on the host. */
+int drn_compact_plan(const int32_t* keep, const int32_t* offsets, int V, int k, int K, int cap, int32_t* carry, int32_t* positions,
+                     int32_t* new_offsets, void* stream);
+/* One launch per shard: the kept rows of the shard to their places.  src is the shard's plain rows [src_rows][E] in `dtype`, or its
+ * codes [src_rows][E] u8 with src_scales [src_rows][E / 32] (src_format DRN_COMPACT_MX8); src_offsets and positions as the shard gave
+ * them to drn_compact_plan and as it wrote them; dst_offsets [dst_videos + 1] the new table's offsets (given exactly when src_offsets
+ * is), dst_videos = V'.  Video v with p = positions[v] in [0, dst_videos) owns the source rows src_offsets[v] .. src_offsets[v + 1] - 1
+ * (row v) and its row j goes to row dst_offsets[p] + j (row p) of the new table; dst (and dst_scales) is a WINDOW of that table or a
+ * staging buffer for it, holding its rows [dst_row0, dst_row0 + dst_rows): a row outside the window is not written, and nothing else
+ * is.  The pairs: plain -> plain, the values as they are; FP8 -> FP8, codes and scale bytes byte for byte (nothing is requantised);
+ * FP8 -> plain, float(code) * 2^(scale - 127) in `dtype`, exact.  plain -> FP8 is REFUSED: the caller stages plain rows and runs
+ * drn_quantize_rows_mx8, the one quantiser.  E % 32 == 0 with an FP8 side; dtype is that of the plain side (of the queries when there
+ * is none).  16-byte accesses when every base pointer and row pitch allows it, one element a lane otherwise; 64-bit row addresses; a
+ * bounded grid.  No atomics, no workspace, nothing read on the host. */
+#define DRN_COMPACT_PLAIN 0
+#define DRN_COMPACT_MX8 1
+int drn_compact_rows(const void* src, const uint8_t* src_scales, const int32_t* src_offsets, const int32_t* positions,
+                     const int32_t* dst_offsets, int V, int src_rows, int E, int src_format, int dst_format, int dtype, int dst_videos,
+                     int dst_row0, int dst_rows, void* dst, uint8_t* dst_scales, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

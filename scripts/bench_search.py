@@ -131,7 +131,16 @@
            on the ragged layout -- rank_late (16 tokens) on the same two layouts and K = 1 / 4 / 16 equal shards, S in {1, 8, 64}, by the
            protocol of --sharded-shortlist, beside the single Shortlister over the same rows (every field asserted equal before timing);
            and append + rank beside torch.cat + Shortlister + rank on the same tensors, the gain judged against the latter's own
-           max - min.  No time is required of the sharded calls (2 K + 3 launches against 3): the ratios are what is reported."""
+           max - min.  No time is required of the sharded calls (2 K + 3 launches against 3): the ratios are what is reported.
+
+  --compact   instead of the above -> profiles/search_compact_bench.json: ShardedShortlister.compact on the same two layouts, all-bf16,
+           all-FP8 and half / half shards (target plain), K = 4 and 16, all kept and a random 10 % dropped, beside the route the parent
+           offers on the same shards and mask -- mx8_dequantize of the FP8 shards, torch.cat, index_select, Shortlister(...) -- by a host
+           clock to a device synchronise, the two taking turns in every round, the result asserted equal to compact_reference byte for
+           byte before timing.  (G1) compact() takes less than the route by more than the route's own max - min: HOLDS / DOES NOT HOLD
+           per shape, no absolute time required.  Without a bar: the rows launches' bytes per second (bytes from the shapes, device
+           events around each launch: launch-inclusive) against the HBM peak, and shortlist and rank at S = 8, n = 16 on the compacted
+           table beside the K = 16 sharded object under the same mask."""
 import argparse
 import json
 import os
@@ -2251,6 +2260,160 @@ def main_sharded_rank(args):
     print("wrote", out)
 
 
+HBM_PEAK_TBS = 8.0                                          # the MI355X's HBM3E peak by its data sheet (a float4 copy reaches about 6.3)
+COMPACT_FORMATS = (("bf16", (), "same"), ("fp8", "all", "same"), ("half_fp8_to_plain", "even", None))
+
+
+def compact_route(sh, mask_dev, mask_host, lens, lens_dev, target):
+    """The way back to one table WITHOUT compact(): dequantise the FP8 shards in torch, torch.cat, index_select of the survivors, and a
+    fresh Shortlister, whose constructor reads the whole table again for finiteness and quantises it when the target is FP8."""
+    import numpy as np
+    from drn_amd import Shortlister
+    from drn_amd.index import mx8_dequantize
+    rows = torch.cat([s.embeddings if s.quantize is None else mx8_dequantize(s.codes, s.scales, s.dtype) for s in sh.shards])
+    if max(lens) == 1:
+        return Shortlister(rows.index_select(0, mask_dev.nonzero().squeeze(1)), quantize=target)
+    live = torch.repeat_interleave(mask_dev, lens_dev)
+    off = np.concatenate([[0], np.cumsum(np.asarray(lens)[mask_host])])
+    return Shortlister(rows.index_select(0, live.nonzero().squeeze(1)), offsets=off, quantize=target)
+
+
+def compact_rows_bytes(sh, kept_rows, target, V):
+    """Bytes the rows launches read plus bytes they write, from the shapes: every kept row once in its source format and once in the
+    target's (512 columns: 1024 bytes in bf16, 528 in FP8), the positions of every video (4 bytes) and, on a ragged corpus, two source
+    offsets a video and one new offset a kept video -- counted as 12 bytes a video, an upper bound."""
+    read = sum(n * (1024 if s.quantize is None else 528) for s, n in zip(sh.shards, kept_rows))
+    return read + sum(kept_rows) * (1024 if target is None else 528) + V * (4 if sh.shards[0]._seg is None else 16)
+
+
+def bench_compact(name, lens, emb, fmt, K, mask_name, rounds, iters=5):
+    """ShardedShortlister.compact beside compact_route on the same shards and mask: host clock from before the call to after a device
+    synchronise, the two taking turns inside every round, a round = the mean of `iters` runs.  Before timing the result is asserted
+    equal to compact_reference byte for byte, and to the route's table wherever the two are promised equal (a plain target)."""
+    import numpy as np
+    from drn_amd import ShardedShortlister, compact_reference, ops, pack_allow
+    label, which, quantize = fmt
+    q8 = range(K) if which == "all" else range(0, K, 2) if which == "even" else ()
+    sh = ShardedShortlister(equal_shards(emb, lens, K, quantize=q8))
+    V = len(sh)
+    lens_dev = torch.tensor(lens, device="cuda:0")
+    g = torch.Generator(device="cuda:0").manual_seed(K)
+    mask_dev = torch.ones(V, dtype=torch.bool, device="cuda:0") if mask_name == "all_kept" else torch.rand(V, generator=g, device="cuda:0") >= 0.1
+    mask_host = mask_dev.cpu().numpy()
+    keep = None if mask_name == "all_kept" else pack_allow(mask_dev)
+    target = sh.shards[0].quantize if quantize == "same" else quantize
+    got, want, route = sh.compact(keep, quantize=quantize), compact_reference(sh, keep=mask_dev.cpu(), quantize=quantize), \
+        compact_route(sh, mask_dev, mask_host, lens, lens_dev, target)
+    assert got.kept == want.kept and torch.equal(got.positions, want.positions)
+    tensors = lambda t: (t.embeddings,) if t.quantize is None else (t.codes, t.scales)
+    for a, b in zip(tensors(got.table), tensors(want.table)):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), (name, label, K, mask_name)
+    route_equal = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(tensors(got.table), tensors(route)))
+    assert route_equal or target is not None, (name, label, K, mask_name)     # (FP8 -> FP8 copies bytes; the route requantises: equality is not promised)
+    if got.table._seg is not None:
+        assert torch.equal(got.table.offsets, want.table.offsets) and torch.equal(got.table.offsets, route.offsets)
+    del want, route
+
+    def timed(run):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+    ours, theirs, rows_us = [], [], []
+    for _ in range(rounds):
+        ours.append(statistics.mean(timed(lambda: sh.compact(keep, quantize=quantize)) for _ in range(iters)))
+        theirs.append(statistics.mean(timed(lambda: compact_route(sh, mask_dev, mask_host, lens, lens_dev, target)) for _ in range(iters)))
+        ops.kernel_timer = []
+        sh.compact(keep, quantize=quantize)
+        torch.cuda.synchronize()
+        rows_us.append(sum(e0.elapsed_time(e1) for tag, _, e0, e1 in ops.kernel_timer if tag == "compact_rows") * 1e3)
+        ops.kernel_timer = None
+    off = np.concatenate([[0], np.cumsum(lens)])
+    kept_rows = [int(np.asarray(lens)[a:b][mask_host[a:b]].sum()) for a, b in zip(sh.bases[:-1], sh.bases[1:])]
+    nbytes = compact_rows_bytes(sh, kept_rows, target, V)
+    gain = statistics.median(theirs) - statistics.median(ours)
+    holds = gain > max(theirs) - min(theirs)                 # (less than the route by more than the route's own spread)
+    return {"layout": name, "R": int(off[-1]), "V": V, "E": 512, "formats": label, "target": target or "plain", "K": K, "mask": mask_name,
+            "kept_videos": got.kept, "kept_rows": sum(kept_rows), "runs_per_round": iters, "compact_us": spread(ours), "route_us": spread(theirs),
+            "compact_over_route": statistics.median(ours) / statistics.median(theirs),
+            "G1": {"route_minus_compact_us": gain, "route_max_minus_min_us": max(theirs) - min(theirs), "verdict": "HOLDS" if holds else "DOES NOT HOLD"},
+            "route_bytes_equal": route_equal,
+            "rows_launches": {"us": spread(rows_us), "bytes": nbytes, "TB_per_s": nbytes / (statistics.median(rows_us) * 1e-6) / 1e12,
+                              "share_of_hbm_peak": nbytes / (statistics.median(rows_us) * 1e-6) / 1e12 / HBM_PEAK_TBS,
+                              "note": "the K rows launches of one call, device events around each launch from Python: launch-inclusive, not "
+                                      "a kernel-trace figure; set against the data sheet's %.1f TB/s" % HBM_PEAK_TBS}}
+
+
+def bench_compact_buys(name, lens, emb, rounds, S=8, n=16, K=16):
+    """What the compaction buys: shortlist and rank at S = 8, n = 16 on the compacted table beside the K = 16 sharded object under the
+    same mask (a random 10 % dropped), every field asserted equal (ids and targets mapped through positions) before timing."""
+    from drn_amd import ShardedShortlister, pack_allow
+    sh = ShardedShortlister(equal_shards(emb, lens, K))
+    V = len(sh)
+    g = torch.Generator(device="cuda:0").manual_seed(99)
+    mask = torch.rand(V, generator=g, device="cuda:0") >= 0.1
+    keep = pack_allow(mask)
+    done = sh.compact(keep)
+    table, pos = done.table, done.positions
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    targets = torch.randint(0, V, (S,), generator=g, device="cuda:0").to(torch.int32)
+    local = pos[targets.long()].contiguous()
+    a, b = table.shortlist(q, n), sh.shortlist(q, n, allow=keep)
+    assert torch.equal(a.ids, torch.where(b.ids >= 0, pos[b.ids.clamp(min=0).long()], b.ids)) and torch.equal(a.scores, b.scores) and torch.equal(a.n, b.n)
+    same_fields(table.rank(q, local), sh.rank(q, targets, allow=keep), (name, "rank"))
+    ra, rb = table.rank(q, local), sh.rank(q, targets, allow=keep)
+    times, reps = interleaved_windows({
+        "shortlist_compacted": lambda: table.shortlist(q, n, out=a), "shortlist_sharded": lambda: sh.shortlist(q, n, out=b, allow=keep),
+        "rank_compacted": lambda: table.rank(q, local, out=ra), "rank_sharded": lambda: sh.rank(q, targets, out=rb, allow=keep)}, rounds)
+    row = {"layout": name, "S": S, "n": n, "K": K, "mask": "random 10 % dropped", "kept_videos": done.kept, "launches_per_window": reps}
+    for m in ("shortlist", "rank"):
+        c, s = times[m + "_compacted"], times[m + "_sharded"]
+        row[m] = {"compacted_us": spread(c), "sharded_masked_us": spread(s), "sharded_over_compacted": statistics.median(s) / statistics.median(c),
+                  "compacted_against_sharded": verdict(c, s)}
+    return row
+
+
+def main_compact(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_compact_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the shards resident, every shape warmed",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds; a round = the mean of 5 runs",
+                      "clock": "host clock from before the call to after a device synchronise (compact and the route); device events "
+                               "around each rows launch (rows_launches); device events around windows of back-to-back calls (buys)",
+                      "yardstick": "the route the parent offers: mx8_dequantize of the FP8 shards, torch.cat, index_select of the survivors, "
+                                   "Shortlister(rows, offsets, quantize=target), in the same process on the same shards and mask",
+                      "G1": "compact() takes less than the route, by more than the route's own max - min: HOLDS / DOES NOT HOLD per "
+                            "shape; a shape where it does not hold is reported and not tuned; no absolute time is required",
+                      "what_this_does_not_say": "random embeddings, bf16 queries, equal shards, E = 512 only; the route is given the mask as a "
+                                                "bool tensor on the device and on the host, compact() its packed words; all-FP8 shards "
+                                                "compact to FP8 by a byte copy where the route requantises (route_bytes_equal says whether "
+                                                "the bytes came out equal all the same: it is not promised); no kernel-only times"},
+           "compact": [], "buys": []}
+
+    def save():
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for name, lens in SEGMENT_LAYOUTS[:2]:
+        for fmt in COMPACT_FORMATS:
+            for K in (4, 16):
+                for mask_name in ("all_kept", "random_10pct_dropped"):
+                    row = bench_compact(name, lens, emb, fmt, K, mask_name, args.rounds)
+                    res["compact"].append(row)
+                    print("compact %s %s K = %d %s: compact / route = %.3f, %.0f against %.0f us, (G1) %s; rows launches %.2f TB/s" % (
+                        name, fmt[0], K, mask_name, row["compact_over_route"], row["compact_us"]["median"], row["route_us"]["median"],
+                        row["G1"]["verdict"], row["rows_launches"]["TB_per_s"]), flush=True)
+                    save()
+        row = bench_compact_buys(name, lens, emb, args.rounds)
+        res["buys"].append(row)
+        print(json.dumps({"buys": row}), flush=True)
+        save()
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -2258,7 +2421,7 @@ def main():
                                             "search_filtered_shortlist_bench.json with --filtered-shortlist, search_late_shortlist_bench.json with "
                                             "--late-shortlist, search_rank_bench.json with --rank, search_rerank_bench.json with --rerank, "
                                             "search_sharded_shortlist_bench.json with --sharded-shortlist, search_sharded_rank_bench.json with "
-                                            "--sharded-rank)")
+                                            "--sharded-rank, search_compact_bench.json with --compact)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shortlist", action="store_true", help="measure Grounder.search(candidates=) beside the cartesian search")
     ap.add_argument("--evaluate", action="store_true", help="measure evaluate_search beside scoring Hits.tolist() on the host")
@@ -2287,9 +2450,14 @@ def main():
                                                                      "shortlist_late, and append beside torch.cat + rebuild")
     ap.add_argument("--sharded-rank", action="store_true", help="measure ShardedShortlister.rank, rank_late and rerank on 1 / 4 / 16 equal shards "
                                                                 "beside the single table, and append + rank beside torch.cat + rebuild + rank")
+    ap.add_argument("--compact", action="store_true", help="measure ShardedShortlister.compact beside dequantise + torch.cat + index_select + "
+                                                           "Shortlister on the same shards, the rows launches' bytes per second, and "
+                                                           "what the compacted table buys against K = 16 shards under the same mask")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.compact:
+        return main_compact(args)
     if args.sharded_rank:
         return main_sharded_rank(args)
     if args.sharded_shortlist:
