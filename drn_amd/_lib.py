@@ -26,6 +26,7 @@ SHORTLIST_SEG_BLOCK = 256  # videos of one block of drn_shortlist_segments_topn'
 LATE_MAX_TOKENS = 64      # DRN_LATE_MAX_TOKENS: token vectors of one sentence of drn_shortlist_late_topn (a choice that bounds a workgroup's time)
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 RERANK_MAX_CANDIDATES = CANDIDATES_MAX  # DRN_RERANK_MAX_CANDIDATES: columns of the list drn_shortlist_rerank takes (a CHOICE: the width the Grounder takes)
+SHORTLIST_DEEP_MAX = RERANK_MAX_CANDIDATES  # DRN_SHORTLIST_DEEP_MAX: the longest list drn_shortlist_deep returns (a CHOICE: the width its consumers take)
 RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
 SHARDS_MAX = 64           # DRN_SHARDS_MAX: tables of one ShardedShortlister, lists a sentence drn_shortlist_merge_lists merges (a choice, not a measurement)
 
@@ -194,6 +195,8 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_segments_topn_q8_allow": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_deep": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_late_topn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_late_topn_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -1,7 +1,8 @@
 // Filtered shortlists (drn_amd/retrieve.py, Shortlister.shortlist(allow=)): the four shortlist entries with a packed ALLOW MASK, and its maker.
 //   drn_shortlist_topn_allow / drn_shortlist_segments_topn_allow             the plain and the ragged table (retrieve.hip, retrieve_seg.hip);
 //   drn_shortlist_topn_q8_allow / drn_shortlist_segments_topn_q8_allow       the same two kept in block-scaled FP8 (retrieve_q8.hip);
-//   drn_pack_allow                                                           a bool mask (V,) or (S, V) -> the packed words, one launch.
+//   drn_pack_allow                                                           a bool mask (V,) or (S, V) -> the packed words, one launch;
+//   drn_shortlist_deep                                                       the four tables at n up to 1024: host code over the same phase one.
 #include "common.h"
 #include "shortlist.h"
 #include "../../include/drn_hip.h"
@@ -244,7 +245,7 @@ struct AlArgs {
   int32_t* rows;
 };
 
-static int al_check(const char* what, const AlArgs& a) {
+static int al_check(const char* what, const AlArgs& a, const int cap) {
   const bool ragged = a.ragged, q8 = a.q8;
   DRN_CHECK_ARG(a.table && (!q8 || a.scales) && a.queries && a.allow && a.ws && a.ids && a.scores && a.counts &&
                     (!ragged || (a.offsets && a.blk_vid && a.vid_blk && a.rows)),
@@ -258,7 +259,7 @@ static int al_check(const char* what, const AlArgs& a) {
   if (ragged)
     DRN_CHECK_ARG(a.nblocks >= 1 && a.nblocks <= a.V && (long)a.nblocks * AL_BLOCK >= a.V, "%s: %d blocks outside [ceil(V / %d), V] for V = %d videos",
                   what, a.nblocks, AL_BLOCK, a.V);
-  DRN_CHECK_ARG(a.n >= 1 && a.n <= DRN_SHORTLIST_MAX, "%s: n = %d outside [1, %d]", what, a.n, DRN_SHORTLIST_MAX);
+  DRN_CHECK_ARG(a.n >= 1 && a.n <= cap, "%s: n = %d outside [1, %d]", what, a.n, cap);
   DRN_CHECK_ARG(a.dtype == DRN_F32 || a.dtype == DRN_BF16, "%s: dtype %d (float32 / bfloat16 only)", what, a.dtype);
   DRN_CHECK_ARG(((uintptr_t)a.table & 15) == 0 && ((uintptr_t)a.queries & 15) == 0 && ((uintptr_t)a.ws & 7) == 0,
                 "%s: the table and the queries must be 16-byte aligned, the workspace 8-byte aligned", what);
@@ -278,10 +279,11 @@ static int al_check(const char* what, const AlArgs& a) {
   return DRN_OK;
 }
 
-// phase one with the operand Op, then the merge (and the segment look-up) of the unmasked entries.  RAGGED is a compile-time switch:
-// an operand instantiates only the kernel it is launched on
+// phase one with the operand Op, then the merge (and the segment look-up) of the unmasked entries -- DEEP: the deep merge of
+// retrieve_deep.hip in its place.  RAGGED is a compile-time switch: an operand instantiates only the kernel it is launched on; deep is
+// a run-time one: both depths launch the same phase-one instantiations
 template <bool RAGGED, typename Op>
-static void al_launch(const Op op, const AlArgs& a, hipStream_t stream) {
+static void al_launch(const Op op, const AlArgs& a, const bool deep, hipStream_t stream) {
   typedef typename Op::Q Q;
   const int m = a.n < AL_BLOCK ? a.n : AL_BLOCK, nblocks = RAGGED ? a.nblocks : cdiv(a.V, AL_BLOCK);
   const dim3 grid(nblocks, cdiv(a.S, 16));
@@ -289,33 +291,33 @@ static void al_launch(const Op op, const AlArgs& a, hipStream_t stream) {
   if constexpr (!RAGGED) {
     shortlist_block_allow_kernel<Op><<<grid, 256, 0, stream>>>(op, (const Q*)a.queries, a.allow, a.allow_stride, a.V, a.E, a.S, m, nblocks,
                                                                 lists_k);
-    sl_launch_merge(lists_k, a.S, a.n, m, nblocks, a.ids, a.scores, a.counts, stream);
+    (deep ? sl_launch_merge_deep : sl_launch_merge)(lists_k, a.S, a.n, m, nblocks, a.ids, a.scores, a.counts, stream);
   } else {
     int* lists_r = (int*)(lists_k + (long)a.S * nblocks * m);
     shortlist_segments_allow_kernel<Op><<<grid, 256, 0, stream>>>(op, (const Q*)a.queries, a.offsets, a.blk_vid, a.allow, a.allow_stride,
                                                                    a.R, a.V, a.E, a.S, m, nblocks, lists_k, lists_r);
-    sl_launch_merge(lists_k, a.S, a.n, m, nblocks, a.ids, a.scores, a.counts, stream);
+    (deep ? sl_launch_merge_deep : sl_launch_merge)(lists_k, a.S, a.n, m, nblocks, a.ids, a.scores, a.counts, stream);
     sl_launch_segment_rows(lists_k, lists_r, a.vid_blk, a.ids, a.V, a.S, a.n, m, nblocks, a.rows, stream);
   }
 }
 
 template <bool RAGGED>
-static void al_launch_table(const AlArgs& a, hipStream_t stream) {
+static void al_launch_table(const AlArgs& a, const bool deep, hipStream_t stream) {
   const uint8_t *codes = (const uint8_t*)a.table, *scales = (const uint8_t*)a.scales;
   const bool bf16 = a.dtype == DRN_BF16;
   // (a quantised bf16 chain keeps two scale blocks of loads in flight in the ranked block, one in the ragged kernel: retrieve_q8.hip
   // says why)
-  if (!a.q8 && bf16) al_launch<RAGGED>(AlPlain<bf16_t>{(const bf16_t*)a.table}, a, stream);
-  else if (!a.q8) al_launch<RAGGED>(AlPlain<float>{(const float*)a.table}, a, stream);
-  else if (bf16) al_launch<RAGGED>(AlQ8<bf16_t, RAGGED ? 1 : 2>{codes, scales}, a, stream);
-  else al_launch<RAGGED>(AlQ8<float, 1>{codes, scales}, a, stream);
+  if (!a.q8 && bf16) al_launch<RAGGED>(AlPlain<bf16_t>{(const bf16_t*)a.table}, a, deep, stream);
+  else if (!a.q8) al_launch<RAGGED>(AlPlain<float>{(const float*)a.table}, a, deep, stream);
+  else if (bf16) al_launch<RAGGED>(AlQ8<bf16_t, RAGGED ? 1 : 2>{codes, scales}, a, deep, stream);
+  else al_launch<RAGGED>(AlQ8<float, 1>{codes, scales}, a, deep, stream);
 }
 
-static int al_run(const char* what, const AlArgs& a, void* stream) {
+static int al_run(const char* what, const AlArgs& a, void* stream, const bool deep = false) {
   drn_clear_status();
-  if (const int rc = al_check(what, a)) return rc;
-  if (a.ragged) al_launch_table<true>(a, (hipStream_t)stream);
-  else al_launch_table<false>(a, (hipStream_t)stream);
+  if (const int rc = al_check(what, a, deep ? DRN_SHORTLIST_DEEP_MAX : DRN_SHORTLIST_MAX)) return rc;
+  if (a.ragged) al_launch_table<true>(a, deep, (hipStream_t)stream);
+  else al_launch_table<false>(a, deep, (hipStream_t)stream);
   return drn_launch_status(what);
 }
 
@@ -352,6 +354,23 @@ extern "C" int drn_shortlist_segments_topn_q8_allow(const uint8_t* codes, const 
   const AlArgs a = {true, true, codes, scales, queries, offsets, blk_vid, vid_blk, allow, allow_stride, R, V, nblocks, E, S, n, dtype,
                     ws, ws_keys, ids, scores, counts, rows};
   return al_run("drn_shortlist_segments_topn_q8_allow", a, stream);
+}
+
+// The DEEP shortlist (include/drn_hip.h): all four tables behind one entry, by the convention of the rank and rerank entries -- scales ==
+// NULL is a plain table, offsets == NULL one row per video.  Host code only: phase one is the eight instantiations above, which already
+// write m up to 256; the merge is sl_launch_merge_deep (retrieve_deep.hip).  The mask is required (the caller without a filter passes
+// an all-ones row with stride 0), so no unmasked phase one is instantiated for it.
+extern "C" int drn_shortlist_deep(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets,
+                                  const int32_t* blk_vid, const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V,
+                                  int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
+                                  int32_t* counts, int32_t* rows, void* stream) {
+  const char* what = "drn_shortlist_deep";
+  const bool ragged = offsets != nullptr;
+  DRN_CHECK_ARG(ragged || !(blk_vid || vid_blk || rows),
+                "%s: null pointer: offsets is NULL (one row per video), so blk_vid, vid_blk and rows must be NULL too", what);
+  const AlArgs a = {ragged, scales != nullptr, table, scales, queries, offsets, blk_vid, vid_blk, allow, allow_stride, ragged ? R : 0, V,
+                    ragged ? nblocks : 0, E, S, n, dtype, ws, ws_keys, ids, scores, counts, rows};
+  return al_run(what, a, stream, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 // retrieve_rank.hip counts, on the same operands and keys, the videos that precede a named one: no sort, no list.
 // retrieve_rerank.hip scores, on the same operands, keys and merge, only the (sentence, video) pairs a candidate list names.
 // retrieve_shard.hip merges the finished lists of several tables: the same key, rebuilt from (score, base + id), and the same sort.
+// retrieve_deep.hip merges the lists of phase one into lists of up to 1024: the same key and sort, one workgroup per sentence.
 #pragma once
 #include "common.h"
 #include "mx8.h"
@@ -185,6 +186,9 @@ struct AlQ8 {
 // shortlist_merge_kernel (retrieve.hip) on `stream`: sentence s merges its nblocks sorted lists of m keys, ws[s][block][0..m), into
 // ids, scores [S][n] and counts [S].  Not part of the C ABI.
 void sl_launch_merge(const sl_key_t* ws, int S, int n, int m, int nblocks, int32_t* ids, float* scores, int32_t* counts, hipStream_t stream);
+// shortlist_merge_deep_kernel (retrieve_deep.hip) on `stream`: the same contract for n up to DRN_SHORTLIST_DEEP_MAX, m = min(n, 256) --
+// one workgroup of 256 threads per sentence, four lists in flight.  Not part of the C ABI.
+void sl_launch_merge_deep(const sl_key_t* ws, int S, int n, int m, int nblocks, int32_t* ids, float* scores, int32_t* counts, hipStream_t stream);
 // shortlist_segment_rows_kernel (retrieve_seg.hip) on `stream`: the winning segment of each listed (sentence, place), looked up in the
 // lists ws / wsr of the video's block, into rows [S][n].  Not part of the C ABI.
 void sl_launch_segment_rows(const sl_key_t* ws, const int* wsr, const int32_t* vid_blk, const int32_t* ids, int V, int S, int n, int m,

@@ -1549,10 +1549,10 @@ def _allow_args(what, allow, V, S):
     return _p(allow), stride
 
 
-def _shortlist_buffers(what, S, n, need, ws, ids, scores, counts, rows=None):
-    """The checks the shortlist wrappers share: n, the output buffers and the workspace."""
-    if not 1 <= n <= _lib.SHORTLIST_MAX:
-        raise _lib.DrnError("%s: n = %d outside [1, %d]" % (what, n, _lib.SHORTLIST_MAX))
+def _shortlist_buffers(what, S, n, need, ws, ids, scores, counts, rows=None, cap=_lib.SHORTLIST_MAX):
+    """The checks the shortlist wrappers share: n (at most cap), the output buffers and the workspace."""
+    if not 1 <= n <= cap:
+        raise _lib.DrnError("%s: n = %d outside [1, %d]" % (what, n, cap))
     outs = (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,)))
     if rows is not None:
         outs += (("rows", rows, torch.int32, (S, n)),)
@@ -1632,6 +1632,42 @@ def shortlist_segments_topn(table, queries, offsets, blk_vid, vid_blk, n, ws, id
     elements.  One C entry and one tag per kind of call (drn_shortlist_segments_topn[_q8][_allow]): three launches on the current
     stream; the tables and the mask are not read on the host and nothing is synchronised."""
     return _shortlist_entry(table, queries, (offsets, blk_vid, vid_blk), n, ws, (ids, scores, counts, rows), allow)
+
+
+def shortlist_deep(table, queries, seg, n, ws, outs, allow):
+    """The DEEP shortlist, 1 <= n <= SHORTLIST_DEEP_MAX, behind ONE entry and one tag (drn_shortlist_deep / shortlist_deep) for all
+    four tables: table is emb or a pair (codes, scales), seg is () or (offsets, blk_vid, vid_blk), outs is (ids, scores, counts) or
+    (ids, scores, counts, rows) -- each as in shortlist_topn / shortlist_segments_topn, with their checks, their workspace sizes
+    (shortlist_ws_keys / shortlist_segments_ws_keys) and their definitions.  allow is REQUIRED: a packed mask (W,) or (S, W) int32 on
+    the device (a caller without a filter passes a row of all-ones words).  Two launches on a plain table, three on a ragged one, on
+    the current stream; nothing is read on the host."""
+    what = "shortlist_deep"
+    if allow is None:
+        raise _lib.DrnError("%s: allow is required: a packed mask (pass a row of all-ones words to list every video)" % what)
+    q8 = isinstance(table, (tuple, list))
+    seg, outs = tuple(seg), tuple(outs)
+    if len(seg) not in (0, 3) or len(outs) != (4 if seg else 3):
+        raise _lib.DrnError("%s: seg must be () or (offsets, blk_vid, vid_blk) and outs (ids, scores, counts) or, on a ragged table, "
+                            "(ids, scores, counts, rows)" % what)
+    tensors = (tuple(table) if q8 else (table,)) + (queries,) + seg
+    _need_gpu(*(tensors + (allow, ws) + outs))
+    n = int(n)
+    rows, E = _q8_table(what, table[0], table[1], queries) if q8 else _plain_table(what, table, queries)
+    S = int(queries.shape[0])
+    if seg:
+        V, nblocks = _segment_tables(what, *seg)
+        need = shortlist_segments_ws_keys(nblocks, S, n)
+    else:
+        V, nblocks = rows, 0
+        need = shortlist_ws_keys(V, S, n)
+    _shortlist_buffers(what, S, n, need, ws, *outs, cap=_lib.SHORTLIST_DEEP_MAX)
+    mask, stride = _allow_args(what, allow, V, S)
+    args = (_p(table[0]), _p(table[1])) if q8 else (_p(table), None)
+    args += (_p(queries),) + (tuple(_p(t) for t in seg) if seg else (None, None, None)) + (mask, stride, rows if seg else 0, V, nblocks, E, S, n,
+                                                                                          dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)))
+    args += tuple(_p(t) for t in outs) + (() if seg else (None,))
+    _timed(what, 2.0 * S * rows * E, lambda: check(lib().drn_shortlist_deep(*args, _stream()), "drn_shortlist_deep"))
+    return outs
 
 
 def shortlist_late_ws_keys(nblocks, S, n):

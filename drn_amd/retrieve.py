@@ -30,6 +30,10 @@ Shortlister.shortlist_late takes the QUERY side multi-vector too (late interacti
 tokens of the token's best row of the video.  late_shortlist_reference is the definition, drn_shortlist_late_topn
 (csrc/retrieve_late.hip) the launch, on a ragged table plain or quantised, with or without a mask.
 
+Shortlister.shortlist_deep is shortlist() up to SHORTLIST_DEEP_MAX = 1024 videos a sentence -- the width rerank and
+Grounder.search(candidates=) take -- on all four tables, with or without a mask: the same definitions, drn_shortlist_deep the one
+entry (the masked phase one, then the merge of csrc/retrieve_deep.hip).
+
 Shortlister.rank and rank_late answer what a list of at most SHORTLIST_MAX cannot: the place of a NAMED video in the FULL order -- how
 many candidates precede targets[s], over the whole table, with its score and the number of candidates -- from the kernels' own scores
 and total order, without a list, a sort or a host read.  rank_reference, segment_rank_reference and late_rank_reference are the
@@ -72,7 +76,8 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK, DrnError      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
+from ._lib import (LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_DEEP_MAX, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK,
+                   DrnError)      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize, mx8_quantize
 
 Shortlist = collections.namedtuple("Shortlist", "ids scores n")
@@ -805,10 +810,10 @@ class Shortlister(object):
         """The refusals of shortlist(allow=), before the library is reached."""
         _check_packed_allow(allow, S, len(self), self._table().device)
 
-    def _check_queries(self, what, queries, S=None, n=None, on_table=True):
+    def _check_queries(self, what, queries, S=None, n=None, on_table=True, cap=SHORTLIST_MAX):
         """What shortlist, rank and rerank refuse about queries of one vector a sentence and (where given) n -> (S, n).  S: the rows
         they must have (rerank: one per row of candidates), None for any S >= 1.  on_table: rank and rerank ask for the table's
-        device, shortlist for the GPU."""
+        device, shortlist for the GPU.  cap: the largest n (shortlist_deep: SHORTLIST_DEEP_MAX)."""
         E, dtype = self.E, self.dtype
         if not torch.is_tensor(queries):
             raise DrnError("%s: the queries must be a tensor" % what)
@@ -820,8 +825,8 @@ class Shortlister(object):
             raise DrnError("%s: the queries are %s, the table is %s" % (what, queries.dtype, dtype))
         if n is not None:
             n = int(n)
-            if not 1 <= n <= SHORTLIST_MAX:
-                raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_MAX))
+            if not 1 <= n <= cap:
+                raise DrnError("%s: n = %d outside [1, %d]" % (what, n, cap))
         if not on_table:
             if not queries.is_cuda:
                 raise DrnError("%s: the queries must be on the GPU; there is no CPU fallback" % what)
@@ -872,6 +877,50 @@ class Shortlister(object):
         ws = self._workspace((S, n), lambda: ops.shortlist_segments_ws_keys(self._nblocks(), S, n))
         ops.shortlist_segments_topn(self._operand(), queries.contiguous(), seg[0], seg[1], seg[2], n, ws, *out, allow=allow)
         return SegmentShortlist(*out)
+
+    def shortlist_deep(self, queries, n, out=None, allow=None):
+        """shortlist() at DEPTH: 1 <= n <= SHORTLIST_DEEP_MAX = 1024, the width rerank / rerank_late (RERANK_MAX_CANDIDATES) and
+        Grounder.search(candidates=) (CANDIDATES_MAX) take -> Shortlist, or SegmentShortlist on a ragged table, on the device.  It is
+        the COARSE stage of a cascade: a pooled or quantised table that needs some hundreds of candidates before a fine rerank
+        recovers the recall (drn_amd.search_eval.evaluate_cascade(deep=True) says how many).  No new definition: shortlist_reference and
+        segment_shortlist_reference hold for any n, on a quantised table over mx8_dequantize(codes, scales).  Everything else is
+        shortlist()'s: queries, every field, the padding (-1 / 0 / -1), the total order, out= written in place, allow=, no host
+        synchronisation, graph capture once the shape is warmed (the workspace is kept per (S, n)), and the refusals.  A listed score
+        has the bits shortlist() gives it, a shorter deep list is a prefix of a longer one, and at n <= SHORTLIST_MAX every field
+        equals shortlist(queries, n)'s.
+
+        ONE entry for the four tables (drn_shortlist_deep): phase one is the masked shortlist's -- with allow=None under an all-ones
+        mask made once per table -- and one workgroup per sentence merges the blocks' lists (csrc/retrieve_deep.hip): two launches, three
+        on a ragged table.  That workgroup walks a sentence's lists in sequence, so a call of few sentences over many blocks is bound
+        by it.
+
+        What this is NOT: there is no shortlist_late at depth, and no ShardedShortlister.shortlist_deep -- a sharded corpus is
+        compact()ed into one table first."""
+        what = "Shortlister.shortlist_deep"
+        S, n = self._check_queries(what, queries, n=n, on_table=False, cap=SHORTLIST_DEEP_MAX)
+        seg = self._seg
+        if out is not None:
+            _check_list_out(what, out, S, n, rows=seg is not None)
+        if allow is not None:
+            self._check_allow(allow, S)
+        else:
+            allow = self._all_allowed()
+        if out is None:
+            out = _list_buffers(self._table().device, S, n, rows=seg is not None)
+        if seg is None:
+            ws = self._workspace(("deep", S, n), lambda: ops.shortlist_ws_keys(len(self), S, n))
+            ops.shortlist_deep(self._operand(), queries.contiguous(), (), n, ws, tuple(out), allow)
+            return Shortlist(*out)
+        ws = self._workspace(("deep", S, n), lambda: ops.shortlist_segments_ws_keys(self._nblocks(), S, n))
+        ops.shortlist_deep(self._operand(), queries.contiguous(), seg, n, ws, tuple(out), allow)
+        return SegmentShortlist(*out)
+
+    def _all_allowed(self):
+        """The packed mask that allows every video, (W,) int32 of -1 on the table's device, shared by all sentences: made once."""
+        ones = self._ws.get("all_allowed")
+        if ones is None:
+            ones = self._ws["all_allowed"] = torch.full((ops.allow_words(len(self)),), -1, dtype=torch.int32, device=self._table().device)
+        return ones
 
     def shortlist_late(self, queries, lengths, n, out=None, allow=None):
         """The shortlist by LATE INTERACTION (late_shortlist_reference defines it) -> Shortlist, on the device.  queries: contiguous

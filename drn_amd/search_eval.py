@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import SHORTLIST_MAX, DrnError
+from ._lib import SHORTLIST_DEEP_MAX, SHORTLIST_MAX, DrnError
 from .metrics import median_rank_from_ranks, mrr_from_ranks, recall_from_first_hits, recall_from_ranks
 from .store import _upload
 
@@ -62,7 +62,7 @@ def evaluate_shortlist(shortlister, batches, topks=(1, 10, 100, 1000), late=Fals
 
 
 @torch.no_grad()
-def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=False, allow=None):
+def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=False, allow=None, deep=False):
     """How deep must the COARSE stage of a cascade be?  coarse and fine: two Shortlisters over the same store positions -- either
     may be a ShardedShortlister, whose names and positions are the corpus's -- (coarse.names == fine.names, refused otherwise) -- a cheap table, pooled or quantised, and the table the second stage reranks.
     batches: an iterable of (names, coarse_queries, fine_queries) -- names[q] the video sentence q is annotated in -- or, with
@@ -72,14 +72,23 @@ def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=Fals
     1 <= depth <= SHORTLIST_MAX, refused otherwise; a topk > depth is legal and SATURATES: no rank reaches depth, so its recall is
     the recall at depth.  Names are resolved on the host before the batch's first launch, the rank is plain torch on the device, and
     the ranks are copied ONCE, after the last batch: nothing inside the loop waits for the device.  allow: None, or a packed mask
-    shared by all sentences, (W,), passed to both stages.  -> ShortlistRecall; no batches: n = 0 and recalls of 0."""
+    shared by all sentences, (W,), passed to both stages.  deep=True asks about a depth beyond SHORTLIST_MAX: 1 <= depth <=
+    SHORTLIST_DEEP_MAX, the coarse stage is coarse.shortlist_deep(coarse_queries, depth) -- a single Shortlister: a ShardedShortlister
+    has no shortlist_deep and is refused before any launch (compact() it first) -- the fine stage reranks to n = min(depth,
+    SHORTLIST_MAX), and a target's rank is its place in that list: a topk > n saturates in the same way.  -> ShortlistRecall; no
+    batches: n = 0 and recalls of 0."""
     topks, depth = [int(k) for k in topks], int(depth)
     if not topks:
         raise DrnError("evaluate_cascade: at least one top-k")
     if coarse.names is None or coarse.names != fine.names:
         raise DrnError("evaluate_cascade: the coarse and the fine table must carry the same names, position by position")
-    if not 1 <= depth <= SHORTLIST_MAX:
-        raise DrnError("evaluate_cascade: depth = %d outside [1, %d]" % (depth, SHORTLIST_MAX))
+    cap = SHORTLIST_DEEP_MAX if deep else SHORTLIST_MAX
+    if not 1 <= depth <= cap:
+        raise DrnError("evaluate_cascade: depth = %d outside [1, %d]" % (depth, cap))
+    if deep and not hasattr(coarse, "shortlist_deep"):
+        raise DrnError("evaluate_cascade: deep=True needs a single Shortlister as the coarse table; a ShardedShortlister has no "
+                       "shortlist_deep (compact() it into one table first)")
+    n = min(depth, SHORTLIST_MAX)
     where = {name: v for v, name in enumerate(fine.names)}
     dev, ranks = fine.device, []
     for batch in batches:
@@ -89,11 +98,11 @@ def evaluate_cascade(coarse, fine, batches, depth, topks=(1, 10, 100), late=Fals
                 raise DrnError("evaluate_cascade: the tables have no video named %s" % (name,))
             ids.append(where[name])
         targets = _upload(torch.tensor(ids, dtype=torch.int32), dev)
-        listed = coarse.shortlist(batch[1], depth, allow=allow).ids
+        listed = (coarse.shortlist_deep if deep else coarse.shortlist)(batch[1], depth, allow=allow).ids
         if late:
-            reranked = fine.rerank_late(listed, batch[2], batch[3], n=depth, allow=allow).ids
+            reranked = fine.rerank_late(listed, batch[2], batch[3], n=n, allow=allow).ids
         else:
-            reranked = fine.rerank(listed, batch[2], n=depth, allow=allow).ids
+            reranked = fine.rerank(listed, batch[2], n=n, allow=allow).ids
         hit = reranked == targets[:, None]
         ranks.append(torch.where(hit.any(dim=1), hit.int().argmax(dim=1), torch.full_like(targets, -1, dtype=torch.int64)).to(torch.int32))
     r = torch.cat(ranks).cpu().numpy() if ranks else np.zeros((0,), dtype=np.int32)

@@ -707,6 +707,22 @@ int drn_shortlist_segments_topn_q8_allow(const uint8_t* codes, const uint8_t* sc
                                          const int32_t* blk_vid, const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V,
                                          int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys, int32_t* ids, float* scores,
                                          int32_t* counts, int32_t* rows, void* stream);
+/* The DEEP shortlist (drn_amd/csrc/retrieve_allow.hip, the merge in drn_amd/csrc/retrieve_deep.hip): the four *_allow entries above
+ * behind one name, with 1 <= n <= DRN_SHORTLIST_DEEP_MAX = DRN_RERANK_MAX_CANDIDATES = DRN_CANDIDATES_MAX -- the width
+ * drn_shortlist_rerank and drn_plan_candidates take, so a coarse table can fill the second stage of a cascade.  table is emb, or the
+ * codes of a block-scaled FP8 table with scales beside them (scales == NULL: a plain table; E % 32 == 0 with scales); dtype is that of
+ * the queries.  offsets == NULL: one row per video -- blk_vid, vid_blk and rows must then be NULL too, and R and nblocks are ignored;
+ * otherwise all four are given, with the checks of drn_shortlist_segments_topn.  allow is REQUIRED: a packed mask with stride 0 or
+ * ceil(V / 32), 4-byte aligned (a caller without a filter passes one row of all-ones words with stride 0).  The definition, the
+ * scores' bits, the order, the padding and the clamps are the *_allow entries': at n <= DRN_SHORTLIST_MAX every field equals theirs.
+ * ws: ws_keys >= S * blocks * min(n, 256) 8-byte keys, times 1.5 on a ragged table, as the twins'.  Two launches on a plain table, three
+ * on a ragged one: the twin's phase one (a block holds at most 256 videos, so at n >= 256 its list is complete), one workgroup per
+ * sentence that merges the lists four at a time in 2 * CAP keys of LDS, CAP = 256 / 512 / 1024 the smallest >= n, and the twin's
+ * segment look-up.  No atomics, no host synchronisation; the queries and the mask may change between replays of a captured graph. */
+#define DRN_SHORTLIST_DEEP_MAX 1024
+int drn_shortlist_deep(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
+                       const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int n,
+                       int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
 /* The shortlist by LATE INTERACTION over a ragged table (drn_amd/csrc/retrieve_late.hip): queries [S][L][E] holds L token vectors a
  * sentence, lengths [S] int32 on the device says how many of them are live -- clamped into [0, L] on the device, never read on the host;
  * the contents of a token at or past it are not read.  sim[s][t][v] = drn_shortlist_segments_topn's score of (query row (s, t), video

@@ -2414,6 +2414,120 @@ def main_compact(args):
     print("wrote", out)
 
 
+DEEP_DEPTHS = (128, 256, 512, 1024)
+DEEP_LAYOUTS = (SEGMENT_LAYOUTS[0], SEGMENT_LAYOUTS[1])     # 65,536 x 1 as a plain table (no offsets), 4,096 x 16 ragged
+
+
+def bench_deep_shortlist(name, lens, emb, S, rounds):
+    """Shortlister.shortlist_deep on R = 65,536 rows: (a) at n = 128 beside shortlist(q, 128) on the same tensors, (b) at n = 256 / 512 /
+    1024, (c) at n = 1024 beside the parent's only way to the same list under the same order -- eight rounds of shortlist(q, 128,
+    allow=), each excluding the videos already listed by a device scatter into a bool mask and pack_allow -- and (d) torch.matmul (+ a
+    segmented amax) + torch.topk(1024), for orientation only.  Every field is asserted equal before timing."""
+    import numpy as np
+    from drn_amd import Shortlister, pack_allow
+    R, V = int(emb.shape[0]), len(lens)
+    ragged = V != R
+    off = np.concatenate([[0], np.cumsum(lens)])
+    assert off[-1] == R and V >= 1024
+    g = torch.Generator(device="cuda:0").manual_seed(S + 1024)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    sl = Shortlister(emb, offsets=off if ragged else None)
+    kind = type(sl.shortlist(q, 1))
+    out_s = kind(*sl.shortlist(q, 128))
+    out_d = {n: kind(*sl.shortlist_deep(q, n)) for n in DEEP_DEPTHS}
+    for f in kind._fields:
+        assert torch.equal(getattr(out_d[128], f), getattr(out_s, f)), (name, S, f, "deep 128 == shortlist 128")
+        for n in DEEP_DEPTHS[:-1]:
+            deep, part = getattr(out_d[1024], f), getattr(out_d[n], f)
+            assert torch.equal(deep[:, :n] if deep.dim() == 2 else deep.clamp(max=n), part), (name, S, n, f, "a prefix of the deep list")
+    mask = torch.ones((S, V), dtype=torch.bool, device="cuda:0")
+    words = pack_allow(mask)
+    out_r = [kind(*sl.shortlist(q, 128, allow=words)) for _ in range(8)]
+
+    def rounds8():
+        mask.fill_(True)
+        for r in range(8):
+            pack_allow(mask, out=words)
+            sl.shortlist(q, 128, out=out_r[r], allow=words)
+            if r < 7:
+                mask.scatter_(1, out_r[r].ids.long(), False)                  # (every list is full: V >= 1024 finite scores, asserted below)
+    rounds8()
+    assert bool((out_d[1024].n == 1024).all()) and all(bool((o.n == 128).all()) for o in out_r)
+    for f in kind._fields:
+        if f != "n":
+            assert torch.equal(torch.cat([getattr(o, f) for o in out_r], dim=1), getattr(out_d[1024], f)), (name, S, f, "eight rounds == deep 1024")
+    variants = {"shortlist_128": lambda: sl.shortlist(q, 128, out=out_s), "rounds8_1024": rounds8}
+    for n in DEEP_DEPTHS:
+        variants["deep_%d" % n] = lambda n=n: sl.shortlist_deep(q, n, out=out_d[n])
+    if ragged:
+        index = torch.repeat_interleave(torch.arange(V, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(S, R).contiguous()
+        best = torch.empty((S, V), dtype=torch.bfloat16, device="cuda:0")
+
+        def torch_way():
+            best.fill_(float("-inf"))
+            best.scatter_reduce_(1, index, torch.matmul(q, emb.t()), "amax")
+            return torch.topk(best, 1024, dim=1)
+    else:
+        torch_way = lambda: torch.topk(torch.matmul(q, emb.t()), 1024, dim=1)
+    variants["torch_1024"] = torch_way
+    times, reps = interleaved_windows(variants, rounds)
+    med = {k: statistics.median(ts) for k, ts in times.items()}
+    c, d = times["rounds8_1024"], times["deep_1024"]
+    over = med["deep_1024"] - med["rounds8_1024"]
+    table = emb.numel() * emb.element_size()
+    row = {"layout": name, "R": R, "V": V, "E": 512, "S": S, "dtype": "bf16", "blocks": sl._nblocks(), "launches_per_window": reps,
+           "table_once_us_at_8.0TB/s": table / HBM_PEAK_BYTES_PER_S * 1e6,
+           "a": {"shortlist_128_us": spread(times["shortlist_128"]), "deep_128_us": spread(times["deep_128"]),
+                 "deep_128_over_shortlist_128": med["deep_128"] / med["shortlist_128"],
+                 "deep_128_against_shortlist_128": verdict(times["deep_128"], times["shortlist_128"])},
+           "b": {"deep_%d_us" % n: spread(times["deep_%d" % n]) for n in DEEP_DEPTHS[1:]},
+           "c": {"eight_rounds_us": spread(c), "deep_1024_over_eight_rounds": med["deep_1024"] / med["rounds8_1024"],
+                 "deep_1024_minus_eight_rounds_us": over, "eight_rounds_max_minus_min_us": max(c) - min(c), "holds": over <= max(c) - min(c),
+                 "deep_1024_against_eight_rounds": verdict(d, c)},
+           "d": {"matmul_topk_1024_us": spread(times["torch_1024"]), "deep_1024_over_matmul_topk": med["deep_1024"] / med["torch_1024"],
+                 "deep_1024_against_matmul_topk": verdict(d, times["torch_1024"])},
+           "note": "launch-inclusive, every launch of a call: two (three on the ragged layout) for shortlist and shortlist_deep; the eight "
+                   "rounds are a fill, eight pack_allow, eight masked shortlists and seven scatters; torch scores in bf16 with no defined tie "
+                   "order: another answer, for orientation"}
+    return row
+
+
+def main_deep_shortlist(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_deep_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "baselines": "(a) shortlist(q, 128) on the same tensors; (c) eight rounds of shortlist(q, 128, allow=), each excluding "
+                                   "the videos already listed (device scatter into a bool mask + pack_allow), the concatenation asserted equal "
+                                   "to shortlist_deep(q, 1024) field for field before timing; (d) torch.matmul + torch.topk(1024).  A "
+                                   "difference inside the baseline's own max - min is NO DIFFERENCE",
+                      "condition": "derived, not measured: (c) reads the table eight times and runs eight merges and eight packs, so "
+                                   "shortlist_deep at n = 1024 may not take longer than (c) beyond (c)'s max - min.  No number gates the change",
+                      "what_this_does_not_say": "random embeddings: nothing here says anything about recall, or about what depth a coarse stage "
+                                                "needs; bf16 only: no fp32, no FP8 tables, no masks; no kernel-only times (no profiler run); "
+                                                "the two-level merge is not built, so nothing says what it would save at S = 1"},
+           "deep_shortlist": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for name, lens in DEEP_LAYOUTS:
+            row = bench_deep_shortlist(name, lens, emb, S, args.rounds)
+            res["deep_shortlist"].append(row)
+            print(json.dumps({"deep_shortlist": row}), flush=True)
+            print("(a) %s S = %d: deep 128 / shortlist 128 = %.3f (%s)" % (name, S, row["a"]["deep_128_over_shortlist_128"],
+                                                                         row["a"]["deep_128_against_shortlist_128"]), flush=True)
+            print("(c) %s S = %d: %s (deep 1024 / eight rounds = %.3f)" % (name, S, "HOLDS" if row["c"]["holds"] else "MISSED",
+                                                                          row["c"]["deep_1024_over_eight_rounds"]), flush=True)
+            print("(d) %s S = %d: deep 1024 / matmul + topk = %.3f (%s)" % (name, S, row["d"]["deep_1024_over_matmul_topk"],
+                                                                          row["d"]["deep_1024_against_matmul_topk"]), flush=True)
+            json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -2453,9 +2567,14 @@ def main():
     ap.add_argument("--compact", action="store_true", help="measure ShardedShortlister.compact beside dequantise + torch.cat + index_select + "
                                                            "Shortlister on the same shards, the rows launches' bytes per second, and "
                                                            "what the compacted table buys against K = 16 shards under the same mask")
+    ap.add_argument("--deep-shortlist", action="store_true", help="measure Shortlister.shortlist_deep at n = 128 / 256 / 512 / 1024 beside "
+                                                                  "shortlist() at 128, eight masked rounds of it and matmul + topk "
+                                                                  "(writes profiles/search_deep_shortlist_bench.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.deep_shortlist:
+        return main_deep_shortlist(args)
     if args.compact:
         return main_compact(args)
     if args.sharded_rank:
