@@ -7,9 +7,9 @@ from .grounding import Grounder, Hits, Moments, group_by_video, plan_candidate_s
 from .store import FeatureStore, StoreLoader  # noqa: E402,F401
 from .index import SearchIndex  # noqa: E402,F401
 from .search_eval import SearchRecall, ShortlistRecall, evaluate_cascade, evaluate_search, evaluate_shortlist, search_batches  # noqa: E402,F401
-from .retrieve import (LATE_MAX_TOKENS, SHARDS_MAX, SHORTLIST_DEEP_MAX, Compacted, compact_reference, SegmentShortlist, ShardedShortlister, Shortlist, Shortlister, TargetRank,  # noqa: E402,F401
+from .retrieve import (LATE_MAX_TOKENS, SHARDS_MAX, SHORTLIST_DEEP_MAX, Compacted, Pooled, compact_reference, SegmentShortlist, ShardedShortlister, Shortlist, Shortlister, TargetRank,  # noqa: E402,F401
                        candidates_mask, late_rank_reference, late_rerank_reference, late_shortlist_reference, merge_shortlists_reference,
-                       pack_allow, pack_allow_reference, plan_segment_blocks, rank_reference, rank_thresholds_reference, rerank_reference,
+                       pack_allow, pack_allow_reference, plan_segment_blocks, pool_offsets, pool_segments_reference, rank_reference, rank_thresholds_reference, rerank_reference,
                        segment_rank_reference,
                        segment_rerank_reference, segment_shortlist_reference, shard_positions_reference, shortlist_reference,
                        slice_allow_reference)

@@ -5,6 +5,7 @@ libdrn_hip.so call on torch's current HIP stream.  Missing library or a non-zero
 return code raises (no fallback).
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -2110,6 +2111,69 @@ def compact_rows(src, src_offsets, positions, dst_offsets, dst_videos, dst, dst_
         _p(s), _p(s_scales), _p(src_offsets), _p(positions), _p(dst_offsets), V, src_rows, E, int(s_scales is not None), int(d_scales is not None),
         code, dst_videos, dst_row0, dst_rows, _p(d), _p(d_scales), _stream()), "drn_compact_rows"))
     return dst
+
+
+POOL_HOW = {"mean": 0, "max": 1}     # DRN_POOL_MEAN / DRN_POOL_MAX
+
+
+def pool_args(what, how, group):
+    """how= and group= of a pooling, for every caller (pool_segments, drn_amd.retrieve) -> group as None or a Python integer >= 1;
+    anything else raises."""
+    if not isinstance(how, str) or how not in POOL_HOW:
+        raise _lib.DrnError("%s: how must be one of %s, not %r" % (what, tuple(POOL_HOW), how))
+    if group is None:
+        return None
+    if isinstance(group, bool) or not isinstance(group, numbers.Integral) or not 1 <= int(group) < 2 ** 31:
+        raise _lib.DrnError("%s: group must be None (one row a video) or an integer in [1, 2^31), not %r" % (what, group))
+    return int(group)
+
+
+def pool_segments(table, offsets, out, how="mean", group=None, out_offsets=None, out_row0=0):
+    """POOL the segments of a ragged table into plain rows (drn_pool_segments; drn_amd.retrieve.pool_segments_reference is the
+    definition, bit for bit).  table: the plain (R, E) rows, float32 / bfloat16, or the pair (codes, scales) of a block-scaled FP8
+    table; offsets (V + 1,) int32 on the device, the table's own.  out: (rows, E) PLAIN rows of the table's dtype -- with a pair it
+    is out's dtype that says how the values are dequantised --, written in place, every element: the pooled table's rows
+    [out_row0, out_row0 + rows), the whole of it or a staging buffer's chunk.  how: "mean" (an fp32 sum in ascending row order, one
+    division, one rounding) or "max" (ascending, x > acc ? x : acc).  group None: one row a video, out_offsets None, out_row0 + rows
+    <= V, and a video without rows gives a row of +0; group = g >= 1: one row per g rows of a video, out_offsets (V + 1,) int32 on the
+    device, the pooled table's own offsets (ceil(len_v / g) rows a video), which the CALLER made.  One launch (tag pool_segments);
+    nothing is read on the host."""
+    what = "pool_segments"
+    q8 = isinstance(table, (tuple, list))
+    t, scales = (table[0], table[1]) if q8 else (table, None)
+    for x in (t, scales, offsets, out, out_offsets):
+        if x is not None and not torch.is_tensor(x):
+            raise _lib.DrnError("%s: the table, the offsets and out must be tensors" % what)
+    _need_gpu(t, scales, offsets, out, out_offsets)
+    group = pool_args(what, how, group)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or not t.is_contiguous():
+        raise _lib.DrnError("%s: the table must be a contiguous (R, E) tensor with R >= 1 and E >= 1, not %s" % (what, tuple(t.shape)))
+    R, E = (int(x) for x in t.shape)
+    if q8:
+        if t.dtype != torch.uint8 or scales.dtype != torch.uint8 or E % 32 or tuple(scales.shape) != (R, E // 32) or not scales.is_contiguous():
+            raise _lib.DrnError("%s: a quantised table is codes (R, E) and scales (R, E / 32), contiguous uint8 tensors with E a multiple "
+                                "of 32" % what)
+    elif t.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.DrnError("%s: a plain table must be float32 or bfloat16, not %s" % (what, t.dtype))
+    if out.dtype not in (torch.float32, torch.bfloat16) or (not q8 and out.dtype != t.dtype):
+        raise _lib.DrnError("%s: out must be float32 or bfloat16, and of a plain table's dtype, not %s" % (what, out.dtype))
+    if out.dim() != 2 or out.shape[0] < 1 or int(out.shape[1]) != E or not out.is_contiguous():
+        raise _lib.DrnError("%s: out must be a contiguous (rows, %d) tensor with rows >= 1, not %s" % (what, E, tuple(out.shape)))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+        raise _lib.DrnError("%s: offsets must be a contiguous (V + 1,) torch.int32 tensor with V >= 1" % what)
+    V, rows, out_row0 = int(offsets.numel()) - 1, int(out.shape[0]), int(out_row0)
+    if (group is None) != (out_offsets is None):
+        raise _lib.DrnError("%s: out_offsets must be given exactly with group= (group=None: one row a video)" % what)
+    if out_offsets is not None and (out_offsets.dtype != torch.int32 or tuple(out_offsets.shape) != (V + 1,) or not out_offsets.is_contiguous()):
+        raise _lib.DrnError("%s: out_offsets must be a contiguous (%d,) torch.int32 tensor" % (what, V + 1))
+    if out_row0 < 0 or out_row0 + rows > (V if group is None else R):
+        raise _lib.DrnError("%s: out holds the pooled rows [%d, %d), outside [0, %d]%s"
+                            % (what, out_row0, out_row0 + rows, V if group is None else R,
+                               " (one row a video)" if group is None else " (a group holds at least one of the R rows)"))
+    _timed(what, 0.0, lambda: check(lib().drn_pool_segments(
+        _p(t), _p(scales), _p(offsets), _p(out_offsets), R, V, rows, out_row0, E, 0 if group is None else group, POOL_HOW[how],
+        dtype_code(out), _p(out), _stream()), "drn_pool_segments"))
+    return out
 
 
 def shortlist_sharded_rank_ws_keys(blocks, S):

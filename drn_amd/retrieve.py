@@ -68,7 +68,14 @@ new positions and new offsets with a carry that runs from shard to shard; after 
 names, the new offsets for the block plan: no table data) drn_compact_rows, once per shard, moves the kept rows: plain rows and FP8
 codes and scales as they are, FP8 rows dequantised exactly where the target is plain; plain rows on their way to FP8 cross a bounded
 staging buffer into ops.quantize_rows_mx8, the one quantiser.  Where nothing is quantised the new table answers every method bit for
-bit as the shards do under allow=keep, positions mapped."""
+bit as the shards do under allow=keep, positions mapped.
+
+Shortlister.pooled and ShardedShortlister.pooled are the fourth verb: a CHEAPER table over the same videos, made on the device from the
+ragged table the caller owns -- one row a video (group=None) or one row per g rows of a video (group=g), the mean or the maximum, from a
+plain or an FP8 table into either format.  pool_segments_reference is the definition, bit for bit: an fp32 sum in ascending row order,
+one IEEE division, one rounding; drn_pool_segments (csrc/retrieve_pool.hip) the launch, one wavefront per pooled row and column slab.
+Store positions and names are unchanged, so the pooled table is the `coarse` of evaluate_cascade beside its source as `fine`; with
+group=None a video without rows is a row of zeros and table.nonempty the mask that keeps it off the lists."""
 import collections
 import numbers
 
@@ -542,6 +549,12 @@ def _allow_of(what, names, V, dev, keep, drop):
         else:
             raise DrnError("%s: an entry must be a name or a position, not %r" % (what, item))
         mask[v] = drop is None
+    return _mask_words(mask, dev)
+
+
+def _mask_words(mask, dev):
+    """A HOST bool mask over the videos -> its packed words on dev: packed on the host (pack_allow_reference), ONE upload from pinned
+    memory.  The tail of allow_of, and how pooled() makes nonempty from the offsets it holds on the host."""
     words = torch.from_numpy(pack_allow_reference(mask))
     if dev.type != "cuda":                    # (a table that is not on a GPU can be asked for its mask, never for a shortlist)
         return words
@@ -606,6 +619,86 @@ def quantized_score_bound(embeddings, scales, queries):
     return q.abs() @ per.t() + E * 2.0 ** -23 * (q.abs() @ x.abs().t())
 
 
+Pooled = collections.namedtuple("Pooled", "rows offsets")
+Pooled.__doc__ = """rows (R', E): the pooled rows in the table's dtype, on the HOST; offsets: None with group=None (row v is video v), else the pooled
+table's own offsets, V + 1 int64 in a numpy array."""
+
+def pool_offsets(offsets, group):
+    """The offsets of a pooled table from the source's host offsets (V + 1 integers): a video of len_v rows keeps ceil(len_v / group)
+    -> V + 1 int64 (a video without rows keeps none); group=None -> None: the pooled table has one row a video and no offsets."""
+    if group is None:
+        return None
+    lens = np.diff(np.asarray(offsets, dtype=np.int64))
+    return np.concatenate([[0], np.cumsum(-(-lens // int(group)))]).astype(np.int64)
+
+
+def pool_segments_reference(embeddings_or_shortlister, offsets=None, how="mean", group=None):
+    """THE DEFINITION of Shortlister.pooled, in plain torch and numpy, EVALUATED ON THE HOST whatever device the inputs live on (so that
+    every add and the division are IEEE fp32, whatever a device's kernels do) -> Pooled(rows, offsets).  embeddings_or_shortlister: the
+    (R, E) segment rows, float32 or bfloat16, with offsets (V + 1 non-decreasing integers from 0 to R); or a ragged Shortlister -- or
+    an object that stands in for one --, whose offsets are taken when offsets is None and whose values are its embeddings or, on a
+    quantised table, mx8_dequantize(codes, scales, dtype), which is exact.
+
+    The rows: a video of len_v = offsets[v + 1] - offsets[v] rows becomes ceil(len_v / group) rows, row j of video v pooling the source
+    rows offsets[v] + j * group .. min(offsets[v] + (j + 1) * group, offsets[v + 1]) - 1; a video without rows keeps none, and the
+    result's offsets are the running sums.  group=None pools a whole video into ONE row and gives a plain (V, E) table without
+    offsets; row v of a video without rows is all +0.
+
+    how="mean": an fp32 accumulator that starts at +0; the group's rows added in ASCENDING row order, one plain fp32 add a row --
+    ((0 + r0) + r1) + ... --; ONE IEEE fp32 division by float(count); ONE rounding to the table's dtype, to nearest even.  The order
+    holds by construction: step i adds row i of every group that has one (a masked add), for i below the longest group -- there is no
+    torch.sum and no torch.mean here, whose order nobody states.
+    how="max": acc = the group's first row, then, in ascending row order, acc = where(row > acc, row, acc): the element-wise
+    maximum, exact in any order -- and of two zeros of different sign, which compare equal, the EARLIER row's (a block-scaled FP8
+    table holds both).  Only finite inputs are defined; tables hold no others.
+    (So group=1 returns the source's values: bit for bit under "max"; under "mean" bit for bit EXCEPT a -0, which comes back as
+    0 + -0 = +0 -- an FP8 table holds such zeros as a matter of course, and a plain table may: its constructor asks for finite values
+    only.)"""
+    what = "pool_segments_reference"
+    group = ops.pool_args(what, how, group)
+    src = embeddings_or_shortlister
+    if torch.is_tensor(src):
+        x = src
+        if offsets is None:
+            raise DrnError("%s: rows need their offsets" % what)
+    else:
+        if getattr(src, "_seg", None) is None:
+            raise DrnError("%s: the table has no offsets: it is one row a video already" % what)
+        x = src.embeddings if src.quantize is None else mx8_dequantize(src.codes.detach().cpu(), src.scales.detach().cpu(), src.dtype)
+        if offsets is None:
+            offsets = src._seg[0]
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() != 2:
+        raise DrnError("%s: the rows must be a (R, E) bfloat16 or float32 tensor, not %s %s" % (what, x.dtype, tuple(x.shape)))
+    dtype = x.dtype
+    vals = x.detach().cpu().float()                         # (exact)
+    R, E = (int(n) for n in vals.shape)
+    off = check_segment_offsets(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets, R)
+    lens = np.diff(off)
+    if group is None:
+        out_off, starts, counts = None, off[:-1].copy(), lens.copy()
+    else:
+        out_off = pool_offsets(off, group)
+        per = np.diff(out_off)
+        within = np.arange(int(out_off[-1]), dtype=np.int64) - np.repeat(out_off[:-1], per)
+        starts = np.repeat(off[:-1], per) + within * group
+        counts = np.minimum(group, np.repeat(off[1:], per) - starts)
+    acc = torch.zeros((len(starts), E), dtype=torch.float32)
+    for i in range(int(counts.max()) if len(counts) else 0):
+        live = torch.from_numpy(np.nonzero(counts > i)[0])
+        row = vals[torch.from_numpy(starts[counts > i] + i)]
+        if how == "mean":
+            acc[live] = acc[live] + row
+        elif i == 0:
+            acc[live] = row
+        else:
+            old = acc[live]
+            acc[live] = torch.where(row > old, row, old)
+    if how == "mean":
+        live = torch.from_numpy(np.nonzero(counts > 0)[0])
+        acc[live] = acc[live] / torch.from_numpy(counts[counts > 0]).to(torch.float32)[:, None]
+    return Pooled(acc.to(dtype), out_off)
+
+
 class Shortlister(object):
     """Shortlister(embeddings, names=None, offsets=None, quantize=None): a (V, E) table of video embeddings, row v belonging to store position v -- a
     contiguous CUDA tensor, bfloat16 or float32, V >= 1 and E >= 1, kept by reference.  Non-finite embeddings are refused here (ONE
@@ -630,6 +723,9 @@ class Shortlister(object):
     table; nbytes, the bytes of the table held (= bytes_of(rows, E, dtype, quantize))."""
 
     quantize = codes = scales = _dtype = _seg = None     # (what a plain table has; also for an object made without the constructor)
+    _off_host = None                                     # (a ragged table's offsets as the constructor's check left them on the host)
+    nonempty = None                                      # (pooled(group=None) sets it on its result: the mask of the videos that own a row)
+    _owners = None                                       # (the same on the host, a bool array (V,); None: every video owns a row)
 
     def __init__(self, embeddings, names=None, offsets=None, quantize=None):
         if quantize not in QUANTIZE:
@@ -728,6 +824,7 @@ class Shortlister(object):
         self.plan = plan
         self._seg = (put(off), put(plan.blk_vid), put(plan.vid_blk))
         self.offsets = self._seg[0]
+        self._off_host = off
 
     def _table(self):
         """The tensor that has the table's rows, columns and device: the embeddings, or the codes of a quantised table."""
@@ -789,6 +886,90 @@ class Shortlister(object):
             return self
         return Shortlister(mx8_dequantize(self.codes, self.scales, self._dtype), names=self.names,
                            offsets=None if self._seg is None else self._seg[0])
+
+    def _host_offsets(self):
+        """A ragged table's offsets on the host, V + 1 int64: what the constructor's check left there; an object made without the
+        constructor reads them back from the device once (a synchronise) and keeps them."""
+        if self._off_host is None:
+            self._off_host = self._seg[0].detach().cpu().numpy().astype(np.int64)
+        return self._off_host
+
+    def pooled(self, how="mean", group=None, quantize="same", stage_elems=None):
+        """POOL this ragged table's segments into a COARSE table over the same videos, on the device -> a new Shortlister;
+        pool_segments_reference is the definition, byte for byte.  The cheap first stage of a cascade, made from the one table the
+        caller owns: coarse = fine.pooled(); evaluate_cascade(coarse, fine, ..., allow=coarse.nonempty).
+
+        group=None pools every video into ONE row: the result is a plain (V, E) table WITHOUT offsets (shortlist() returns a
+        Shortlist).  group=g >= 1 pools every g consecutive rows of a video (the last group of a video may be shorter): the result is
+        ragged, a video of len_v rows owning ceil(len_v / g) -- its offsets are pool_offsets(self offsets, g), a video without rows
+        keeps none -- and pooled row r of video v starts at source row offsets_src[v] + (r - offsets_pooled[v]) * g: that is the map
+        back from the `rows` of its SegmentShortlist (segment j of the pooled video covers the source segments j * g .. j * g + g - 1).
+        how="mean": fp32 sum in ascending row order, one division, one rounding; how="max": the element-wise maximum.  The rows are
+        NOT normalised.  names are carried over and len() is unchanged: store positions are the source's, so the result is a legal
+        `coarse` beside this table as `fine`.  This table is not modified and the result owns its memory.
+
+        A VIDEO WITHOUT ROWS, with group=None, becomes a row of ZEROS.  A zero row scores 0 against every query and IS A CANDIDATE: it
+        is listed, ahead of every video with a negative score, unless the caller passes allow=table.nonempty.  nonempty is the packed
+        (W,) allow mask of the videos that own a row, on the device (what allow_of(keep=those videos) returns, made the same way from
+        the host offsets), and None when every video owns one -- so allow=table.nonempty is always right.  With group=g the videos
+        without rows own none in the result either and are never listed; nonempty is None.
+
+        quantize: the format of the result -- "same" (the default) keeps this table's, None gives plain rows in self.dtype, "mxfp8"
+        block-scaled FP8 (E % 32 == 0, refused otherwise).  The kernel always writes PLAIN rows (a quantised source is dequantised in
+        registers, exactly); an FP8 result is those rows run through ops.quantize_rows_mx8, the one quantiser, crossing a staging
+        buffer of at most stage_elems elements (COMPACT_STAGE_ELEMS when None) in chunks of stage_elems // E rows: the result is
+        mx8_quantize(pool_segments_reference(...).rows) byte for byte, whatever the chunks.
+
+        One drn_pool_segments launch (per chunk, beside one quantiser launch, for an FP8 result); the new offsets and block plan are
+        made on the host from the offsets the constructor already checked there.  It synchronises ONCE, at the end, for the result's
+        finiteness -- an fp32 sum can overflow, and a table that is not finite raises here as the constructor would -- and cannot be
+        captured in a graph.  A plain table (no offsets=) is refused: it is one row a video already."""
+        what = "Shortlister.pooled"
+        group = ops.pool_args(what, how, group)
+        if self._seg is None:
+            raise DrnError("%s: this table has no offsets=: it is one row a video already, and there is nothing to pool" % what)
+        target = _compact_target(what, [self], quantize, self.E)
+        return self._pooled(what, how, group, target, stage_elems)
+
+    def _pooled(self, what, how, group, target, stage_elems):
+        """pooled() behind its refusals of how, group and quantize (ShardedShortlister.pooled pools its shards through it)."""
+        table, E, dtype = self._table(), self.E, self.dtype
+        if not table.is_cuda:
+            raise DrnError("%s: the table must be on the GPU; there is no CPU fallback (pool_segments_reference is the definition)" % what)
+        stage_elems = COMPACT_STAGE_ELEMS if stage_elems is None else int(stage_elems)
+        if stage_elems < 1:
+            raise DrnError("%s: stage_elems = %d below 1" % (what, stage_elems))
+        dev = table.device
+        off = self._host_offsets()
+        lens = np.diff(off)
+        out_off = pool_offsets(off, group)
+        rows = len(lens) if group is None else int(out_off[-1])
+        out_off_dev = None
+        if out_off is not None:
+            out_off_dev = torch.from_numpy(out_off.astype(np.int32))
+            if dev.type == "cuda":
+                out_off_dev = out_off_dev.pin_memory().to(dev, non_blocking=True)
+        if target is None:
+            dst = torch.empty((rows, E), dtype=dtype, device=dev)
+            ops.pool_segments(self._operand(), self._seg[0], dst, how, group, out_off_dev)
+            finite = torch.isfinite(dst).all()
+        else:
+            dst = (torch.empty((rows, E), dtype=torch.uint8, device=dev), torch.empty((rows, E // MX8_BLOCK), dtype=torch.uint8, device=dev))
+            step = max(1, stage_elems // E)
+            stage = torch.empty((min(step, rows), E), dtype=dtype, device=dev)
+            finite = torch.ones((), dtype=torch.bool, device=dev)
+            for r0 in range(0, rows, step):
+                r1 = min(r0 + step, rows)
+                ops.pool_segments(self._operand(), self._seg[0], stage[:r1 - r0], how, group, out_off_dev, out_row0=r0)
+                finite = finite & torch.isfinite(stage[:r1 - r0]).all()
+                ops.quantize_rows_mx8(stage[:r1 - r0], dst[0][r0:r1], dst[1][r0:r1])
+        owners = lens > 0 if group is None and bool((lens == 0).any()) else None
+        nonempty = None if owners is None else _mask_words(owners, dev)
+        if not bool(finite):                          # THE one synchronise
+            raise DrnError("%s: the pooled rows hold values that are not finite (an fp32 sum overflowed)" % what)
+        out = _trusted_table(dst, dtype, None if self.names is None else list(self.names), out_off)
+        out.nonempty, out._owners = nonempty, owners
+        return out
 
     def __len__(self):
         return int(self._table().shape[0]) if self._seg is None else int(self._seg[0].shape[0]) - 1
@@ -1183,6 +1364,7 @@ def _trusted_table(rows, dtype, names, offsets):
         self.plan = plan
         self._seg = (put(off), put(plan.blk_vid), put(plan.vid_blk))
         self.offsets = self._seg[0]
+        self._off_host = off
     return self
 
 
@@ -1303,6 +1485,8 @@ class ShardedShortlister(object):
     compact(keep) is the third verb beside append() and allow_of(drop=): ONE new table over the videos a mask keeps, built on the
     device, for when the shard count or the tombstone list has grown (a single table is the faster one to query)."""
 
+    nonempty = None                              # (the corpus mask of the videos that own a row, over shards made by pooled(group=None): _placed)
+
     def __init__(self, shards):
         try:
             shards = list(shards)
@@ -1351,6 +1535,12 @@ class ShardedShortlister(object):
         dev = self.device
         self.bases_device = bases if dev.type != "cuda" else bases.pin_memory().to(dev, non_blocking=True)
         self.blk_off_device = blk_off if dev.type != "cuda" else blk_off.pin_memory().to(dev, non_blocking=True)
+        # nonempty follows the shards: where a shard came from pooled(group=None) with videos that own no row, the corpus's mask is the
+        # shards' host masks side by side (a shard without one allows all its videos), made again after every append
+        self.nonempty = None
+        if any(shard._owners is not None for shard in self.shards):
+            owners = [np.ones(len(shard), dtype=np.bool_) if shard._owners is None else shard._owners for shard in self.shards]
+            self.nonempty = _mask_words(np.concatenate(owners), dev)
 
     def append(self, shard):
         """One more shard at the end of the corpus -- the same checks as the constructor, before anything changes -- at the positions
@@ -1495,6 +1685,25 @@ class ShardedShortlister(object):
             else:
                 ops.compact_rows(src, src_off, positions[a:b], new_off, kept, dst, dtype=dtype)
         return Compacted(_trusted_table(dst, dtype, names, offsets), positions, kept)
+
+    def pooled(self, how="mean", group=None, quantize="same", stage_elems=None):
+        """Shortlister.pooled over the CORPUS -> a new ShardedShortlister of the shards' pooled tables, shard by shard: the same
+        arguments, definition (pool_segments_reference of each shard; a group never crosses a video, so never a shard), refusals and
+        launches, and one synchronise a shard.  The video counts, bases and names are unchanged, so the result is a legal `coarse`
+        beside this corpus as `fine`, and it answers shortlist() bit for bit like the pooled() of ONE table over the concatenated
+        rows.  quantize="same" keeps every shard's own format and is refused on mixed shards, as compact() refuses it; None or
+        "mxfp8" gives every shard that format.  nonempty, with group=None, is the packed (W,) mask OVER THE CORPUS of the videos that
+        own a row (what allow_of(keep=those videos) returns), None when every video owns one: a video without rows is a row of
+        ZEROS there, scores 0 and IS a candidate unless allow=result.nonempty is passed.  Every shard of the result carries its own
+        nonempty over its own videos, and the corpus's is put together from the shards' whenever the shards change: after
+        result.append(new_shard.pooled()) it covers the new videos too (a NEW tensor: read result.nonempty again after an append; a
+        shard that did not come from pooled() allows all its videos).  The shards must be ragged."""
+        what = "ShardedShortlister.pooled"
+        group = ops.pool_args(what, how, group)
+        if self.shards[0]._seg is None:
+            raise DrnError("%s: the shards have no offsets=: they are one row a video already, and there is nothing to pool" % what)
+        target = _compact_target(what, self.shards, quantize, self.E)
+        return ShardedShortlister([shard._pooled(what, how, group, target, stage_elems) for shard in self.shards])
 
     def _lists(self, S, n):
         """The stacked per-shard lists of this (K, S, n): slices along dim 0 are contiguous, legal out= buffers of the shards."""

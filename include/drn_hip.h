@@ -887,6 +887,27 @@ int drn_compact_plan(const int32_t* keep, const int32_t* offsets, int V, int k, 
 int drn_compact_rows(const void* src, const uint8_t* src_scales, const int32_t* src_offsets, const int32_t* positions,
                      const int32_t* dst_offsets, int V, int src_rows, int E, int src_format, int dst_format, int dtype, int dst_videos,
                      int dst_row0, int dst_rows, void* dst, uint8_t* dst_scales, void* stream);
+/* POOLING A RAGGED TABLE'S SEGMENTS INTO A COARSE TABLE (drn_amd/csrc/retrieve_pool.hip; drn_amd.retrieve.pool_segments_reference is the
+ * definition, bit for bit).  table is the plain rows [R][E] in `dtype`, or the codes [R][E] u8 of a block-scaled FP8 table with scales
+ * [R][E / 32] beside them (scales == NULL: a plain table; E % 32 == 0 with scales); offsets [V + 1] the table's own.  out [R_out][E] is
+ * ALWAYS plain rows in `dtype` (a caller that wants FP8 runs drn_quantize_rows_mx8, the one quantiser, over them) and a WINDOW of the
+ * pooled table: its rows [out_row0, out_row0 + R_out) -- the whole table with out_row0 = 0, or a staging buffer's chunk of it.
+ *   group == 0, out_offsets == NULL: one row a video, out_row0 + R_out <= V; row v pools the rows offsets[v] .. offsets[v + 1] - 1, and a video
+ *     without rows gives a row of +0;
+ *   group = g >= 1, out_offsets [V + 1] given: video v owns the output rows out_offsets[v] .. out_offsets[v + 1] - 1 (the caller made
+ *     them: ceil(len_v / g) each, running sums from 0), and its row j pools the source rows offsets[v] + j g .. + g - 1, cut at
+ *     offsets[v + 1].
+ * how = DRN_POOL_MEAN: an fp32 accumulator from +0, the group's rows added in ASCENDING row order, one fp32 add a row, one correctly
+ * rounded fp32 division by float(count), one rounding to `dtype` (nearest even); DRN_POOL_MAX: the first row, then acc = x > acc ? x :
+ * acc in ascending order -- the maximum, exact, and of two zeros of either sign the earlier row's.  A source value of an FP8 table is
+ * float(code) * 2^(scale - 127), exact.  So a row's bits depend on its group's rows alone, not on V, the grid or the other videos.
+ * The table and out are 16-byte aligned, 1 <= R_out < 2^31; every index read from offsets and out_offsets is clamped, and nothing is
+ * written outside out's R_out * E elements, every one of which is.  One launch: one wavefront per (output row, slab of 512 bf16 / 256
+ * fp32 columns), so few videos with very long runs fill little of the chip.  No atomics, no LDS, no workspace, nothing read on the host. */
+#define DRN_POOL_MEAN 0
+#define DRN_POOL_MAX 1
+int drn_pool_segments(const void* table, const uint8_t* scales, const int32_t* offsets, const int32_t* out_offsets, int R, int V, int R_out,
+                      int out_row0, int E, int group, int how, int dtype, void* out, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

@@ -140,7 +140,15 @@
            byte before timing.  (G1) compact() takes less than the route by more than the route's own max - min: HOLDS / DOES NOT HOLD
            per shape, no absolute time required.  Without a bar: the rows launches' bytes per second (bytes from the shapes, device
            events around each launch: launch-inclusive) against the HBM peak, and shortlist and rank at S = 8, n = 16 on the compacted
-           table beside the K = 16 sharded object under the same mask."""
+           table beside the K = 16 sharded object under the same mask.
+
+  --pooled   instead of the above -> profiles/search_pooled_bench.json: Shortlister.pooled(how="mean") with group=None and group=4 on
+           65,536 rows x 512 bf16 as 4,096 videos x 16 and as 5,120 videos of 1 / 3 / 0 / 17 / 43 rows, from a bf16 and from an FP8
+           table (target "same"), beside the parent's only way to such a table, in torch on the device -- (mx8_dequantize,) an fp32
+           index_add_, a divide, a cast, Shortlister(...) -- by a host clock to a device synchronise, the two taking turns in every
+           round, every field asserted equal to pool_segments_reference (evaluated on the host) before timing.  The condition:
+           pooled() takes no longer than that route beyond the route's own max - min, HOLDS / DOES NOT HOLD per shape, no absolute
+           time required.  For orientation only: the bytes read and written over 8 TB/s."""
 import argparse
 import json
 import os
@@ -2528,6 +2536,110 @@ def main_deep_shortlist(args):
     print("wrote", out)
 
 
+POOLED_LAYOUTS = (SEGMENT_LAYOUTS[1], ("5120x(1,3,0,17,43)", [1, 3, 0, 17, 43] * 1024))     # R = 65,536 each: 4,096 x 16, and an unequal one
+
+
+def pooled_route(sl, index, counts, rows_out, out_off):
+    """The way to a pooled table WITHOUT pooled(), in torch on the device: (dequantise,) an fp32 index_add_ -- whose add order nobody
+    states --, a divide, a cast, and a fresh Shortlister, whose constructor reads the result again for finiteness (its host round
+    trip) and quantises it when the source was FP8.  index (the pooled row of every source row) and counts are made outside the clock."""
+    from drn_amd import Shortlister
+    from drn_amd.index import mx8_dequantize
+    rows = sl.embeddings if sl.quantize is None else mx8_dequantize(sl.codes, sl.scales, sl.dtype)
+    acc = torch.zeros((rows_out, rows.shape[1]), dtype=torch.float32, device=rows.device).index_add_(0, index, rows.float())
+    return Shortlister((acc / counts[:, None]).to(rows.dtype), offsets=out_off, quantize=sl.quantize)
+
+
+def bench_pooled(name, lens, emb, fp8, group, rounds, iters=5):
+    """Shortlister.pooled(how="mean", group=group) beside pooled_route on the same table: host clock from before the call to after a
+    device synchronise (both synchronise by design), the two taking turns inside every round, a round = the mean of `iters` runs.
+    Before timing every field of the result is asserted equal to pool_segments_reference, evaluated on the host."""
+    import numpy as np
+    from drn_amd import Shortlister, pool_offsets, pool_segments_reference
+    from drn_amd.index import mx8_quantize
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    R, V = int(off[-1]), len(lens)
+    assert R == int(emb.shape[0])
+    sl = Shortlister(emb, offsets=off, quantize="mxfp8" if fp8 else None)
+    got, want = sl.pooled(group=group), pool_segments_reference(sl, how="mean", group=group)
+    if fp8:
+        codes, scales = mx8_quantize(want.rows)
+        assert torch.equal(got.codes.cpu(), codes) and torch.equal(got.scales.cpu(), scales), (name, fp8, group)
+    else:
+        assert torch.equal(got.embeddings.cpu().view(torch.int16), want.rows.view(torch.int16)), (name, fp8, group)
+    assert (got._seg is None) == (want.offsets is None) and (group is None or got.offsets.cpu().tolist() == want.offsets.tolist())
+    out_off = pool_offsets(off, group)
+    rows_out = V if group is None else int(out_off[-1])
+    per = np.asarray(lens) if group is None else None
+    if group is None:
+        index, counts = np.repeat(np.arange(V), per), np.maximum(per, 1)
+    else:
+        within = np.arange(R) - np.repeat(off[:-1], lens)
+        index = np.repeat(out_off[:-1], lens) + within // group
+        counts = np.bincount(index, minlength=rows_out)
+    index, counts = torch.from_numpy(index).to("cuda:0"), torch.from_numpy(counts).to("cuda:0", torch.float32)
+    route = pooled_route(sl, index, counts, rows_out, out_off)
+    tensors = lambda t: (t.embeddings,) if t.quantize is None else (t.codes, t.scales)
+    route_equal = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(tensors(got), tensors(route)))
+    del want, route
+
+    def timed(run):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+    ours, theirs = [], []
+    for _ in range(rounds):
+        ours.append(statistics.mean(timed(lambda: sl.pooled(group=group)) for _ in range(iters)))
+        theirs.append(statistics.mean(timed(lambda: pooled_route(sl, index, counts, rows_out, out_off)) for _ in range(iters)))
+    over = statistics.median(ours) - statistics.median(theirs)
+    row_bytes = 528 if fp8 else 1024
+    nbytes = R * row_bytes + 4 * (V + 1) * (1 if group is None else 2) + rows_out * (1024 + (1024 + 528 if fp8 else 0))
+    return {"layout": name, "R": R, "V": V, "E": 512, "source": "mxfp8" if fp8 else "bf16", "target": "same", "how": "mean",
+            "group": group, "pooled_rows": rows_out, "runs_per_round": iters, "pooled_us": spread(ours), "route_us": spread(theirs),
+            "pooled_over_route": statistics.median(ours) / statistics.median(theirs),
+            "condition": {"pooled_minus_route_us": over, "route_max_minus_min_us": max(theirs) - min(theirs),
+                          "verdict": "HOLDS" if over <= max(theirs) - min(theirs) else "DOES NOT HOLD"},
+            "route_bytes_equal": route_equal,
+            "bytes": {"read_and_written": nbytes, "us_at_8.0TB/s": nbytes / HBM_PEAK_BYTES_PER_S * 1e6,
+                      "note": "for orientation only: every source row once in its format, the offsets, every pooled row written in bf16 "
+                              "and, for an FP8 result, read again by the quantiser and written as codes and scales"}}
+
+
+def main_pooled(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_pooled_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the table resident, every shape warmed",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds; a round = the mean of 5 runs",
+                      "clock": "host clock from before the call to after a device synchronise: launch-inclusive us per call, the "
+                               "synchronise of pooled() and of the route's constructor included",
+                      "yardstick": "the parent's only way to a pooled table, in torch on the device: (mx8_dequantize of an FP8 table,) an "
+                                   "fp32 index_add_, a divide, a cast and Shortlister(rows, offsets, quantize=) -- in the same rounds, on "
+                                   "the same table; its index and counts are made outside the clock",
+                      "condition": "derived, not measured: pooled() reads the table once and writes the pooled rows once, the route "
+                                   "writes and reads an fp32 copy besides, so pooled() may not take longer than the route beyond the "
+                                   "route's own max - min: HOLDS / DOES NOT HOLD per shape; no absolute time is required",
+                      "what_this_does_not_say": "no kernel-only time (no profiler run); bf16 only, no fp32; no long runs on few videos, "
+                                                "where one wavefront a pooled row fills little of the chip; how=\"mean\" only; random "
+                                                "embeddings: nothing here says anything about recall of a pooled table"},
+           "pooled": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for name, lens in POOLED_LAYOUTS:
+        for fp8 in (False, True):
+            for group in (None, 4):
+                row = bench_pooled(name, lens, emb, fp8, group, args.rounds)
+                res["pooled"].append(row)
+                print("pooled %s %s group = %s: pooled / route = %.3f, %.0f against %.0f us, condition %s" % (
+                    name, row["source"], group, row["pooled_over_route"], row["pooled_us"]["median"], row["route_us"]["median"],
+                    row["condition"]["verdict"]), flush=True)
+                with open(out, "w") as f:
+                    json.dump(res, f, indent=1)
+                    f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -2570,9 +2682,14 @@ def main():
     ap.add_argument("--deep-shortlist", action="store_true", help="measure Shortlister.shortlist_deep at n = 128 / 256 / 512 / 1024 beside "
                                                                   "shortlist() at 128, eight masked rounds of it and matmul + topk "
                                                                   "(writes profiles/search_deep_shortlist_bench.json)")
+    ap.add_argument("--pooled", action="store_true", help="measure Shortlister.pooled (mean, one row a video and one per 4 rows, bf16 and FP8 "
+                                                          "sources) beside index_add_ + divide + cast + Shortlister in torch "
+                                                          "(writes profiles/search_pooled_bench.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.pooled:
+        return main_pooled(args)
     if args.deep_shortlist:
         return main_deep_shortlist(args)
     if args.compact:
