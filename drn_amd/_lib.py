@@ -28,6 +28,8 @@ CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates t
 RERANK_MAX_CANDIDATES = CANDIDATES_MAX  # DRN_RERANK_MAX_CANDIDATES: columns of the list drn_shortlist_rerank takes (a CHOICE: the width the Grounder takes)
 SHORTLIST_DEEP_MAX = RERANK_MAX_CANDIDATES  # DRN_SHORTLIST_DEEP_MAX: the longest list drn_shortlist_deep returns (a CHOICE: the width its consumers take)
 RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
+FUSE_MAX_TABLES = 8       # DRN_FUSE_MAX_TABLES: score matrices drn_shortlist_fuse_topn / _rank fold (a choice, not a measurement)
+FUSE_MODES = {"drop": 0, "skip": 1}   # DRN_FUSE_DROP / DRN_FUSE_SKIP
 SHARDS_MAX = 64           # DRN_SHARDS_MAX: tables of one ShardedShortlister, lists a sentence drn_shortlist_merge_lists merges (a choice, not a measurement)
 
 
@@ -226,6 +228,12 @@ SIGNATURES = {
     "drn_compact_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                          c_void_p, c_void_p, c_void_p],
     "drn_pool_segments": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "drn_shortlist_scores": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_void_p, c_int, c_void_p],
+    "drn_shortlist_fuse_topn": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_fuse_rank": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

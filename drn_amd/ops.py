@@ -1931,6 +1931,110 @@ def shortlist_rerank(table, queries, lengths, offsets, candidates, n, ws, ids, s
     return ids, scores, counts
 
 
+def _row_strided(t, rows, cols):
+    """Is t a (rows, cols) view whose elements lie at row * ld + column with ld >= cols -> ld, or None."""
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols) or (cols > 1 and t.stride(1) != 1):
+        return None
+    ld = int(t.stride(0)) if rows > 1 else cols
+    return ld if cols <= ld < 2 ** 31 else None
+
+
+def shortlist_scores(table, queries, lengths, plan, out, allow=None):
+    """The WHOLE score matrix of a table (drn_shortlist_scores; drn_amd.retrieve.scores_reference is the definition): table is emb, float32
+    / bfloat16, or a pair (codes, scales) of a block-scaled FP8 table; plan is () on a table of one row per video, (offsets, blk_vid)
+    int32 on the device on a ragged one; lengths is None -- queries (S, E) -- or (S,) int32 on the device -- late interaction, queries
+    (S, L, E), a ragged table only -> out, float32 (S, V), written in place, exactly those elements: out may be a ROW-STRIDED view (last
+    stride 1, row stride >= V), such as a column slice of a wider buffer.  out[s, v] has the bits the matching shortlist entry lists
+    for the pair (-0 as +0) and is -inf where the video is no candidate (no row, a score that is not finite, a clear mask bit, no
+    live token).  allow: None, or a packed mask as in shortlist_topn.  One launch (tag shortlist_scores), no workspace; nothing is
+    read on the host."""
+    what = "shortlist_scores"
+    plan = tuple(plan)
+    late = lengths is not None
+    if len(plan) not in (0, 2) or (late and not plan):
+        raise _lib.DrnError("%s: plan must be () or (offsets, blk_vid), and lengths (late interaction) need a ragged table" % what)
+    if late:
+        if queries.dim() != 3 or not queries.is_contiguous() or not 1 <= queries.shape[1] <= _lib.LATE_MAX_TOKENS or queries.shape[0] < 1:
+            raise _lib.DrnError("%s: queries must be a contiguous (S, L, E) tensor with S >= 1 and 1 <= L <= %d, not %s"
+                                % (what, _lib.LATE_MAX_TOKENS, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), int(queries.shape[1])
+    else:
+        if queries.dim() != 2 or queries.shape[0] < 1:
+            raise _lib.DrnError("%s: queries must be a contiguous (S, E) tensor with S >= 1, not %s" % (what, tuple(queries.shape)))
+        S, L = int(queries.shape[0]), 1
+    tensors, tab, scl, R, E = _rank_table(what, table, queries.view(S * L, -1) if late else queries)
+    _need_gpu(*(tensors + (queries, out) + plan + tuple(t for t in (lengths, allow) if t is not None)))
+    if late and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,) or not lengths.is_contiguous()):
+        raise _lib.DrnError("%s: lengths must be a contiguous (%d,) torch.int32 tensor" % (what, S))
+    V, nblocks = _rank_plan(what, *plan) if plan else (R, 0)
+    ld = _row_strided(out, S, V) if out.dtype == torch.float32 else None
+    if ld is None:
+        raise _lib.DrnError("%s: out must be a (%d, %d) torch.float32 tensor with last stride 1 and row stride >= %d, not %s %s with strides %s"
+                            % (what, S, V, V, out.dtype, tuple(out.shape), tuple(out.stride())))
+    mask, stride = _allow_args(what, allow, V, S)
+    _timed(what, 2.0 * S * L * R * E, lambda: check(lib().drn_shortlist_scores(
+        tab, scl, _p(queries), None if lengths is None else _p(lengths), _p(plan[0]) if plan else None, _p(plan[1]) if plan else None, mask,
+        stride, R if plan else 0, V, nblocks, E, S, L, dtype_code(queries), _p(out), ld, _stream()), "drn_shortlist_scores"))
+    return out
+
+
+def _fuse_args(what, scores, weights, missing, allow):
+    """The checks the two fuse wrappers share -> (M, S, V, stride_m, ld, mode, mask pointer, allow_stride)."""
+    if missing not in _lib.FUSE_MODES:
+        raise _lib.DrnError("%s: missing must be one of %s, not %r" % (what, sorted(_lib.FUSE_MODES), missing))
+    if scores.dim() != 3 or scores.dtype != torch.float32 or not 1 <= scores.shape[0] <= _lib.FUSE_MAX_TABLES or scores.shape[1] < 1 \
+            or scores.shape[2] < 1:
+        raise _lib.DrnError("%s: scores must be (M, S, V) torch.float32 with 1 <= M <= %d, S >= 1 and V >= 1, not %s %s"
+                            % (what, _lib.FUSE_MAX_TABLES, scores.dtype, tuple(scores.shape)))
+    M, S, V = (int(x) for x in scores.shape)
+    ld = _row_strided(scores[0], S, V)
+    stride_m = int(scores.stride(0)) if M > 1 else 0
+    if ld is None or (M > 1 and stride_m < (S - 1) * ld + V):
+        raise _lib.DrnError("%s: scores must have last stride 1, row stride >= V and matrices that do not overlap, not strides %s"
+                            % (what, tuple(scores.stride())))
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (M,) or not weights.is_contiguous():
+        raise _lib.DrnError("%s: weights must be a contiguous (%d,) torch.float32 tensor on the device" % (what, M))
+    mask, stride = _allow_args(what, allow, V, S)
+    return M, S, V, stride_m, ld, _lib.FUSE_MODES[missing], mask, stride
+
+
+def shortlist_fuse_topn(scores, weights, missing, n, ws, ids, out_scores, counts, allow=None):
+    """Each sentence's best n videos under the FUSED score of M stacked score matrices (drn_shortlist_fuse_topn;
+    drn_amd.retrieve.fused_shortlist_reference is the definition): scores (M, S, V) float32 on the device, last stride 1, row stride >= V
+    (what shortlist_scores writes: -inf = the video is missing from that table); weights (M,) float32 ON THE DEVICE; missing "drop" -- a
+    video missing from any table is no candidate -- or "skip" -- a missing term adds nothing; 1 <= n <= SHORTLIST_DEEP_MAX -> ids,
+    out_scores (S, n) and counts (S,), written in place, -1 / 0 past the list.  The fused score is ((0 + w0 * s0) + w1 * s1) + ... in
+    fp32, two roundings a term.  allow: None, or a packed mask as in shortlist_topn.  ws: an int64 tensor of at least
+    shortlist_ws_keys(V, S, n) elements.  Two launches (tag shortlist_fuse_topn); nothing is read on the host."""
+    what = "shortlist_fuse_topn"
+    _need_gpu(scores, weights, ws, ids, out_scores, counts, *(() if allow is None else (allow,)))
+    M, S, V, stride_m, ld, mode, mask, stride = _fuse_args(what, scores, weights, missing, allow)
+    n = int(n)
+    _shortlist_buffers(what, S, n, shortlist_ws_keys(V, S, n), ws, ids, out_scores, counts, cap=_lib.SHORTLIST_DEEP_MAX)
+    _timed(what, 2.0 * M * S * V, lambda: check(lib().drn_shortlist_fuse_topn(
+        _p(scores), stride_m, ld, _p(weights), M, mode, mask, stride, V, S, n, _p(ws), int(min(ws.numel(), 0x7fffffff)), _p(ids),
+        _p(out_scores), _p(counts), _stream()), "drn_shortlist_fuse_topn"))
+    return ids, out_scores, counts
+
+
+def shortlist_fuse_rank(scores, weights, missing, targets, rank, score, total, allow=None):
+    """The place of targets[s] in sentence s's full order under the fused score (drn_shortlist_fuse_rank;
+    drn_amd.retrieve.fused_rank_reference is the definition): scores, weights, missing and allow as in shortlist_fuse_topn; targets (S,)
+    int32 ON THE DEVICE, a value outside [0, V) meaning "no target" -> rank, score, total (S,) as in shortlist_rank, written in place.
+    One launch (tag shortlist_fuse_rank), no workspace; nothing is read on the host."""
+    what = "shortlist_fuse_rank"
+    _need_gpu(scores, weights, targets, rank, score, total, *(() if allow is None else (allow,)))
+    M, S, V, stride_m, ld, mode, mask, stride = _fuse_args(what, scores, weights, missing, allow)
+    for name, t, dt in (("targets", targets, torch.int32), ("rank", rank, torch.int32), ("score", score, torch.float32),
+                        ("total", total, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous (%d,) %s tensor" % (what, name, S, dt))
+    _timed(what, 2.0 * M * S * V, lambda: check(lib().drn_shortlist_fuse_rank(
+        _p(scores), stride_m, ld, _p(weights), M, mode, _p(targets), mask, stride, V, S, _p(rank), _p(score), _p(total), _stream()),
+        "drn_shortlist_fuse_rank"))
+    return rank, score, total
+
+
 def shortlist_merge_lists(in_ids, in_scores, in_counts, in_rows, bases, n, ids, scores, counts, rows=None):
     """Merge K stacked per-shard lists a sentence into the corpus's list: in_ids, in_scores (K, S, n_in) and in_counts (K, S) as the
     shards' shortlist entries wrote them, in_rows (K, S, n_in) beside them on ragged shards or None, bases (K + 1,) int32 ON THE DEVICE

@@ -75,7 +75,14 @@ ragged table the caller owns -- one row a video (group=None) or one row per g ro
 plain or an FP8 table into either format.  pool_segments_reference is the definition, bit for bit: an fp32 sum in ascending row order,
 one IEEE division, one rounding; drn_pool_segments (csrc/retrieve_pool.hip) the launch, one wavefront per pooled row and column slab.
 Store positions and names are unchanged, so the pooled table is the `coarse` of evaluate_cascade beside its source as `fine`; with
-group=None a video without rows is a row of zeros and table.nonempty the mask that keeps it off the lists."""
+group=None a video without rows is a row of zeros and table.nonempty the mask that keeps it off the lists.
+
+Shortlister.scores / scores_late (and ShardedShortlister's) hand out the DENSE score matrix the lists are cut from: float32 (S, V), a
+written score with the bits the list would show, -inf where the video is no candidate (scores_reference; drn_shortlist_scores,
+csrc/retrieve_fuse.hip, one launch).  shortlist_scores ranks any such matrix under the total order, and FusedShortlister ranks SEVERAL
+tables over the same videos as one -- w_0 * best window + w_1 * best subtitle line, each table taking its own maximum over its own rows
+-- by a fold whose order is stated (fuse_scores_reference: acc = acc + (w_m * s_m), m ascending, fp32, two roundings a term;
+fused_shortlist_reference and fused_rank_reference cut the list and take the rank; drn_shortlist_fuse_topn / _rank the launches)."""
 import collections
 import numbers
 
@@ -83,7 +90,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import (LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_DEEP_MAX, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK,
+from ._lib import (FUSE_MAX_TABLES, FUSE_MODES, LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_DEEP_MAX, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK,
                    DrnError)      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize, mx8_quantize
 
@@ -186,6 +193,90 @@ def late_rank_reference(embeddings, offsets, queries, lengths, targets, allow=No
     the sum over the live tokens of its best row and is a candidate when it owns a row, the sum is finite, allow does not exclude it
     and the sentence has a live token (one without has total = 0 and rank = -1).  -> TargetRank."""
     return _ranked(*_late_scores(embeddings, offsets, queries, lengths, allow), targets)
+
+
+def scores_reference(embeddings, queries, offsets=None, lengths=None, allow=None):
+    """THE DEFINITION of Shortlister.scores / scores_late (usable on the CPU): the WHOLE score matrix the shortlist references cut
+    their lists from -> float32 (S, V) on the inputs' device.  Without offsets: shortlist_reference's scores (_plain_scores); with
+    offsets: segment_shortlist_reference's, a video's best row (_segment_scores); with offsets and lengths: late_shortlist_reference's,
+    queries (S, L, E) (_late_scores) -- computed in float64 and rounded to float32, a -0 returned as +0.  Where the video is NO
+    CANDIDATE of the sentence -- it owns no row, its score is not finite (in float32), allow excludes it or (late) the sentence has no
+    live token -- the entry is -inf: finite <=> candidate, and no NaN is ever returned.  No arithmetic of its own."""
+    if lengths is not None:
+        if offsets is None:
+            raise DrnError("scores_reference: lengths (late interaction) need offsets: a ragged table")
+        score, finite = _late_scores(embeddings, offsets, queries, lengths, allow)
+    elif offsets is not None:
+        score, _, finite = _segment_scores(embeddings, offsets, queries, allow)
+    else:
+        score, finite = _plain_scores(embeddings, queries, allow)
+    value = torch.where(finite, score, torch.zeros_like(score)).float() + 0.0      # (-0 + 0 = +0)
+    return torch.where(finite & torch.isfinite(value), value, torch.full_like(value, float("-inf")))
+
+
+def _fuse_inputs(what, scores, weights, missing):
+    """What the fuse references take -> (scores (M, S, V) float32 ON THE HOST, weights (M,) float32 on the host, the scores' device)."""
+    if missing not in FUSE_MODES:
+        raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
+    if not torch.is_tensor(scores):
+        try:
+            scores = torch.stack(list(scores))
+        except Exception:
+            raise DrnError("%s: scores must be an (M, S, V) float32 tensor or a sequence of M (S, V) float32 tensors" % what)
+    if scores.dim() != 3 or scores.dtype != torch.float32 or not 1 <= scores.shape[0] <= FUSE_MAX_TABLES or scores.shape[1] < 1 \
+            or scores.shape[2] < 1:
+        raise DrnError("%s: scores must be (M, S, V) float32 with 1 <= M <= %d, S >= 1 and V >= 1, not %s %s"
+                       % (what, FUSE_MAX_TABLES, scores.dtype, tuple(scores.shape)))
+    M = int(scores.shape[0])
+    w = torch.ones(M, dtype=torch.float32) if weights is None else torch.as_tensor(weights).detach().cpu()
+    if tuple(w.shape) != (M,) or w.dtype == torch.bool or w.is_complex():
+        raise DrnError("%s: weights must be %d numbers, one per score matrix, not %s %s" % (what, M, w.dtype, tuple(w.shape)))
+    return scores.detach().cpu(), w.to(torch.float32), scores.device
+
+
+def fuse_scores_reference(scores, weights, missing="drop"):
+    """THE DEFINITION of the fused score, EVALUATED ON THE HOST in float32 whatever device the inputs live on -> (fused (S, V) float32,
+    candidate (S, V) bool) on the scores' device.  scores: (M, S, V) float32, or a sequence of M (S, V) matrices, 1 <= M <=
+    FUSE_MAX_TABLES -- what Shortlister.scores returns: an entry that is not finite says the video is MISSING from that table;
+    weights: M numbers (None: all ones), rounded to float32.  The order is FIXED, one float32 multiply and one float32 add a term,
+    each rounded on its own (not an FMA, and not a sum whose order nobody states):
+        acc = +0;  for m = 0 .. M - 1 ascending:  present = isfinite(scores[m]);
+            missing="drop":  acc = acc + (w[m] * scores[m]);      missing="skip":  acc = where(present, acc + (w[m] * scores[m]), acc)
+        candidate = isfinite(acc) and (drop: every m present | skip: some m present).
+    Under "drop" a video missing from any table is missing from the answer; under "skip" a modality the video lacks adds nothing.
+    With M = 1 and w = 1 the candidates are the finite entries and the fused score is the entry (0 + 1 * s, exact; a -0 becomes +0)."""
+    sc, w, dev = _fuse_inputs("fuse_scores_reference", scores, weights, missing)
+    M = int(sc.shape[0])
+    acc = torch.zeros(tuple(sc.shape[1:]), dtype=torch.float32)
+    every, some = torch.ones(tuple(sc.shape[1:]), dtype=torch.bool), torch.zeros(tuple(sc.shape[1:]), dtype=torch.bool)
+    for m in range(M):
+        present = torch.isfinite(sc[m])
+        term = w[m] * sc[m]                                  # (one rounding)
+        added = acc + term                                   # (one more)
+        acc = added if missing == "drop" else torch.where(present, added, acc)
+        every, some = every & present, some | present
+    candidate = torch.isfinite(acc) & (every if missing == "drop" else some)
+    return acc.to(dev), candidate.to(dev)
+
+
+def fused_shortlist_reference(scores, weights, n, missing="drop", allow=None):
+    """THE DEFINITION of FusedShortlister.shortlist and of shortlist_scores (M = 1, w = 1): the list every reference cuts, from
+    fuse_scores_reference's fused scores and candidates -- a candidate that allow (a bool tensor (V,) or (S, V)) excludes is none --
+    ordered by higher fused score, then lower position, cut to n; -1 / 0 past the list.  -> Shortlist on the scores' device."""
+    fused, candidate = fuse_scores_reference(scores, weights, missing)
+    if allow is not None:
+        candidate = candidate & _allowed(allow, int(fused.shape[0]), int(fused.shape[1]), fused.device)
+    ids, listed, count, _ = _listed(fused.double(), candidate, int(n))
+    return Shortlist(ids, listed, count)
+
+
+def fused_rank_reference(scores, weights, targets, missing="drop", allow=None):
+    """THE DEFINITION of FusedShortlister.rank: rank_reference's answer (_ranked) from fuse_scores_reference's fused scores and
+    candidates, allow applied as in fused_shortlist_reference.  -> TargetRank on the scores' device."""
+    fused, candidate = fuse_scores_reference(scores, weights, missing)
+    if allow is not None:
+        candidate = candidate & _allowed(allow, int(fused.shape[0]), int(fused.shape[1]), fused.device)
+    return _ranked(fused.double(), candidate, targets)
 
 
 def candidates_mask(candidates, V):
@@ -590,6 +681,15 @@ def _check_list_out(what, out, S, n, rows=False):
                                   ((S, n), (S, n), (S,), (S, n))):
         if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise DrnError("%s: out.%s must be a contiguous %s %s tensor on the GPU" % (what, name, shape, dt))
+
+
+def _check_scores_out(what, out, S, V, dev):
+    """out= of scores() / scores_late(): a float32 (S, V) tensor on dev whose rows are contiguous -- last stride 1, row stride >= V."""
+    if not torch.is_tensor(out) or not out.is_cuda or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (S, V):
+        raise DrnError("%s: out must be a (%d, %d) torch.float32 tensor on the table's device %s" % (what, S, V, dev))
+    if (V > 1 and out.stride(1) != 1) or (S > 1 and out.stride(0) < V):
+        raise DrnError("%s: out must have last stride 1 and row stride >= %d (a contiguous matrix, or a column slice of a wider one), "
+                       "not strides %s" % (what, V, tuple(out.stride())))
 
 
 def _list_buffers(dev, S, n, rows=False):
@@ -1302,6 +1402,47 @@ class Shortlister(object):
         ops.shortlist_late_rank(self._operand(), queries, lengths, seg[0], seg[1], targets, ws, *out, allow=allow)
         return TargetRank(*out)
 
+    def scores(self, queries, out=None, allow=None):
+        """THE WHOLE SCORE MATRIX shortlist() ranks and throws away -> float32 (S, V) on the device (scores_reference defines it).
+        queries as in rank(): (S, E) on the table's device in the table's dtype.  out[s, v] is the score shortlist() gives the pair --
+        the same MFMA chain and, on a ragged table, the same best row: scores()[s, ids[s, k]] has the bits of shortlist().scores[s, k],
+        a -0 written as +0 -- and -inf where the video is NO CANDIDATE: it owns no row, its score is not finite, or allow excludes
+        it.  So finite <=> candidate, no NaN is ever written, and an entry depends on the sentence, the video's rows and its mask bit
+        alone.  Works on all four tables; on a quantised one it is bit for bit dequantized().scores(...).  out: a float32 (S, V) tensor
+        on the table's device written in place, EXACTLY those elements: it may be a row-strided view (last stride 1, row stride >= V),
+        such as a column slice buffer[:, a:a + V] of a wider matrix.  allow= as in shortlist().  ONE launch on the current stream
+        (drn_shortlist_scores), no workspace, no host synchronisation, and it can be captured in a graph, where the queries and the
+        mask's contents may change in place between replays.
+        What this costs: 4 * S * V bytes written, where shortlist() writes 12 * S * n; a threshold, a calibration or a distillation
+        target reads it, and shortlist_scores() ranks it (or anything made from it) under the project's total order."""
+        what = "Shortlister.scores"
+        S, _ = self._check_queries(what, queries)
+        return self._scores(what, S, queries.contiguous(), None, out, allow)
+
+    def scores_late(self, queries, lengths, out=None, allow=None):
+        """scores() by LATE INTERACTION -> float32 (S, V): queries (S, L, E) and lengths (S,) as in shortlist_late(); out[s, v] has
+        the bits shortlist_late() lists for the pair -- the fp32 sum over the live tokens, in ascending order, of the token's best row
+        -- and is -inf where the video is no candidate; a sentence without a live token is a row of -inf.  out= and allow= as in
+        scores().  One launch, capturable, where queries, lengths and the mask's contents may change in place between replays.  A table
+        without offsets is refused as in shortlist_late()."""
+        what = "Shortlister.scores_late"
+        if self._seg is None:
+            _refuse_late(what, "scores")
+        S, _, _ = self._check_late(what, queries, lengths)
+        return self._scores(what, S, queries, lengths, out, allow)
+
+    def _scores(self, what, S, queries, lengths, out, allow):
+        """What scores (lengths=None) and scores_late share once their queries are checked: out=, allow= and the one launch."""
+        dev, V = self._table().device, len(self)
+        if out is None:
+            out = torch.empty((S, V), dtype=torch.float32, device=dev)
+        else:
+            _check_scores_out(what, out, S, V, dev)
+        if allow is not None:
+            self._check_allow(allow, S)
+        seg = self._seg
+        return ops.shortlist_scores(self._operand(), queries, lengths, () if seg is None else (seg[0], seg[1]), out, allow=allow)
+
     def _rank_keys(self, what, queries, lengths, targets, keys, allow=None):
         """PHASE 1 of rank() (lengths=None) or rank_late() alone, for ShardedShortlister: each sentence's target key in THIS table ->
         keys, a contiguous (S,) int64 tensor written in place (0 where the target is no candidate here).  The refusals are the public
@@ -1830,6 +1971,41 @@ class ShardedShortlister(object):
             raise DrnError("%s: lengths must be a contiguous torch.int32 tensor on the device, the live tokens of each sentence" % what)
         return self._rank(what, queries, lengths, targets, out, allow)
 
+    def _scores(self, what, S, queries, lengths, out, allow):
+        """What scores (lengths=None) and scores_late share once their queries are checked: shard k writes the columns bases[k] ..
+        bases[k + 1] - 1 of out through its row stride -- K launches and no merge; with allow=, one slicing launch first."""
+        dev, V = self.device, len(self)
+        if out is None:
+            out = torch.empty((S, V), dtype=torch.float32, device=dev)
+        else:
+            _check_scores_out(what, out, S, V, dev)
+        if allow is not None:
+            _check_packed_allow(allow, S, V, dev)
+        for shard, piece, a, b in zip(self.shards, self._slices(allow), self.bases[:-1], self.bases[1:]):
+            shard._scores(what, S, queries, lengths, out[:, a:b], piece)
+        return out
+
+    def scores(self, queries, out=None, allow=None):
+        """Shortlister.scores over the corpus -> float32 (S, V), column v the corpus's video v: the arguments, the refusals and out=
+        of the single table's method, and every element bit for bit what one Shortlister over the concatenated rows writes (a score's
+        bits do not depend on the table that holds the video).  allow: a packed mask over the WHOLE corpus.  Each shard writes its own
+        columns of out in place: K launches, one more under a mask, NO merge; no host synchronisation, capturable once the mask's
+        slices are warmed."""
+        what = "Shortlister.scores"
+        S = self.shards[0]._check_rank_queries(what, queries, None)
+        return self._scores(what, S, queries.contiguous(), None, out, allow)
+
+    def scores_late(self, queries, lengths, out=None, allow=None):
+        """Shortlister.scores_late over the corpus (ragged shards) -> float32 (S, V), as scores().  Shards without offsets are refused
+        as in shortlist_late()."""
+        what = "Shortlister.scores_late"
+        if self.shards[0]._seg is None:
+            _refuse_late(what, "scores", whose="these tables have")
+        if not torch.is_tensor(lengths):
+            raise DrnError("%s: lengths must be a contiguous torch.int32 tensor on the device, the live tokens of each sentence" % what)
+        S = self.shards[0]._check_rank_queries(what, queries, lengths)
+        return self._scores(what, S, queries, lengths, out, allow)
+
     def _rerank(self, what, candidates, queries, lengths, n, out, allow):
         """What rerank (lengths=None) and rerank_late share: the refusals of the single table's method, then K + 2 launch groups."""
         first = self.shards[0]
@@ -1884,3 +2060,196 @@ class ShardedShortlister(object):
         if not torch.is_tensor(lengths):
             raise DrnError("%s: lengths must be a contiguous torch.int32 tensor on the device, the live tokens of each sentence" % what)
         return self._rerank(what, candidates, queries, lengths, n, out, allow)
+
+
+def _check_matrix(what, scores):
+    """What shortlist_scores refuses about its matrix, before the library is reached -> (S, V)."""
+    if not torch.is_tensor(scores) or not scores.is_cuda:
+        raise DrnError("%s: scores must be a tensor on the GPU; there is no CPU fallback (fused_shortlist_reference is the definition)" % what)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise DrnError("%s: scores must be a (S, V) torch.float32 tensor with S >= 1 and V >= 1, not %s %s"
+                       % (what, scores.dtype, tuple(scores.shape)))
+    S, V = (int(x) for x in scores.shape)
+    if (V > 1 and scores.stride(1) != 1) or (S > 1 and scores.stride(0) < V):
+        raise DrnError("%s: scores must have last stride 1 and row stride >= %d, not strides %s" % (what, V, tuple(scores.stride())))
+    return S, V
+
+
+def _check_depth(what, n):
+    """1 <= n <= SHORTLIST_DEEP_MAX -> n."""
+    n = int(n)
+    if not 1 <= n <= SHORTLIST_DEEP_MAX:
+        raise DrnError("%s: n = %d outside [1, %d]" % (what, n, SHORTLIST_DEEP_MAX))
+    return n
+
+
+def shortlist_scores(scores, n, allow=None, out=None):
+    """RANK A SCORE MATRIX the caller already has under the project's total order -> Shortlist, on the device
+    (fused_shortlist_reference(scores[None], None, n) defines it).  scores: float32 (S, V) on the GPU, last stride 1 and row stride
+    >= V -- what Shortlister.scores returns, or anything computed from it: calibrated, thresholded, distilled.  An entry that is not
+    finite (-inf, +inf, NaN) is NO CANDIDATE; the others are listed by higher score, then lower position, cut to 1 <= n <=
+    SHORTLIST_DEEP_MAX, with -1 / 0 past the list, and a listed score has the entry's bits (-0 as +0).  So
+    shortlist_scores(table.scores(q), n) is table.shortlist(q, n) -- table.shortlist_deep(q, n) above SHORTLIST_MAX -- without its rows.
+    allow: a packed mask over the V columns, as in Shortlister.shortlist.  out: the three buffers of a Shortlist, written in place.
+    Two launches (drn_shortlist_fuse_topn with one matrix and the weight 1: 0 + 1 * s is exact), no host synchronisation; the
+    workspace is allocated per call."""
+    what = "shortlist_scores"
+    S, V = _check_matrix(what, scores)
+    n = _check_depth(what, n)
+    if out is not None:
+        _check_list_out(what, out, S, n)
+    if allow is not None:
+        _check_packed_allow(allow, S, V, scores.device)
+    if out is None:
+        out = _list_buffers(scores.device, S, n)
+    ws = torch.empty(ops.shortlist_ws_keys(V, S, n), dtype=torch.int64, device=scores.device)
+    one = torch.ones(1, dtype=torch.float32, device=scores.device)
+    ops.shortlist_fuse_topn(scores.unsqueeze(0), one, "drop", n, ws, *out, allow=allow)
+    return Shortlist(*out)
+
+
+class FusedShortlister(object):
+    """FusedShortlister(tables, weights=None, missing="drop"): ONE ranking of several tables over the same videos -- a visual window
+    table, a subtitle table, a pooled coarse table, an FP8 copy: score[s, v] = w_0 * score_0[s, v] + w_1 * score_1[s, v] + ..., each
+    table scoring the video its own way (its best row over its own offsets, its own E and dtype, its own late interaction), the sum
+    folded in a FIXED order in fp32 (fuse_scores_reference defines it: two roundings a term), and the list cut under the one total
+    order (fused score descending, then position ascending).  Over ragged tables this is no concatenation: every modality takes its
+    own maximum over its own rows.
+
+    tables: 1 to FUSE_MAX_TABLES Shortlister / ShardedShortlister objects over the SAME V videos on one device, held by reference;
+    where names are given they must be equal position by position (refused here, before any launch); E, dtype, offsets, quantisation
+    and sharding may all differ.  weights: None (all ones), a host sequence of M numbers (rounded to fp32, uploaded ONCE through pinned
+    memory) or a contiguous float32 (M,) tensor on the device, kept BY REFERENCE and never read on the host: its contents may change
+    between calls and between replays of a captured graph.  missing: "drop" -- a video that is no candidate of ANY table (no row there,
+    a score that is not finite) is no candidate of the answer -- or "skip" -- a table the video is missing from adds nothing (a video
+    without subtitles), and only a video missing from every table is dropped.
+
+    What this is NOT.  For tables of one row per video and one dtype it is the plain shortlist of the table of concatenated (weighted)
+    columns, which is cheaper: one launch group and no dense buffer.  The dense buffers cost 4 * M * S * V bytes, kept per S.  There
+    is no fused rerank: the M score launches read every table whole.  No `rows` come back: a fused score has no single winning
+    segment.  Attributes: tables, weights (the device tensor), missing, names (the first table's that has any), device; len() is V."""
+
+    def __init__(self, tables, weights=None, missing="drop"):
+        what = "FusedShortlister"
+        try:
+            tables = list(tables)
+        except TypeError:
+            raise DrnError("%s: the tables must be a sequence of Shortlister / ShardedShortlister objects" % what)
+        if not 1 <= len(tables) <= FUSE_MAX_TABLES:
+            raise DrnError("%s: %d tables outside [1, %d]" % (what, len(tables), FUSE_MAX_TABLES))
+        if missing not in FUSE_MODES:
+            raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
+        names = None
+        for m, table in enumerate(tables):
+            if not isinstance(table, (Shortlister, ShardedShortlister)):
+                raise DrnError("%s: table %d must be a Shortlister or a ShardedShortlister, not %s" % (what, m, type(table).__name__))
+            if len(table) != len(tables[0]):
+                raise DrnError("%s: table %d holds %d videos, table 0 holds %d: the tables must rank the same videos, position by position"
+                               % (what, m, len(table), len(tables[0])))
+            if table.device != tables[0].device:
+                raise DrnError("%s: table %d is on %s, table 0 on %s" % (what, m, table.device, tables[0].device))
+            if table.names is not None:
+                if names is not None and list(table.names) != names:
+                    raise DrnError("%s: the names of table %d are not those of the tables before it (position v must be the same video "
+                                   "in every table)" % (what, m))
+                names = list(table.names)
+        M, dev = len(tables), tables[0].device
+        if weights is None:
+            w = torch.ones(M, dtype=torch.float32)
+        elif torch.is_tensor(weights):
+            if weights.dtype != torch.float32 or tuple(weights.shape) != (M,) or not weights.is_contiguous():
+                raise DrnError("%s: a weights tensor must be contiguous (%d,) torch.float32, one weight per table, not %s %s"
+                               % (what, M, weights.dtype, tuple(weights.shape)))
+            if weights.device != dev:
+                raise DrnError("%s: a weights tensor must be on the tables' device %s (it is kept by reference and never read on the "
+                               "host); pass a host sequence to have it uploaded" % (what, dev))
+            w = None
+        else:
+            try:
+                w = torch.tensor([float(x) for x in weights], dtype=torch.float32)
+            except (TypeError, ValueError):
+                raise DrnError("%s: weights must be None, %d numbers or a float32 (%d,) tensor on the device" % (what, M, M))
+            if tuple(w.shape) != (M,):
+                raise DrnError("%s: %d weights for %d tables" % (what, int(w.shape[0]), M))
+        if w is not None:
+            weights = w.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else w
+        self.tables, self.weights, self.missing, self.names = tables, weights, missing, names
+        self._bufs = {}
+
+    @property
+    def device(self):
+        return self.tables[0].device
+
+    def __len__(self):
+        return len(self.tables[0])
+
+    def _check_items(self, what, queries):
+        """What shortlist() and rank() refuse about the M query items, ALL before the first launch -> (S, [(queries, lengths)] * M)."""
+        M = len(self.tables)
+        if not isinstance(queries, (list, tuple)) or len(queries) != M:
+            raise DrnError("%s: queries must be a sequence of %d items, one per table: what the table's scores() takes, or a pair "
+                           "(queries, lengths) for its scores_late()" % (what, M))
+        items, S = [], None
+        for m, (table, item) in enumerate(zip(self.tables, queries)):
+            q, lengths = (item[0], item[1]) if isinstance(item, (list, tuple)) and len(item) == 2 else (item, None)
+            if isinstance(item, (list, tuple)) and len(item) != 2:
+                raise DrnError("%s: item %d must be a queries tensor or a pair (queries, lengths)" % (what, m))
+            first = table if isinstance(table, Shortlister) else table.shards[0]
+            if lengths is not None and not torch.is_tensor(lengths):
+                raise DrnError("%s: the lengths of item %d must be a contiguous torch.int32 tensor on the device" % (what, m))
+            Sm = first._check_rank_queries("%s (table %d)" % (what, m), q, lengths)
+            if S is not None and Sm != S:
+                raise DrnError("%s: item %d holds %d sentences, item 0 holds %d" % (what, m, Sm, S))
+            S = Sm
+            items.append((q if lengths is not None else q.contiguous(), lengths))
+        return S, items
+
+    def _stack(self, what, S, items):
+        """The M score launch groups (K launches on a sharded table), UNMASKED, into the stacked (M, S, V) buffer kept per S."""
+        buf = self._bufs.get(("scores", S))
+        if buf is None:
+            buf = self._bufs[("scores", S)] = torch.empty((len(self.tables), S, len(self)), dtype=torch.float32, device=self.device)
+        for m, (table, (q, lengths)) in enumerate(zip(self.tables, items)):
+            table._scores(what, S, q, lengths, buf[m], None)
+        return buf
+
+    def shortlist(self, queries, n, out=None, allow=None):
+        """Each sentence's best n videos under the fused score -> Shortlist, on the device (fused_shortlist_reference applied to the
+        tables' own scores() is the definition, bit for bit).  queries: a sequence of M items, item m what table m's scores() takes --
+        (S, E_m) in that table's dtype -- or a pair (queries (S, L, E_m), lengths (S,)) for its scores_late(); every item holds the same
+        S sentences.  1 <= n <= SHORTLIST_DEEP_MAX.  out: the three buffers of a Shortlist, written in place.  allow: a packed mask
+        over the V videos, as in Shortlister.shortlist; it is applied AFTER fusion, by the ranking launch alone: the score launches run
+        unmasked, so a score matrix never depends on the mask.  M score launch groups (K launches on a table of K shards) into a
+        stacked buffer kept per S, then drn_shortlist_fuse_topn (two launches); all on the current stream, no host synchronisation,
+        and it can be captured in a graph once the shape is warmed (the buffers are kept per S and per (S, n)), where the queries,
+        lengths, the weights tensor and the mask's contents may change in place between replays.  No `rows` are returned."""
+        what = "FusedShortlister.shortlist"
+        S, items = self._check_items(what, queries)
+        n = _check_depth(what, n)
+        if out is not None:
+            _check_list_out(what, out, S, n)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        if out is None:
+            out = _list_buffers(self.device, S, n)
+        ws = self._bufs.get(("ws", S, n))
+        if ws is None:
+            ws = self._bufs[("ws", S, n)] = torch.empty(ops.shortlist_ws_keys(len(self), S, n), dtype=torch.int64, device=self.device)
+        ops.shortlist_fuse_topn(self._stack(what, S, items), self.weights, self.missing, n, ws, *out, allow=allow)
+        return Shortlist(*out)
+
+    def rank(self, queries, targets, out=None, allow=None):
+        """The place of each sentence's TARGET video in the full fused order -> TargetRank, on the device (fused_rank_reference
+        applied to the tables' own scores() is the definition): queries as in shortlist(), targets, out= and allow= as in
+        Shortlister.rank.  rank[s] = k >= 0 exactly when shortlist(queries, n).ids[s, k] is the target for every n > k, and score[s] has
+        the listed score's bits.  M score launch groups, then ONE launch (drn_shortlist_fuse_rank); no host synchronisation,
+        capturable once the shape is warmed.  evaluate_shortlist(fused, batches) works as it stands, batch[1] being the M items."""
+        what = "FusedShortlister.rank"
+        S, items = self._check_items(what, queries)
+        table = self.tables[0]
+        first = table if isinstance(table, Shortlister) else table.shards[0]
+        out = first._check_rank(what, S, targets, out, None)
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        ops.shortlist_fuse_rank(self._stack(what, S, items), self.weights, self.missing, targets, *out, allow=allow)
+        return TargetRank(*out)

@@ -908,6 +908,49 @@ int drn_compact_rows(const void* src, const uint8_t* src_scales, const int32_t* 
 #define DRN_POOL_MAX 1
 int drn_pool_segments(const void* table, const uint8_t* scales, const int32_t* offsets, const int32_t* out_offsets, int R, int V, int R_out,
                       int out_row0, int E, int group, int how, int dtype, void* out, void* stream);
+/* DENSE SCORES AND FUSED SHORTLISTS (drn_amd/csrc/retrieve_fuse.hip; drn_amd.retrieve.scores_reference, fuse_scores_reference,
+ * fused_shortlist_reference and fused_rank_reference are the definitions).
+ *
+ * drn_shortlist_scores writes the WHOLE score matrix the shortlist entries rank and throw away: out[s * ld_out + v], fp32, for s < S and
+ * v < V, ld_out >= V -- exactly those elements and nothing else.  table is emb, or the codes of a block-scaled FP8 table with scales
+ * beside them (scales == NULL: a plain table; E % 32 == 0 with scales); dtype is that of the queries.  offsets == NULL: one row per
+ * video -- blk_vid and lengths must then be NULL too, R and nblocks are ignored and L must be 1; otherwise offsets and blk_vid are the
+ * table and block plan of drn_shortlist_segments_topn.  lengths == NULL: queries [S][E], L must be 1; otherwise late interaction,
+ * queries [S][L][E] and lengths [S] as in drn_shortlist_late_topn.  allow: a packed mask as in the *_allow entries, or NULL for none.
+ * out[s][v] is the score the matching *_topn entry gives the pair -- the same MFMA chain, the same segmented maximum, the same token
+ * fold: its bits are the listed score's, a -0 written as +0 as the key folds it -- and -inf where the video is NO CANDIDATE: it owns no
+ * row, its score is not finite, its mask bit is clear or (late) the sentence has no live token.  So finite <=> candidate, and no NaN
+ * is ever written.  A block whose mask words are all clear for the tile reads no table row and writes its -inf all the same.  Every
+ * index read from a device table is clamped.  out is 4-byte aligned.  ONE launch, no workspace, no atomics, no host synchronisation;
+ * the queries, lengths and the mask may change between replays of a captured graph. */
+int drn_shortlist_scores(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths, const int32_t* offsets,
+                         const int32_t* blk_vid, const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int L,
+                         int dtype, float* out, int ld_out, void* stream);
+/* The FUSED score of M stacked score matrices, element (m, s, v) at scores[m * stride_m + s * ld + v], ld >= V, under weights [M] fp32
+ * ON THE DEVICE (never read on the host), 1 <= M <= DRN_FUSE_MAX_TABLES (a CHOICE, not a measurement: the tables a sentence's score
+ * is folded over), in a FIXED order, in fp32, two roundings a term (a multiply, then an add: no FMA):
+ *   acc = +0;  for m = 0 .. M - 1 ascending:  present = isfinite(scores[m][s][v]);
+ *     mode DRN_FUSE_DROP:  acc = acc + (w[m] * scores[m][s][v]);      DRN_FUSE_SKIP:  if present: acc = acc + (w[m] * scores[m][s][v]);
+ *   candidate = isfinite(acc) and allowed(s, v) and (DROP: every m present | SKIP: some m present).
+ * drn_shortlist_fuse_topn lists each sentence's candidates by fused score descending, then position ascending, cut to n, 1 <= n <=
+ * DRN_SHORTLIST_DEEP_MAX, into ids / out_scores [S][n] and counts [S] with the -1 / 0 padding of drn_shortlist_topn.  ws: ws_keys >= S *
+ * ceil(V / 256) * min(n, 256) 8-byte keys.  Two launches: workgroup (block of 256 videos, sentence) fuses, sorts and writes min(n, 256)
+ * keys; then the merge of drn_shortlist_topn (n <= DRN_SHORTLIST_MAX) or of drn_shortlist_deep (above).  With M = 1 and w = 1 this
+ * ranks ANY score matrix under the total order: 0 + 1 * s is exact.
+ * drn_shortlist_fuse_rank answers drn_shortlist_rank's three fields under the fused score: targets [S] int32 on the device (a value
+ * outside [0, V) means "no target" and is clamped for every read), rank = the candidates whose fused key precedes the target's (-1
+ * where the target is no candidate), score = the target's fused score (0 beside -1), total = the candidates.  ONE launch, one
+ * workgroup per sentence walks the V videos; no workspace.
+ * allow: a packed mask as in the *_allow entries, or NULL.  scores and weights are 4-byte aligned.  No atomics, no host
+ * synchronisation; the matrices, the weights, the targets and the mask may change between replays of a captured graph. */
+#define DRN_FUSE_MAX_TABLES 8
+#define DRN_FUSE_DROP 0
+#define DRN_FUSE_SKIP 1
+int drn_shortlist_fuse_topn(const float* scores, long long stride_m, int ld, const float* weights, int M, int mode, const int32_t* allow,
+                            int allow_stride, int V, int S, int n, void* ws, int ws_keys, int32_t* ids, float* out_scores, int32_t* counts,
+                            void* stream);
+int drn_shortlist_fuse_rank(const float* scores, long long stride_m, int ld, const float* weights, int M, int mode, const int32_t* targets,
+                            const int32_t* allow, int allow_stride, int V, int S, int32_t* rank, float* score, int32_t* total, void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the

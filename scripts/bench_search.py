@@ -148,7 +148,15 @@
            index_add_, a divide, a cast, Shortlister(...) -- by a host clock to a device synchronise, the two taking turns in every
            round, every field asserted equal to pool_segments_reference (evaluated on the host) before timing.  The condition:
            pooled() takes no longer than that route beyond the route's own max - min, HOLDS / DOES NOT HOLD per shape, no absolute
-           time required.  For orientation only: the bytes read and written over 8 TB/s."""
+           time required.  For orientation only: the bytes read and written over 8 TB/s.
+
+  --fused-shortlist   instead of the above -> profiles/search_fused_shortlist_bench.json, on 65,536 rows x 512 bf16 at S = 1 / 8 / 64,
+           launch-inclusive us from device events around windows of back-to-back calls, the variants taking turns in every round:
+           (a) Shortlister.scores beside shortlist(q, 16) on the same table, 65,536 x 1 plain and 4,096 x 16 ragged -- the derived
+           condition: scores() takes no longer than shortlist() beyond that launch's own max - min, HOLDS / MISSED per shape, no
+           absolute time required; (b) FusedShortlister.shortlist at M = 2, the 4,096 x 16 ragged table and its pooled table, beside
+           torch.matmul per table + scatter_reduce_(amax) + the weighted sum + torch.topk, the fused list asserted equal to
+           fused_shortlist_reference of the tables' own scores() before timing."""
 import argparse
 import json
 import os
@@ -2640,6 +2648,91 @@ def main_pooled(args):
     print("wrote", out)
 
 
+def bench_fused_shortlist(emb, S, rounds, n=16):
+    """(a) Shortlister.scores beside shortlist(q, n) on the same table, plain (65,536 x 1) and ragged (4,096 x 16); (b)
+    FusedShortlister.shortlist at M = 2 -- the 4,096 x 16 ragged table and its pooled table over the same 4,096 videos -- beside what a
+    caller can do without it: torch.matmul per table, scatter_reduce_(amax), the weighted sum, torch.topk.  The fused list is asserted
+    equal to fused_shortlist_reference of the tables' own scores() before timing."""
+    import numpy as np
+    from drn_amd import FusedShortlister, Shortlister, fused_shortlist_reference
+    R = int(emb.shape[0])
+    g = torch.Generator(device="cuda:0").manual_seed(S + 4096)
+    q = torch.randn(S, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    rows = []
+    tables = {}
+    for name, lens in (SEGMENT_LAYOUTS[0], SEGMENT_LAYOUTS[1]):
+        V = len(lens)
+        sl = Shortlister(emb, offsets=np.concatenate([[0], np.cumsum(lens)]) if V != R else None)
+        tables[name] = sl
+        out_l = type(sl.shortlist(q, 1))(*sl.shortlist(q, n))
+        out_s = sl.scores(q)
+        assert torch.equal(torch.gather(out_s, 1, out_l.ids.long()).view(torch.int32), out_l.scores.view(torch.int32)), (name, S)
+        times, reps = interleaved_windows({"shortlist": lambda: sl.shortlist(q, n, out=out_l), "scores": lambda: sl.scores(q, out=out_s)}, rounds)
+        base, new = times["shortlist"], times["scores"]
+        over = statistics.median(new) - statistics.median(base)
+        rows.append({"report": "a", "layout": name, "R": R, "V": V, "E": 512, "S": S, "n": n, "dtype": "bf16", "launches_per_window": reps,
+                     "shortlist_us": spread(base), "scores_us": spread(new), "scores_bytes_written": 4 * S * V,
+                     "scores_over_shortlist": statistics.median(new) / statistics.median(base), "scores_minus_shortlist_us": over,
+                     "shortlist_max_minus_min_us": max(base) - min(base), "holds": over <= max(base) - min(base),
+                     "scores_against_shortlist": verdict(new, base)})
+    fine = tables[SEGMENT_LAYOUTS[1][0]]
+    coarse = fine.pooled()
+    V, lens = len(fine), SEGMENT_LAYOUTS[1][1]
+    w = [1.0, 0.5]
+    fused = FusedShortlister([fine, coarse], weights=w)
+    out_f = fused.shortlist([q, q], n)
+    want = fused_shortlist_reference(torch.stack([fine.scores(q), coarse.scores(q)]), w, n)
+    for f in ("ids", "scores", "n"):
+        assert torch.equal(getattr(out_f, f), getattr(want, f)), (S, f, "the fused list is the definition's")
+    index = torch.repeat_interleave(torch.arange(V, device="cuda:0"), torch.as_tensor(lens, device="cuda:0"))[None].expand(S, R).contiguous()
+    best = torch.empty((S, V), dtype=torch.bfloat16, device="cuda:0")
+    pooled = coarse.embeddings
+
+    def torch_way():
+        best.fill_(float("-inf"))
+        best.scatter_reduce_(1, index, torch.matmul(q, emb.t()), "amax")
+        return torch.topk(w[0] * best + w[1] * torch.matmul(q, pooled.t()), n, dim=1)
+    times, reps = interleaved_windows({"fused": lambda: fused.shortlist([q, q], n, out=out_f), "torch": torch_way}, rounds)
+    rows.append({"report": "b", "tables": "4096x16 ragged bf16 + its pooled 4096x1 bf16", "M": 2, "V": V, "E": 512, "S": S, "n": n,
+                 "launches_per_window": reps, "fused_us": spread(times["fused"]), "matmul_amax_sum_topk_us": spread(times["torch"]),
+                 "fused_over_torch": statistics.median(times["fused"]) / statistics.median(times["torch"]),
+                 "fused_against_torch": verdict(times["fused"], times["torch"]),
+                 "note": "the fused call is two score launches and the two launches of drn_shortlist_fuse_topn; torch scores in bf16, sums "
+                         "in bf16 and has no defined tie order: another answer, for orientation"})
+    return rows
+
+
+def main_fused_shortlist(args):
+    out = args.out or os.path.join(ROOT, "profiles", "search_fused_shortlist_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    res = {"device": torch.cuda.get_device_name(0), "measured_on": "MI355X, one process, the tables resident",
+           "method": {"interleaved": True, "statistic": "median [min, max] over rounds of the mean time of a window of ~0.2 s",
+                      "clock": "device events around windows of back-to-back calls issued from Python: launch-inclusive us per call",
+                      "condition": "derived, not measured: scores() does the reads and the MFMA chain of shortlist() and writes 4 * S * V bytes "
+                                   "where the other sorts and merges, so (a) scores() may not take longer than shortlist(q, 16) on the same "
+                                   "table beyond that launch's own max - min.  No number gates the change; a miss is a finding",
+                      "what_this_does_not_say": "random embeddings say nothing about recall; bf16 only: no fp32, no FP8 tables, no masks, no "
+                                                "late interaction; no kernel-only times (no profiler run)"},
+           "fused_shortlist": []}
+    g = torch.Generator(device="cuda:0").manual_seed(65536)
+    emb = torch.randn(65536, 512, generator=g, device="cuda:0").to(torch.bfloat16).contiguous()
+    for S in (1, 8, 64):
+        for row in bench_fused_shortlist(emb, S, args.rounds):
+            res["fused_shortlist"].append(row)
+            print(json.dumps({"fused_shortlist": row}), flush=True)
+            if row["report"] == "a":
+                print("(a) %s S = %d: %s (scores / shortlist = %.3f, %s)" % (row["layout"], S, "HOLDS" if row["holds"] else "MISSED",
+                                                                           row["scores_over_shortlist"], row["scores_against_shortlist"]), flush=True)
+            else:
+                print("(b) S = %d: fused / matmul + amax + sum + topk = %.3f (%s)" % (S, row["fused_over_torch"], row["fused_against_torch"]),
+                      flush=True)
+        json.dump(res, open(out, "w"), indent=1)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (search_pairs_bench.json with --shortlist, search_eval_bench.json with --evaluate, "
@@ -2685,9 +2778,15 @@ def main():
     ap.add_argument("--pooled", action="store_true", help="measure Shortlister.pooled (mean, one row a video and one per 4 rows, bf16 and FP8 "
                                                           "sources) beside index_add_ + divide + cast + Shortlister in torch "
                                                           "(writes profiles/search_pooled_bench.json)")
+    ap.add_argument("--fused-shortlist", action="store_true", help="measure Shortlister.scores beside shortlist(q, 16), and "
+                                                                   "FusedShortlister.shortlist over a ragged table and its pooled table beside "
+                                                                   "matmul + amax + weighted sum + topk in torch "
+                                                                   "(writes profiles/search_fused_shortlist_bench.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_search.py measures on an MI355X; no GPU found")
+    if args.fused_shortlist:
+        return main_fused_shortlist(args)
     if args.pooled:
         return main_pooled(args)
     if args.deep_shortlist:
