@@ -15,3 +15,5 @@ from .retrieve import (LATE_MAX_TOKENS, SHARDS_MAX, SHORTLIST_DEEP_MAX, Compacte
                        slice_allow_reference)
 from .retrieve import (FUSE_MAX_TABLES, FusedShortlister, fuse_scores_reference, fused_rank_reference, fused_shortlist_reference,  # noqa: E402,F401
                        fused_rerank, fused_rerank_reference, rerank_scores_reference, scores_reference, shortlist_scores)
+from .retrieve import (RANK_FUSE_MAX_LISTS, RankFusedShortlister, rank_fuse, rank_fuse_rank, rank_fuse_rank_reference,  # noqa: E402,F401
+                       rank_fuse_reference)

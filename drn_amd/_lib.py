@@ -30,6 +30,7 @@ SHORTLIST_DEEP_MAX = RERANK_MAX_CANDIDATES  # DRN_SHORTLIST_DEEP_MAX: the longes
 RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
 FUSE_MAX_TABLES = 8       # DRN_FUSE_MAX_TABLES: score matrices drn_shortlist_fuse_topn / _rank fold (a choice, not a measurement)
 FUSE_MODES = {"drop": 0, "skip": 1}   # DRN_FUSE_DROP / DRN_FUSE_SKIP
+RANK_FUSE_MAX_LISTS = 8   # DRN_RANK_FUSE_MAX_LISTS: id lists drn_rank_fuse_topn / _rank fuse (a choice: 8 x 1024 words of 8 bytes fill 64 KiB of LDS)
 SHARDS_MAX = 64           # DRN_SHARDS_MAX: tables of one ShardedShortlister, lists a sentence drn_shortlist_merge_lists merges (a choice, not a measurement)
 
 
@@ -238,6 +239,10 @@ SIGNATURES = {
                                 c_void_p, c_void_p],
     "drn_shortlist_fuse_rerank": [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_rank_fuse_topn": [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                           c_void_p, c_void_p, c_void_p],
+    "drn_rank_fuse_rank": [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p],
     "drn_plan_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 

@@ -8,6 +8,7 @@
 //                             of a row belonging to the video candidates[s][j]: the fused second stage of a cascade.
 #include "common.h"
 #include "shortlist.h"
+#include "fuse.h"
 #include "../../include/drn_hip.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -318,16 +319,7 @@ __global__ __launch_bounds__(256) void scores_late_kernel(const Op op, const typ
 // ---------------------------------------------------------------------------------------------------------------------------
 // THE FUSED SCORE of (sentence s, video v) over M stacked matrices, and its key.  The order is the definition's
 // (drn_amd.retrieve.fuse_scores_reference): acc = +0, then for m ascending acc = acc + (w[m] * x_m), every product and every sum rounded
-// on its own.  hipcc contracts a + b * c into one FMA by default, and __fmul_rn / __fadd_rn are plain operators in its headers, which
-// contract all the same once inlined: the two helpers below switch contraction off where the operators stand.
-__device__ __forceinline__ float fu_mul(const float a, const float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float fu_add(const float a, const float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
+// on its own, by fu_mul and fu_add of fuse.h, which keep hipcc from contracting the two into one FMA.
 
 // `at` = s * ld + v.  Key 0 where the pair is no candidate: the fold is not finite, the mask bit is clear, or (drop) a term is not
 // finite / (skip) none is.
@@ -470,16 +462,6 @@ static void fs_launch(const Op op, const FsArgs& a, hipStream_t stream) {
   else
     scores_late_kernel<Op><<<dim3(a.nblocks, a.S), 256, 0, stream>>>(op, q, a.lengths, a.offsets, a.blk_vid, a.allow, stride, a.R, a.V, a.E, a.L,
                                                                      a.out, a.ld_out);
-}
-
-static int fu_check_allow(const char* what, const int32_t* allow, int allow_stride, int V) {
-  if (allow) {
-    DRN_CHECK_ARG(allow_stride == 0 || allow_stride == cdiv(V, 32),
-                  "%s: allow_stride = %d is neither 0 (one mask for all sentences) nor ceil(V / 32) = %d (one row per sentence)", what,
-                  allow_stride, cdiv(V, 32));
-    DRN_CHECK_ARG(((uintptr_t)allow & 3) == 0, "%s: the mask must be 4-byte aligned", what);
-  }
-  return DRN_OK;
 }
 
 extern "C" int drn_shortlist_scores(const void* table, const uint8_t* scales, const void* queries, const int32_t* lengths,

@@ -2092,6 +2092,72 @@ def shortlist_fuse_rerank(scores, weights, missing, candidates, V, n, ws, ids, o
     return ids, out_scores, counts
 
 
+def _rank_fuse_args(what, lists, V, weights, k0, missing, allow):
+    """The checks the two rank-fusion wrappers share -> (M, S, C, V, stride_m, ld, k0, mode, mask pointer, allow_stride)."""
+    if missing not in _lib.FUSE_MODES:
+        raise _lib.DrnError("%s: missing must be one of %s, not %r" % (what, sorted(_lib.FUSE_MODES), missing))
+    if lists.dim() != 3 or lists.dtype != torch.int32 or not 1 <= lists.shape[0] <= _lib.RANK_FUSE_MAX_LISTS or lists.shape[1] < 1 \
+            or not 1 <= lists.shape[2] <= _lib.SHORTLIST_DEEP_MAX:
+        raise _lib.DrnError("%s: lists must be (M, S, C) torch.int32 with 1 <= M <= %d, S >= 1 and 1 <= C <= %d, not %s %s"
+                            % (what, _lib.RANK_FUSE_MAX_LISTS, _lib.SHORTLIST_DEEP_MAX, lists.dtype, tuple(lists.shape)))
+    M, S, C = (int(x) for x in lists.shape)
+    ld = _row_strided(lists[0], S, C)
+    stride_m = int(lists.stride(0)) if M > 1 else 0
+    if ld is None or (M > 1 and stride_m < (S - 1) * ld + C):
+        raise _lib.DrnError("%s: lists must have last stride 1, row stride >= C and lists that do not overlap, not strides %s"
+                            % (what, tuple(lists.stride())))
+    V, k0 = int(V), float(k0)
+    if V < 1:
+        raise _lib.DrnError("%s: V = %d videos, at least one is needed" % (what, V))
+    if not (0.0 <= k0 < float("inf")):
+        raise _lib.DrnError("%s: k0 = %r is not a finite number >= 0" % (what, k0))
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (M,) or not weights.is_contiguous():
+        raise _lib.DrnError("%s: weights must be a contiguous (%d,) torch.float32 tensor on the device" % (what, M))
+    mask, stride = _allow_args(what, allow, V, S)
+    return M, S, C, V, stride_m, ld, k0, _lib.FUSE_MODES[missing], mask, stride
+
+
+def rank_fuse_topn(lists, V, weights, k0, missing, n, ids, scores, counts, allow=None):
+    """Each sentence's best n videos under RECIPROCAL-RANK FUSION of M id lists (drn_rank_fuse_topn;
+    drn_amd.retrieve.rank_fuse_reference is the definition): lists (M, S, C) int32 on the device, last stride 1, row stride >= C --
+    other shortlists' ids, -1 padding, repeats and out-of-range values included; V the videos of the store the positions index;
+    weights (M,) float32 ON THE DEVICE; k0 a finite host number >= 0; missing "skip" -- a list that does not hold the video adds
+    nothing -- or "drop" -- every list must hold it; 1 <= n <= SHORTLIST_DEEP_MAX -> ids, scores (S, n) and counts (S,), written in
+    place, -1 / 0 past the list.  The score is the fp32 sum, m ascending, of w[m] / (k0 + rank in list m + 1).  allow: None, or a packed
+    mask as in shortlist_topn.  One launch (tag rank_fuse_topn), no workspace; nothing is read on the host."""
+    what = "rank_fuse_topn"
+    _need_gpu(lists, weights, ids, scores, counts, *(() if allow is None else (allow,)))
+    M, S, C, V, stride_m, ld, k0, mode, mask, stride = _rank_fuse_args(what, lists, V, weights, k0, missing, allow)
+    n = int(n)
+    if not 1 <= n <= _lib.SHORTLIST_DEEP_MAX:
+        raise _lib.DrnError("%s: n = %d outside [1, %d]" % (what, n, _lib.SHORTLIST_DEEP_MAX))
+    for name, t, dt, shape in (("ids", ids, torch.int32, (S, n)), ("scores", scores, torch.float32, (S, n)), ("counts", counts, torch.int32, (S,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous %s %s tensor" % (what, name, shape, dt))
+    _timed(what, 2.0 * M * S * C, lambda: check(lib().drn_rank_fuse_topn(
+        _p(lists), stride_m, ld, C, M, V, _p(weights), k0, mode, mask, stride, S, n, _p(ids), _p(scores), _p(counts), _stream()),
+        "drn_rank_fuse_topn"))
+    return ids, scores, counts
+
+
+def rank_fuse_rank(lists, V, weights, k0, missing, targets, rank, score, total, allow=None):
+    """The place of targets[s] in sentence s's full order under reciprocal-rank fusion (drn_rank_fuse_rank;
+    drn_amd.retrieve.rank_fuse_rank_reference is the definition): lists, V, weights, k0, missing and allow as in rank_fuse_topn; targets
+    (S,) int32 ON THE DEVICE, a value outside [0, V) meaning "no target" -> rank, score, total (S,) as in shortlist_rank, written in
+    place.  One launch (tag rank_fuse_rank), no workspace; nothing is read on the host."""
+    what = "rank_fuse_rank"
+    _need_gpu(lists, weights, targets, rank, score, total, *(() if allow is None else (allow,)))
+    M, S, C, V, stride_m, ld, k0, mode, mask, stride = _rank_fuse_args(what, lists, V, weights, k0, missing, allow)
+    for name, t, dt in (("targets", targets, torch.int32), ("rank", rank, torch.int32), ("score", score, torch.float32),
+                        ("total", total, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+            raise _lib.DrnError("%s: %s must be a contiguous (%d,) %s tensor" % (what, name, S, dt))
+    _timed(what, 2.0 * M * S * C, lambda: check(lib().drn_rank_fuse_rank(
+        _p(lists), stride_m, ld, C, M, V, _p(weights), k0, mode, mask, stride, S, _p(targets), _p(rank), _p(score), _p(total), _stream()),
+        "drn_rank_fuse_rank"))
+    return rank, score, total
+
+
 def shortlist_merge_lists(in_ids, in_scores, in_counts, in_rows, bases, n, ids, scores, counts, rows=None):
     """Merge K stacked per-shard lists a sentence into the corpus's list: in_ids, in_scores (K, S, n_in) and in_counts (K, S) as the
     shards' shortlist entries wrote them, in_rows (K, S, n_in) beside them on ragged shards or None, bases (K + 1,) int32 ON THE DEVICE

@@ -89,7 +89,14 @@ column j the score rerank() would list for the pair (s, candidates[s, j]) and -i
 (rerank_scores_reference; drn_shortlist_rerank_scores, csrc/retrieve_rerank.hip: the rerank kernel up to its sums, one launch), and
 fused_rerank(fused, candidates, queries, n) is the fused SECOND stage of a cascade: M such matrices, unmasked, then one ranking of
 candidate slots under the fold and the total order above (fused_rerank_reference: the fused shortlist under the mask "listed, and
-allowed"; drn_shortlist_fuse_rerank, csrc/retrieve_fuse.hip).  Only the listed videos' rows of every table are read."""
+allowed"; drn_shortlist_fuse_rerank, csrc/retrieve_fuse.hip).  Only the listed videos' rows of every table are read.
+
+rank_fuse / rank_fuse_rank and RankFusedShortlister fuse BY RANK, for tables whose scores share no scale (a dot product against a sum
+over 64 tokens): reciprocal-rank fusion of M finished id lists -- list m votes w[m] / (k0 + rank + 1) for each video it holds, the rank
+being the column of the video's first occurrence, the votes added in fp32 in list order, the sums ranked under the total order, which
+decides the constant ties of reciprocal ranks the same way in every run.  rank_fuse_reference and rank_fuse_rank_reference are the
+definitions, drn_rank_fuse_topn / _rank (csrc/retrieve_rrf.hip) the launches: one workgroup a sentence sorts the M * C <= 8192 entries
+in LDS, folds and sorts again; no dense buffer, no second read of any table."""
 import collections
 import numbers
 
@@ -97,7 +104,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import (FUSE_MAX_TABLES, FUSE_MODES, LATE_MAX_TOKENS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_DEEP_MAX, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK,
+from ._lib import (FUSE_MAX_TABLES, FUSE_MODES, LATE_MAX_TOKENS, RANK_FUSE_MAX_LISTS, RERANK_MAX_CANDIDATES, SHARDS_MAX, SHORTLIST_BLOCK, SHORTLIST_DEEP_MAX, SHORTLIST_MAX, SHORTLIST_SEG_BLOCK,
                    DrnError)      # SHORTLIST_MAX = 128 and SHARDS_MAX = 64 are CHOICES, not measurements (see _lib.py, include/drn_hip.h)
 from .index import MX8_BLOCK, MX8_EMIN, QUANTIZE, mx8_dequantize, mx8_quantize
 
@@ -387,6 +394,113 @@ def fused_rerank_reference(scores, weights, candidates, V, n, missing="drop", al
     where = torch.where(first, c, torch.full_like(c, V))
     stack.scatter_(2, where[None].expand(M, S, C), sc)
     return fused_shortlist_reference(stack[:, :, :V].contiguous().to(dev), w, n, missing=missing, allow=allow)
+
+
+def _check_k0(what, k0):
+    """k0 of a rank fusion: a host number, rounded to float32, finite and >= 0 -> the rounded value as a Python float."""
+    if isinstance(k0, bool) or not isinstance(k0, numbers.Real):
+        raise DrnError("%s: k0 must be a host number, not %s" % (what, type(k0).__name__))
+    with np.errstate(over="ignore"):
+        k0 = float(np.float32(k0))
+    if not 0.0 <= k0 < float("inf"):
+        raise DrnError("%s: k0 = %r is not a finite number >= 0 (in float32)" % (what, k0))
+    return k0
+
+
+def _rank_fuse_lists(what, lists, V):
+    """What the rank-fusion functions take as lists -> (a list of M (S, C_m) integer tensors on one device, S, V)."""
+    V = int(V)
+    if V < 1:
+        raise DrnError("%s: V = %d videos, at least one is needed" % (what, V))
+    if torch.is_tensor(lists):
+        if lists.dim() != 3:
+            raise DrnError("%s: a lists tensor must be (M, S, C), not %s" % (what, tuple(lists.shape)))
+        lists = list(lists.unbind(0))
+    else:
+        try:
+            lists = list(lists)
+        except TypeError:
+            raise DrnError("%s: lists must be an (M, S, C) tensor or a sequence of (S, C_m) tensors" % what)
+    if not 1 <= len(lists) <= RANK_FUSE_MAX_LISTS:
+        raise DrnError("%s: %d lists outside [1, %d]" % (what, len(lists), RANK_FUSE_MAX_LISTS))
+    for m, t in enumerate(lists):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise DrnError("%s: list %d must be an integer tensor (S, C), a row of store positions per sentence" % (what, m))
+        if int(t.shape[0]) != int(lists[0].shape[0]) or t.shape[0] < 1:
+            raise DrnError("%s: list %d holds %d sentences, list 0 holds %d" % (what, m, int(t.shape[0]), int(lists[0].shape[0])))
+        if not 1 <= int(t.shape[1]) <= SHORTLIST_DEEP_MAX:
+            raise DrnError("%s: list %d has C = %d entries a sentence outside [1, %d]" % (what, m, int(t.shape[1]), SHORTLIST_DEEP_MAX))
+        if t.device != lists[0].device:
+            raise DrnError("%s: list %d is on %s, list 0 on %s" % (what, m, t.device, lists[0].device))
+    return lists, int(lists[0].shape[0]), V
+
+
+def _rank_fuse_scores(what, lists, V, weights, k0, missing, allow):
+    """What the two rank-fusion references share -> (fused (S, V) float32, candidate (S, V) bool) on the lists' device, by tensor
+    operations alone: nothing is read on the host."""
+    if missing not in FUSE_MODES:
+        raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
+    lists, S, V = _rank_fuse_lists(what, lists, V)
+    M, dev = len(lists), lists[0].device
+    k0 = torch.full((), _check_k0(what, k0), dtype=torch.float32, device=dev)
+    if weights is None:
+        w = torch.ones(M, dtype=torch.float32, device=dev)
+    elif torch.is_tensor(weights):
+        w = weights.to(dev)
+    else:
+        try:
+            w = torch.tensor([float(x) for x in weights], dtype=torch.float32).to(dev)
+        except (TypeError, ValueError):
+            raise DrnError("%s: weights must be None, %d numbers or a float32 (%d,) tensor" % (what, M, M))
+    if tuple(w.shape) != (M,) or w.dtype != torch.float32:
+        raise DrnError("%s: weights must be %d float32 numbers, one per list, not %s %s" % (what, M, w.dtype, tuple(w.shape)))
+    acc = torch.zeros((S, V), dtype=torch.float32, device=dev)
+    held = torch.zeros((S, V), dtype=torch.int32, device=dev)
+    for m, c in enumerate(lists):
+        c = c.to(torch.int64)
+        C = int(c.shape[1])
+        valid = (c >= 0) & (c < V)
+        # the column of the FIRST occurrence of every video: the minimum over the columns that hold it (column V collects the junk)
+        first = torch.full((S, V + 1), C, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(1, torch.where(valid, c, torch.full_like(c, V)), torch.arange(C, device=dev)[None, :].expand(S, C), "amin")
+        j = first[:, :V]
+        holds = j < C
+        term = w[m] / (k0 + (j + 1).to(torch.float32))          # (one add, one division: each rounded to float32 on its own)
+        acc = torch.where(holds, acc + term, acc)
+        held = held + holds.to(torch.int32)
+    candidate = torch.isfinite(acc) & (held == M if missing == "drop" else held > 0)
+    if allow is not None:
+        candidate = candidate & _allowed(allow, S, V, dev)
+    return acc + 0.0, candidate
+
+
+def rank_fuse_reference(lists, V, n, weights=None, k0=60.0, missing="skip", allow=None):
+    """THE DEFINITION of rank_fuse: reciprocal-rank fusion (RRF) of M id lists over the same V videos, in float32 (usable on the CPU,
+    and on any device without a host synchronisation) -> Shortlist on the lists' device.  lists: an (M, S, C) integer tensor or a
+    sequence of M (S, C_m) integer tensors, 1 <= M <= RANK_FUSE_MAX_LISTS, 1 <= C_m <= SHORTLIST_DEEP_MAX -- other shortlists' ids as
+    they lie on the device.  The entries mean what candidates_mask says: a value outside [0, V) means nothing (-1, V, INT_MIN,
+    INT_MAX), and of a position repeated in one row the first occurrence counts.  THE RANK of video v in list m is the column j of
+    its first occurrence: for any list a shortlist produces that is its place in the list, because the padding sits at the end.
+    weights: M numbers (None: all ones) or a float32 (M,) tensor; k0: a host number rounded to float32, finite and >= 0 (anything else
+    is refused).  The order is FIXED, every operation rounded to float32 on its own:
+        acc = +0;  for m = 0 .. M - 1 ascending, where list m holds v at rank j:  acc = acc + w[m] / (k0 + float(j + 1))
+    missing="skip" (standard RRF): a list that does not hold v adds nothing, and v is a candidate when any list holds it;
+    missing="drop": every list must hold v.  A video whose acc is not finite is no candidate (the weights may hold anything), nor is
+    one that allow (a bool tensor (V,) or (S, V)) excludes.  The candidates are listed by higher acc, then lower position, cut to n;
+    -1 / 0 past the list.  With M = 1 and w = 1 the ids are the list's distinct valid entries in order.
+    What this is NOT: a fusion of scores -- the votes depend on the lists alone and so on the DEPTH they were cut at: a video just
+    past a list's end gets nothing from it.  Subnormal terms follow IEEE here; the kernels are tested away from them."""
+    fused, candidate = _rank_fuse_scores("rank_fuse_reference", lists, V, weights, k0, missing, allow)
+    ids, listed, count, _ = _listed(fused.double(), candidate, _check_depth("rank_fuse_reference", n))
+    return Shortlist(ids, listed, count)
+
+
+def rank_fuse_rank_reference(lists, V, targets, weights=None, k0=60.0, missing="skip", allow=None):
+    """THE DEFINITION of rank_fuse_rank: rank_reference's answer (_ranked) from rank_fuse_reference's fused scores and candidates, so
+    rank[s] = k >= 0 exactly when rank_fuse_reference(..., n).ids[s, k] is the target for every n > k; total is the number of fused
+    candidates.  -> TargetRank on the lists' device."""
+    fused, candidate = _rank_fuse_scores("rank_fuse_rank_reference", lists, V, weights, k0, missing, allow)
+    return _ranked(fused.double(), candidate, targets)
 
 
 SegmentShortlist = collections.namedtuple("SegmentShortlist", "ids scores n rows")
@@ -754,6 +868,30 @@ def _list_buffers(dev, S, n, rows=False):
     out = (torch.empty((S, n), dtype=torch.int32, device=dev), torch.empty((S, n), dtype=torch.float32, device=dev),
            torch.empty((S,), dtype=torch.int32, device=dev))
     return out + (torch.empty((S, n), dtype=torch.int32, device=dev),) if rows else out
+
+
+def _check_targets(what, S, targets, dev):
+    """What every rank refuses about targets on dev, before the library is reached."""
+    if not torch.is_tensor(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (S,) or not targets.is_contiguous():
+        raise DrnError("%s: targets must be a contiguous (%d,) torch.int32 tensor, the store position of each sentence's video" % (what, S))
+    if not targets.is_cuda or targets.device != dev:
+        raise DrnError("%s: targets must be on the table's device %s (they are never read on the host)" % (what, dev))
+
+
+def _check_rank_out(what, S, out):
+    """out= of a method that returns a TargetRank: None, or the three buffers of its shapes and dtypes."""
+    if out is not None:
+        if len(out) != 3:
+            raise DrnError("%s: out must hold the three buffers of a TargetRank (rank, score, total), not %d" % (what, len(out)))
+        for name, t, dt in zip(TargetRank._fields, out, (torch.int32, torch.float32, torch.int32)):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
+                raise DrnError("%s: out.%s must be a contiguous (%d,) %s tensor on the GPU" % (what, name, S, dt))
+
+
+def _rank_buffers(dev, S):
+    """The result buffers (rank, score, total) of S sentences, made on dev."""
+    return (torch.empty((S,), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.float32, device=dev),
+            torch.empty((S,), dtype=torch.int32, device=dev))
 
 
 def _refuse_late(what, instead, whose="this table has"):
@@ -1451,28 +1589,15 @@ class Shortlister(object):
 
     def _check_targets(self, what, S, targets):
         """What every rank refuses about targets, before the library is reached."""
-        dev = self._table().device
-        if not torch.is_tensor(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (S,) or not targets.is_contiguous():
-            raise DrnError("%s: targets must be a contiguous (%d,) torch.int32 tensor, the store position of each sentence's video" % (what, S))
-        if not targets.is_cuda or targets.device != dev:
-            raise DrnError("%s: targets must be on the table's device %s (they are never read on the host)" % (what, dev))
+        _check_targets(what, S, targets, self._table().device)
 
     def _check_rank(self, what, S, targets, out, allow):
         """What rank() and rank_late() refuse about targets, out= and allow=, before the library is reached -> out, made where None."""
-        dev = self._table().device
         self._check_targets(what, S, targets)
-        if out is not None:
-            if len(out) != 3:
-                raise DrnError("%s: out must hold the three buffers of a TargetRank (rank, score, total), not %d" % (what, len(out)))
-            for name, t, dt in zip(TargetRank._fields, out, (torch.int32, torch.float32, torch.int32)):
-                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (S,) or not t.is_contiguous():
-                    raise DrnError("%s: out.%s must be a contiguous (%d,) %s tensor on the GPU" % (what, name, S, dt))
+        _check_rank_out(what, S, out)
         if allow is not None:
             self._check_allow(allow, S)
-        if out is None:
-            out = (torch.empty((S,), dtype=torch.int32, device=dev), torch.empty((S,), dtype=torch.float32, device=dev),
-                   torch.empty((S,), dtype=torch.int32, device=dev))
-        return tuple(out)
+        return _rank_buffers(self._table().device, S) if out is None else tuple(out)
 
     def rank(self, queries, targets, out=None, allow=None):
         """The place of each sentence's TARGET video in its full shortlist order -> TargetRank (rank_reference defines it; on a ragged
@@ -2264,6 +2389,80 @@ def shortlist_scores(scores, n, allow=None, out=None):
     return Shortlist(*out)
 
 
+def _fused_tables(what, tables, missing, cap):
+    """What FusedShortlister and RankFusedShortlister refuse about their tables and `missing` -> (the tables as a list, the names of
+    the first table that has any): 1 to cap tables over the same videos on one device, equal names position by position."""
+    try:
+        tables = list(tables)
+    except TypeError:
+        raise DrnError("%s: the tables must be a sequence of Shortlister / ShardedShortlister objects" % what)
+    if not 1 <= len(tables) <= cap:
+        raise DrnError("%s: %d tables outside [1, %d]" % (what, len(tables), cap))
+    if missing not in FUSE_MODES:
+        raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
+    names = None
+    for m, table in enumerate(tables):
+        if not isinstance(table, (Shortlister, ShardedShortlister)):
+            raise DrnError("%s: table %d must be a Shortlister or a ShardedShortlister, not %s" % (what, m, type(table).__name__))
+        if len(table) != len(tables[0]):
+            raise DrnError("%s: table %d holds %d videos, table 0 holds %d: the tables must rank the same videos, position by position"
+                           % (what, m, len(table), len(tables[0])))
+        if table.device != tables[0].device:
+            raise DrnError("%s: table %d is on %s, table 0 on %s" % (what, m, table.device, tables[0].device))
+        if table.names is not None:
+            if names is not None and list(table.names) != names:
+                raise DrnError("%s: the names of table %d are not those of the tables before it (position v must be the same video "
+                               "in every table)" % (what, m))
+            names = list(table.names)
+    return tables, names
+
+
+def _fused_weights(what, weights, M, dev, things):
+    """The weights of a fusion of M `things` ("tables", "lists") on dev -> a float32 (M,) tensor on dev: None is all ones, host numbers
+    are rounded to fp32 and uploaded ONCE through pinned memory, a device tensor is checked and kept BY REFERENCE."""
+    if weights is None:
+        w = torch.ones(M, dtype=torch.float32)
+    elif torch.is_tensor(weights):
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (M,) or not weights.is_contiguous():
+            raise DrnError("%s: a weights tensor must be contiguous (%d,) torch.float32, one weight per %s, not %s %s"
+                           % (what, M, things[:-1], weights.dtype, tuple(weights.shape)))
+        if weights.device != dev:
+            raise DrnError("%s: a weights tensor must be on the %s' device %s (it is kept by reference and never read on the "
+                           "host); pass a host sequence to have it uploaded" % (what, things, dev))
+        return weights
+    else:
+        try:
+            w = torch.tensor([float(x) for x in weights], dtype=torch.float32)
+        except (TypeError, ValueError):
+            raise DrnError("%s: weights must be None, %d numbers or a float32 (%d,) tensor on the device" % (what, M, M))
+        if tuple(w.shape) != (M,):
+            raise DrnError("%s: %d weights for %d %s" % (what, int(w.shape[0]), M, things))
+    return w.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else w
+
+
+def _check_fused_items(what, tables, queries):
+    """What FusedShortlister and RankFusedShortlister refuse about the M query items, one per table, ALL before the first launch ->
+    (S, [(queries, lengths)] * M)."""
+    M = len(tables)
+    if not isinstance(queries, (list, tuple)) or len(queries) != M:
+        raise DrnError("%s: queries must be a sequence of %d items, one per table: what the table's scores() takes, or a pair "
+                       "(queries, lengths) for its scores_late()" % (what, M))
+    items, S = [], None
+    for m, (table, item) in enumerate(zip(tables, queries)):
+        q, lengths = (item[0], item[1]) if isinstance(item, (list, tuple)) and len(item) == 2 else (item, None)
+        if isinstance(item, (list, tuple)) and len(item) != 2:
+            raise DrnError("%s: item %d must be a queries tensor or a pair (queries, lengths)" % (what, m))
+        first = table if isinstance(table, Shortlister) else table.shards[0]
+        if lengths is not None and not torch.is_tensor(lengths):
+            raise DrnError("%s: the lengths of item %d must be a contiguous torch.int32 tensor on the device" % (what, m))
+        Sm = first._check_rank_queries("%s (table %d)" % (what, m), q, lengths)
+        if S is not None and Sm != S:
+            raise DrnError("%s: item %d holds %d sentences, item 0 holds %d" % (what, m, Sm, S))
+        S = Sm
+        items.append((q if lengths is not None else q.contiguous(), lengths))
+    return S, items
+
+
 class FusedShortlister(object):
     """FusedShortlister(tables, weights=None, missing="drop"): ONE ranking of several tables over the same videos -- a visual window
     table, a subtitle table, a pooled coarse table, an FP8 copy: score[s, v] = w_0 * score_0[s, v] + w_1 * score_1[s, v] + ..., each
@@ -2289,48 +2488,8 @@ class FusedShortlister(object):
 
     def __init__(self, tables, weights=None, missing="drop"):
         what = "FusedShortlister"
-        try:
-            tables = list(tables)
-        except TypeError:
-            raise DrnError("%s: the tables must be a sequence of Shortlister / ShardedShortlister objects" % what)
-        if not 1 <= len(tables) <= FUSE_MAX_TABLES:
-            raise DrnError("%s: %d tables outside [1, %d]" % (what, len(tables), FUSE_MAX_TABLES))
-        if missing not in FUSE_MODES:
-            raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
-        names = None
-        for m, table in enumerate(tables):
-            if not isinstance(table, (Shortlister, ShardedShortlister)):
-                raise DrnError("%s: table %d must be a Shortlister or a ShardedShortlister, not %s" % (what, m, type(table).__name__))
-            if len(table) != len(tables[0]):
-                raise DrnError("%s: table %d holds %d videos, table 0 holds %d: the tables must rank the same videos, position by position"
-                               % (what, m, len(table), len(tables[0])))
-            if table.device != tables[0].device:
-                raise DrnError("%s: table %d is on %s, table 0 on %s" % (what, m, table.device, tables[0].device))
-            if table.names is not None:
-                if names is not None and list(table.names) != names:
-                    raise DrnError("%s: the names of table %d are not those of the tables before it (position v must be the same video "
-                                   "in every table)" % (what, m))
-                names = list(table.names)
-        M, dev = len(tables), tables[0].device
-        if weights is None:
-            w = torch.ones(M, dtype=torch.float32)
-        elif torch.is_tensor(weights):
-            if weights.dtype != torch.float32 or tuple(weights.shape) != (M,) or not weights.is_contiguous():
-                raise DrnError("%s: a weights tensor must be contiguous (%d,) torch.float32, one weight per table, not %s %s"
-                               % (what, M, weights.dtype, tuple(weights.shape)))
-            if weights.device != dev:
-                raise DrnError("%s: a weights tensor must be on the tables' device %s (it is kept by reference and never read on the "
-                               "host); pass a host sequence to have it uploaded" % (what, dev))
-            w = None
-        else:
-            try:
-                w = torch.tensor([float(x) for x in weights], dtype=torch.float32)
-            except (TypeError, ValueError):
-                raise DrnError("%s: weights must be None, %d numbers or a float32 (%d,) tensor on the device" % (what, M, M))
-            if tuple(w.shape) != (M,):
-                raise DrnError("%s: %d weights for %d tables" % (what, int(w.shape[0]), M))
-        if w is not None:
-            weights = w.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else w
+        tables, names = _fused_tables(what, tables, missing, FUSE_MAX_TABLES)
+        weights = _fused_weights(what, weights, len(tables), tables[0].device, "tables")
         self.tables, self.weights, self.missing, self.names = tables, weights, missing, names
         self._bufs = {}
 
@@ -2343,24 +2502,7 @@ class FusedShortlister(object):
 
     def _check_items(self, what, queries):
         """What shortlist() and rank() refuse about the M query items, ALL before the first launch -> (S, [(queries, lengths)] * M)."""
-        M = len(self.tables)
-        if not isinstance(queries, (list, tuple)) or len(queries) != M:
-            raise DrnError("%s: queries must be a sequence of %d items, one per table: what the table's scores() takes, or a pair "
-                           "(queries, lengths) for its scores_late()" % (what, M))
-        items, S = [], None
-        for m, (table, item) in enumerate(zip(self.tables, queries)):
-            q, lengths = (item[0], item[1]) if isinstance(item, (list, tuple)) and len(item) == 2 else (item, None)
-            if isinstance(item, (list, tuple)) and len(item) != 2:
-                raise DrnError("%s: item %d must be a queries tensor or a pair (queries, lengths)" % (what, m))
-            first = table if isinstance(table, Shortlister) else table.shards[0]
-            if lengths is not None and not torch.is_tensor(lengths):
-                raise DrnError("%s: the lengths of item %d must be a contiguous torch.int32 tensor on the device" % (what, m))
-            Sm = first._check_rank_queries("%s (table %d)" % (what, m), q, lengths)
-            if S is not None and Sm != S:
-                raise DrnError("%s: item %d holds %d sentences, item 0 holds %d" % (what, m, Sm, S))
-            S = Sm
-            items.append((q if lengths is not None else q.contiguous(), lengths))
-        return S, items
+        return _check_fused_items(what, self.tables, queries)
 
     def _stack(self, what, S, items):
         """The M score launch groups (K launches on a sharded table), UNMASKED, into the stacked (M, S, V) buffer kept per S."""
@@ -2458,3 +2600,220 @@ def fused_rerank(fused, candidates, queries, n=None, out=None, allow=None):
         table._rerank_scores(what, S, C, candidates, q if lengths is not None else q.view(S, 1, -1), lengths, buf[m], None)
     ops.shortlist_fuse_rerank(buf, fused.weights, fused.missing, candidates, len(fused), n, ws, *out, allow=allow)
     return Shortlist(*out)
+
+
+_RANK_FUSE_WEIGHTS = {}   # (device, the host weights as a tuple) -> their tensor on the device: host weights are uploaded ONCE
+_RANK_FUSE_WEIGHTS_KEPT = 64   # uploads kept before the cache is emptied: a CHOICE (a caller whose weights change passes a device tensor)
+
+
+def _rank_fuse_weights(what, weights, M, dev):
+    """weights= of rank_fuse / rank_fuse_rank -> a float32 (M,) tensor on dev: _fused_weights, host numbers cached by value."""
+    if torch.is_tensor(weights):
+        return _fused_weights(what, weights, M, dev, "lists")
+    try:
+        key = (str(dev), tuple(1.0 for _ in range(M)) if weights is None else tuple(float(x) for x in weights))
+    except (TypeError, ValueError):
+        key = None
+    w = _RANK_FUSE_WEIGHTS.get(key)
+    if w is None:
+        w = _fused_weights(what, weights, M, dev, "lists")       # (raises what a bad sequence deserves)
+        if len(_RANK_FUSE_WEIGHTS) >= _RANK_FUSE_WEIGHTS_KEPT:
+            _RANK_FUSE_WEIGHTS.clear()
+        _RANK_FUSE_WEIGHTS[key] = w
+    return w
+
+
+def _check_rank_fuse(what, lists, V, weights, k0, missing, allow):
+    """What rank_fuse and rank_fuse_rank refuse about everything but their results, before the library is reached and before
+    anything is launched -> (lists: the (M, S, C) tensor or the checked sequence, S, V, weights on the device, k0)."""
+    if missing not in FUSE_MODES:
+        raise DrnError("%s: missing must be \"drop\" or \"skip\", not %r" % (what, missing))
+    V = int(V)
+    if V < 1:
+        raise DrnError("%s: V = %d videos, at least one is needed" % (what, V))
+    k0 = _check_k0(what, k0)
+    if torch.is_tensor(lists):
+        seq, dims, shape = [lists], 3, "(M, S, C)"
+    else:
+        try:
+            seq, dims, shape = list(lists), 2, "(S, C)"
+        except TypeError:
+            raise DrnError("%s: lists must be an (M, S, C) torch.int32 tensor on the device or a sequence of (S, C_m) ones" % what)
+        if not 1 <= len(seq) <= RANK_FUSE_MAX_LISTS:
+            raise DrnError("%s: %d lists outside [1, %d]" % (what, len(seq), RANK_FUSE_MAX_LISTS))
+    for m, t in enumerate(seq):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise DrnError("%s: the lists must be tensors on the GPU; there is no CPU fallback (rank_fuse_reference is the definition)" % what)
+        if t.dtype != torch.int32 or t.dim() != dims or not t.is_contiguous() or min(t.shape) < 1:
+            raise DrnError("%s: a list must be a contiguous %s torch.int32 tensor -- another shortlist's ids -- not %s %s"
+                           % (what, shape, t.dtype, tuple(t.shape)))
+        if not 1 <= int(t.shape[-1]) <= SHORTLIST_DEEP_MAX:
+            raise DrnError("%s: C = %d entries a sentence outside [1, %d]" % (what, int(t.shape[-1]), SHORTLIST_DEEP_MAX))
+        if int(t.shape[-2]) != int(seq[0].shape[-2]):
+            raise DrnError("%s: list %d holds %d sentences, list 0 holds %d" % (what, m, int(t.shape[-2]), int(seq[0].shape[-2])))
+        if t.device != seq[0].device:
+            raise DrnError("%s: list %d is on %s, list 0 on %s" % (what, m, t.device, seq[0].device))
+    M = int(lists.shape[0]) if torch.is_tensor(lists) else len(seq)
+    if not 1 <= M <= RANK_FUSE_MAX_LISTS:
+        raise DrnError("%s: %d lists outside [1, %d]" % (what, M, RANK_FUSE_MAX_LISTS))
+    S, dev = int(seq[0].shape[-2]), seq[0].device
+    weights = _rank_fuse_weights(what, weights, M, dev)
+    if allow is not None:
+        _check_packed_allow(allow, S, V, dev)
+    return (lists if torch.is_tensor(lists) else seq), S, V, weights, k0
+
+
+def _stacked_lists(lists):
+    """The checked lists of _check_rank_fuse -> one (M, S, C) int32 tensor: a sequence is copied into a buffer padded with -1, which
+    means nothing, by M + 1 launches and no host synchronisation."""
+    if torch.is_tensor(lists):
+        return lists
+    S, C = int(lists[0].shape[0]), max(int(t.shape[1]) for t in lists)
+    buf = torch.full((len(lists), S, C), -1, dtype=torch.int32, device=lists[0].device)
+    for m, t in enumerate(lists):
+        buf[m, :, :int(t.shape[1])].copy_(t)
+    return buf
+
+
+def rank_fuse(lists, V, n, weights=None, k0=60.0, missing="skip", allow=None, out=None):
+    """RECIPROCAL-RANK FUSION of several shortlists, on the device -> Shortlist (rank_fuse_reference defines it, bit for bit): the
+    fusion for tables whose scores share no scale -- a bf16 window table, an FP8 copy, a pooled coarse table, a late-interaction
+    subtitle table.  List m votes w[m] / (k0 + rank + 1) for each video it holds, the votes are added in fp32 in list order, and the
+    videos are ranked by the sum under the project's total order (sum descending, then position ascending): fused reciprocal ranks
+    tie constantly, and the ties fall the same way in every run and build.
+    lists: a contiguous (M, S, C) torch.int32 tensor on the device, or a sequence of M contiguous (S, C_m) ones, 1 <= M <=
+    RANK_FUSE_MAX_LISTS, 1 <= C_m <= SHORTLIST_DEEP_MAX -- other shortlists' ids as they lie on the device: -1 padding, repeats and
+    out-of-range values mean what candidates_mask says, and a video's rank in a list is the column of its first occurrence.  A
+    sequence is copied into a stacked buffer padded with -1, which by the definition changes nothing.  V: the videos of the store the
+    positions index.  1 <= n <= SHORTLIST_DEEP_MAX.  weights: None (all ones), M host numbers (rounded to fp32 and uploaded ONCE per
+    distinct value and device) or a contiguous float32 (M,) tensor on the device, used BY REFERENCE and never read on the host.  k0: a
+    host number, finite and >= 0 in fp32.  missing: "skip" -- a list that does not hold the video adds nothing (standard RRF) -- or
+    "drop" -- every list must hold it.  allow: a packed mask over the V videos, as in Shortlister.shortlist, applied by the fusing
+    launch: the lists are given.  out: the three buffers of a Shortlist, written in place.
+    ONE launch (drn_rank_fuse_topn, csrc/retrieve_rrf.hip: one workgroup a sentence sorts the M * C entries in LDS, folds and sorts
+    again), after the M + 1 copies of a sequence; no dense buffer, no table read, no host synchronisation, and it can be captured in a
+    graph once the shape is warmed, where the lists' contents, the weights tensor and the mask may change in place between replays.
+    What this is NOT: the votes depend on the depth the lists were cut at -- see rank_fuse_reference."""
+    what = "rank_fuse"
+    lists, S, V, weights, k0 = _check_rank_fuse(what, lists, V, weights, k0, missing, allow)
+    n = _check_depth(what, n)
+    if out is not None:
+        _check_list_out(what, out, S, n)
+    else:
+        out = _list_buffers(weights.device, S, n)
+    ops.rank_fuse_topn(_stacked_lists(lists), V, weights, k0, missing, n, *out, allow=allow)
+    return Shortlist(*out)
+
+
+def rank_fuse_rank(lists, V, targets, weights=None, k0=60.0, missing="skip", allow=None, out=None):
+    """The place of each sentence's TARGET video in the full order of rank_fuse -> TargetRank, on the device
+    (rank_fuse_rank_reference defines it): lists, V, weights, k0, missing and allow as in rank_fuse; targets: contiguous int32 (S,) on
+    the lists' device, never read on the host, a value outside [0, V) meaning "no target"; out: three (S,) buffers (rank, score,
+    total).  rank[s] = k >= 0 exactly when rank_fuse(lists, V, n).ids[s, k] is the target for every n > k, score[s] has the listed
+    score's bits and total[s] counts the fused candidates.  ONE launch (drn_rank_fuse_rank), no host synchronisation, capturable."""
+    what = "rank_fuse_rank"
+    lists, S, V, weights, k0 = _check_rank_fuse(what, lists, V, weights, k0, missing, allow)
+    _check_targets(what, S, targets, weights.device)
+    _check_rank_out(what, S, out)
+    if out is None:
+        out = _rank_buffers(weights.device, S)
+    ops.rank_fuse_rank(_stacked_lists(lists), V, weights, k0, missing, targets, *out, allow=allow)
+    return TargetRank(*out)
+
+
+class RankFusedShortlister(object):
+    """RankFusedShortlister(tables, weights=None, k0=60.0, depth=SHORTLIST_MAX, missing="skip"): several tables over the same videos
+    ranked as one BY RANK -- each table lists its best `depth` videos its own way (its own rows, E, dtype, quantisation, shards, late
+    interaction) and the lists are fused by rank_fuse: what FusedShortlister cannot do for tables whose scores share no scale, and
+    cheaper -- no dense 4 * M * S * V buffers, M * S * depth ids instead.
+
+    tables: 1 to RANK_FUSE_MAX_LISTS Shortlister / ShardedShortlister objects over the SAME V videos on one device, held by
+    reference; names as in FusedShortlister (equal position by position where given, refused here).  weights, k0 and missing as in
+    rank_fuse; a device weights tensor is kept by reference.  depth: the length each table's list is cut at, 1 <= depth <=
+    SHORTLIST_DEEP_MAX: a Shortlister lists by shortlist() up to SHORTLIST_MAX and by shortlist_deep() beyond it; a ShardedShortlister
+    and a late item have no deep entry, so a depth above SHORTLIST_MAX is refused for them -- the table here, the item in the call,
+    before any launch.
+
+    What this is NOT: a fusion of scores.  A video outside a table's best `depth` gets no vote from it (under "drop" it is no
+    candidate), so the answer depends on depth; rank_fuse_reference over the tables' own shortlist().ids is the definition.
+    Attributes: tables, weights (the device tensor), k0, depth, missing, names, device; len() is V."""
+
+    def __init__(self, tables, weights=None, k0=60.0, depth=SHORTLIST_MAX, missing="skip"):
+        what = "RankFusedShortlister"
+        tables, names = _fused_tables(what, tables, missing, RANK_FUSE_MAX_LISTS)
+        k0, depth = _check_k0(what, k0), int(depth)
+        if not 1 <= depth <= SHORTLIST_DEEP_MAX:
+            raise DrnError("%s: depth = %d outside [1, %d]" % (what, depth, SHORTLIST_DEEP_MAX))
+        for m, table in enumerate(tables):
+            if depth > SHORTLIST_MAX and isinstance(table, ShardedShortlister):
+                raise DrnError("%s: depth = %d above SHORTLIST_MAX = %d needs shortlist_deep, and table %d is a ShardedShortlister, which "
+                               "has no deep entry (compact() it into one table first)" % (what, depth, SHORTLIST_MAX, m))
+        weights = _fused_weights(what, weights, len(tables), tables[0].device, "tables")
+        self.tables, self.weights, self.k0, self.depth, self.missing, self.names = tables, weights, k0, depth, missing, names
+        self._bufs = {}
+
+    @property
+    def device(self):
+        return self.tables[0].device
+
+    def __len__(self):
+        return len(self.tables[0])
+
+    def _check_items(self, what, queries, allow):
+        """What shortlist() and rank() refuse about the query items and the mask, ALL before the first launch -> (S, items)."""
+        S, items = _check_fused_items(what, self.tables, queries)
+        for m, (_, lengths) in enumerate(items):
+            if lengths is not None and self.depth > SHORTLIST_MAX:
+                raise DrnError("%s: depth = %d above SHORTLIST_MAX = %d needs shortlist_deep, and item %d selects late interaction, which "
+                               "has no deep entry" % (what, self.depth, SHORTLIST_MAX, m))
+        if allow is not None:
+            _check_packed_allow(allow, S, len(self), self.device)
+        return S, items
+
+    def _lists(self, S, items, allow):
+        """Each table's own list of `depth` under the mask, its ids into slice [m] of the stacked buffer kept per S -> that buffer."""
+        bufs, depth = self._bufs.get(S), self.depth
+        if bufs is None:
+            bufs = self._bufs[S] = (torch.empty((len(self.tables), S, depth), dtype=torch.int32, device=self.device),) \
+                + _list_buffers(self.device, S, depth, rows=True)[1:]
+        ids, scores, counts, rows = bufs                          # (scores, counts and rows are scratch: only the ids are fused)
+        for m, (table, (q, lengths)) in enumerate(zip(self.tables, items)):
+            if lengths is not None:
+                table.shortlist_late(q, lengths, depth, out=(ids[m], scores, counts), allow=allow)
+                continue
+            first = table if isinstance(table, Shortlister) else table.shards[0]
+            out = (ids[m], scores, counts) + ((rows,) if first._seg is not None else ())
+            (table.shortlist_deep if depth > SHORTLIST_MAX else table.shortlist)(q, depth, out=out, allow=allow)
+        return ids
+
+    def shortlist(self, queries, n, out=None, allow=None):
+        """Each sentence's best n videos under the fused reciprocal ranks -> Shortlist, on the device: rank_fuse over the tables' own
+        shortlist(item, depth, allow=allow).ids, bit for bit.  queries: the M items of FusedShortlister.shortlist, a pair (queries,
+        lengths) selecting that table's shortlist_late; every item holds the same S sentences.  1 <= n <= SHORTLIST_DEEP_MAX.  out:
+        the three buffers of a Shortlist.  allow: a packed mask over the V videos; it goes to the TABLES' shortlists, so the filter
+        comes before the ranking -- a masked video takes no rank in any list -- and the fusing launch runs unmasked.  Each table's
+        launches into buffers kept per S, then ONE fusing launch; no host synchronisation, capturable once the shape is warmed,
+        where the queries, lengths, the weights tensor and the mask's contents may change in place between replays."""
+        what = "RankFusedShortlister.shortlist"
+        S, items = self._check_items(what, queries, allow)
+        n = _check_depth(what, n)
+        if out is not None:
+            _check_list_out(what, out, S, n)
+        else:
+            out = _list_buffers(self.device, S, n)
+        ops.rank_fuse_topn(self._lists(S, items, allow), len(self), self.weights, self.k0, self.missing, n, *out)
+        return Shortlist(*out)
+
+    def rank(self, queries, targets, out=None, allow=None):
+        """The place of each sentence's TARGET video in the full fused order -> TargetRank, on the device (rank_fuse_rank over the
+        tables' own lists): queries and allow as in shortlist(), targets and out= as in Shortlister.rank.  rank[s] = k >= 0 exactly
+        when shortlist(queries, n).ids[s, k] is the target for every n > k; -1 where no list holds the target (or, under "drop", not
+        every list).  evaluate_shortlist(rank_fused, batches) works as it stands, batch[1] being the M items."""
+        what = "RankFusedShortlister.rank"
+        S, items = self._check_items(what, queries, allow)
+        _check_targets(what, S, targets, self.device)
+        _check_rank_out(what, S, out)
+        if out is None:
+            out = _rank_buffers(self.device, S)
+        ops.rank_fuse_rank(self._lists(S, items, allow), len(self), self.weights, self.k0, self.missing, targets, *out)
+        return TargetRank(*out)

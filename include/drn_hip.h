@@ -980,6 +980,29 @@ int drn_shortlist_fuse_rank(const float* scores, long long stride_m, int ld, con
 int drn_shortlist_fuse_rerank(const float* scores, long long stride_m, int ld, const float* weights, int M, int mode,
                               const int32_t* candidates, const int32_t* allow, int allow_stride, int V, int C, int S, int n, void* ws,
                               int ws_keys, int32_t* ids, float* out_scores, int32_t* counts, void* stream);
+/* RANK FUSION (drn_amd/csrc/retrieve_rrf.hip; drn_amd.retrieve.rank_fuse_reference and rank_fuse_rank_reference are the definitions):
+ * reciprocal-rank fusion of M finished id lists over the same V videos, for tables whose scores share no scale.  lists holds M stacked
+ * [S][C] int32 matrices ON THE DEVICE, element (m, s, j) at lists[m * stride_m + s * ld + j], ld >= C, 1 <= M <= DRN_RANK_FUSE_MAX_LISTS (a
+ * CHOICE: M * C words of 8 bytes fill 64 KiB of LDS), 1 <= C <= DRN_SHORTLIST_DEEP_MAX -- other shortlists' ids as they lie on the device.
+ * An entry outside [0, V) means nothing (-1, V, INT_MIN, INT_MAX), and of a position repeated in one row of one list the first
+ * occurrence counts; the RANK of video v in list m is the column j of that first occurrence.  weights [M] fp32 ON THE DEVICE (never read
+ * on the host); k0 >= 0 and finite.  In fp32, nothing contracted:
+ *   acc = +0;  for m ascending over the lists that hold v:  acc = acc + w[m] / (k0 + float(j + 1))      (the division correctly rounded)
+ *   candidate = isfinite(acc) and allowed(s, v) and (DRN_FUSE_SKIP: some list holds v | DRN_FUSE_DROP: every list holds v).
+ * drn_rank_fuse_topn lists each sentence's candidates by acc descending, then position ascending, cut to n, 1 <= n <=
+ * DRN_SHORTLIST_DEEP_MAX, into ids / scores [S][n] and counts [S] with the -1 / 0 padding of drn_shortlist_topn.  drn_rank_fuse_rank
+ * answers drn_shortlist_rank's three fields in that order: targets [S] int32 on the device (a value outside [0, V) means "no target"; it
+ * is compared, never used as an index), rank = the candidates that precede the target (-1 where it is no candidate), score = its acc (0
+ * beside -1), total = the candidates.  allow: a packed mask as in the *_allow entries, or NULL; a mask word is read only for an id
+ * already known to lie in [0, V).  Every pointer is 4-byte aligned.  ONE launch each, one workgroup per sentence: the entries are sorted
+ * in LDS (a power of two >= M * C words, 256 to 8192), folded, and the candidates sorted again; no workspace, no atomics, no host
+ * synchronisation; the lists, the weights, the targets and the mask may change between replays of a captured graph. */
+#define DRN_RANK_FUSE_MAX_LISTS 8
+int drn_rank_fuse_topn(const int32_t* lists, long long stride_m, int ld, int C, int M, int V, const float* weights, float k0, int mode,
+                       const int32_t* allow, int allow_stride, int S, int n, int32_t* ids, float* scores, int32_t* counts, void* stream);
+int drn_rank_fuse_rank(const int32_t* lists, long long stride_m, int ld, int C, int M, int V, const float* weights, float k0, int mode,
+                       const int32_t* allow, int allow_stride, int S, const int32_t* targets, int32_t* rank, float* score, int32_t* total,
+                       void* stream);
 /* The data half of Grounder.search(candidates= a device tensor): cand [S][N] int32 on the device, row s = sentence s's set of
  * positions in a store of Nv videos (an entry outside [0, Nv) is no candidate; of a position repeated in a row the first occurrence
  * counts, across the whole row), 1 <= N <= DRN_CANDIDATES_MAX (a choice: one row is held in 4 KiB of LDS) -> table [steps][pairs], the
