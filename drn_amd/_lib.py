@@ -27,6 +27,7 @@ LATE_MAX_TOKENS = 64      # DRN_LATE_MAX_TOKENS: token vectors of one sentence o
 CANDIDATES_MAX = 1024     # DRN_CANDIDATES_MAX: columns of a device candidates tensor (a choice: one row in 4 KiB of LDS)
 RERANK_MAX_CANDIDATES = CANDIDATES_MAX  # DRN_RERANK_MAX_CANDIDATES: columns of the list drn_shortlist_rerank takes (a CHOICE: the width the Grounder takes)
 SHORTLIST_DEEP_MAX = RERANK_MAX_CANDIDATES  # DRN_SHORTLIST_DEEP_MAX: the longest list drn_shortlist_deep returns (a CHOICE: the width its consumers take)
+BINARY_MAX_E = 4096       # DRN_BINARY_MAX_E: columns of a table of sign codes (a CHOICE: 16 sentences' query codes are 8 KiB of LDS)
 RERANK_GROUP = 16         # DRN_RERANK_GROUP: slots of a list one workgroup of drn_shortlist_rerank scores (a choice, not a measurement)
 FUSE_MAX_TABLES = 8       # DRN_FUSE_MAX_TABLES: score matrices drn_shortlist_fuse_topn / _rank fold (a choice, not a measurement)
 FUSE_MODES = {"drop": 0, "skip": 1}   # DRN_FUSE_DROP / DRN_FUSE_SKIP
@@ -200,6 +201,8 @@ SIGNATURES = {
                                              c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_deep": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "drn_shortlist_bin": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_late_topn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "drn_shortlist_late_topn_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

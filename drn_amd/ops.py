@@ -1671,6 +1671,53 @@ def shortlist_deep(table, queries, seg, n, ws, outs, allow):
     return outs
 
 
+def binary_words(E):
+    """The int32 words of one row of sign codes over E columns: ceil(E / 32) (allow_words' arithmetic: the bit convention is the same)."""
+    return -(-int(E) // 32)
+
+
+def shortlist_bin(codes, E, queries, seg, n, ws, outs, allow):
+    """The BINARY shortlist, 1 <= n <= SHORTLIST_DEEP_MAX, behind one entry and one tag (drn_shortlist_bin / shortlist_bin): codes
+    (rows, W) int32 sign codes, W = binary_words(E), 1 <= E <= BINARY_MAX_E (drn_amd.binary.binary_quantize_reference is the format);
+    queries (S, E) float32 / bfloat16, binarised by the launch; seg is () or (offsets, blk_vid, vid_blk), outs is (ids, scores, counts)
+    or (ids, scores, counts, rows) -- as in shortlist_deep, with its checks and its workspace sizes (shortlist_ws_keys /
+    shortlist_segments_ws_keys); drn_amd.binary.binary_shortlist_reference is the definition.  allow is REQUIRED: a packed mask (W,) or
+    (S, W) int32 on the device (a caller without a filter passes a row of all-ones words).  Two launches on a plain table, three on a
+    ragged one, on the current stream; nothing is read on the host."""
+    what = "shortlist_bin"
+    if allow is None:
+        raise _lib.DrnError("%s: allow is required: a packed mask (pass a row of all-ones words to list every video)" % what)
+    seg, outs = tuple(seg), tuple(outs)
+    if len(seg) not in (0, 3) or len(outs) != (4 if seg else 3):
+        raise _lib.DrnError("%s: seg must be () or (offsets, blk_vid, vid_blk) and outs (ids, scores, counts) or, on a ragged table, "
+                            "(ids, scores, counts, rows)" % what)
+    _need_gpu(*((codes, queries) + seg + (allow, ws) + outs))
+    E, n = int(E), int(n)
+    if not 1 <= E <= _lib.BINARY_MAX_E:
+        raise _lib.DrnError("%s: E = %d outside [1, %d]" % (what, E, _lib.BINARY_MAX_E))
+    cs, qs = tuple(codes.shape), tuple(queries.shape)
+    if codes.dtype != torch.int32 or len(cs) != 2 or cs[0] < 1 or cs[1] != binary_words(E) or not codes.is_contiguous():
+        raise _lib.DrnError("%s: codes must be a contiguous (rows, %d) torch.int32 tensor, ceil(E / 32) words a row for E = %d, not %s %s"
+                            % (what, binary_words(E), E, codes.dtype, cs))
+    if len(qs) != 2 or qs[0] < 1 or qs[1] != E or not queries.is_contiguous() or queries.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.DrnError("%s: queries must be a contiguous (S, %d) float32 / bfloat16 tensor" % (what, E))
+    rows, S = int(cs[0]), int(qs[0])
+    if seg:
+        V, nblocks = _segment_tables(what, *seg)
+        need = shortlist_segments_ws_keys(nblocks, S, n)
+    else:
+        V, nblocks = rows, 0
+        need = shortlist_ws_keys(V, S, n)
+    _shortlist_buffers(what, S, n, need, ws, *outs, cap=_lib.SHORTLIST_DEEP_MAX)
+    mask, stride = _allow_args(what, allow, V, S)
+    args = (_p(codes), _p(queries)) + (tuple(_p(t) for t in seg) if seg else (None, None, None))
+    args += (mask, stride, rows if seg else 0, V, nblocks, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)))
+    args += tuple(_p(t) for t in outs) + (() if seg else (None,))
+    # (per (sentence, row): E bit products and E additions, as the dot product they stand for)
+    _timed(what, 2.0 * S * rows * E, lambda: check(lib().drn_shortlist_bin(*args, _stream()), "drn_shortlist_bin"))
+    return outs
+
+
 def shortlist_late_ws_keys(nblocks, S, n):
     """The 8-byte keys of workspace drn_shortlist_late_topn needs: S * nblocks * min(n, SHORTLIST_SEG_BLOCK)."""
     return int(S) * int(nblocks) * min(int(n), _lib.SHORTLIST_SEG_BLOCK)

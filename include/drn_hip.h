@@ -723,6 +723,24 @@ int drn_shortlist_segments_topn_q8_allow(const uint8_t* codes, const uint8_t* sc
 int drn_shortlist_deep(const void* table, const uint8_t* scales, const void* queries, const int32_t* offsets, const int32_t* blk_vid,
                        const int32_t* vid_blk, const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int n,
                        int dtype, void* ws, int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
+/* The BINARY shortlist (drn_amd/csrc/retrieve_bin.hip): a table of 1-bit SIGN CODES ranked by Hamming distance.  codes [rows][W] int32,
+ * W = ceil(E / 32): bit e & 31 of word e >> 5 is 1 unless x[row][e] < 0 (+0 and -0 give 1), bits at or past E are 0 -- a packed allow
+ * mask's convention, and drn_pack_allow over ~(x < 0) is the quantiser.  queries [S][E] are floats of `dtype`; the launch binarises
+ * them by the same rule, and a row with an element that is not finite lists nothing.  score[s][r] = E - 2 popcount(code(q_s) xor
+ * codes[r]) over the E real bits = sum_e sign(q_e) sign(x_e), an integer that is exact as a float: 1 <= E <= DRN_BINARY_MAX_E (a CHOICE:
+ * 16 sentences' query codes are 8 KiB of LDS).  The conventions are drn_shortlist_deep's: offsets == NULL is one row per video --
+ * blk_vid, vid_blk and rows must then be NULL too, and R and nblocks are ignored; otherwise all four are given, a video is scored by
+ * its best row and rows names the lowest row that reaches it.  allow is REQUIRED: a packed mask over the videos with stride 0 or
+ * ceil(V / 32), 4-byte aligned (a caller without a filter passes one row of all-ones words with stride 0).  1 <= n <=
+ * DRN_SHORTLIST_DEEP_MAX; the total order, the -1 / 0 / -1 padding and the clamps of every index read from the device tables are those
+ * of drn_shortlist_topn and drn_shortlist_segments_topn.  ws: ws_keys >= S * blocks * min(n, 256) 8-byte keys, times 1.5 on a ragged
+ * table.  Two launches on a plain table, three on a ragged one: the XOR / popcount phase one (one table row per thread, 16-byte loads
+ * when W % 4 == 0), then the merge of drn_shortlist_deep at every n, and the segment look-up.  No
+ * atomics, no host synchronisation; the queries and the mask may change between replays of a captured graph. */
+#define DRN_BINARY_MAX_E 4096
+int drn_shortlist_bin(const int32_t* codes, const void* queries, const int32_t* offsets, const int32_t* blk_vid, const int32_t* vid_blk,
+                      const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys,
+                      int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
 /* The shortlist by LATE INTERACTION over a ragged table (drn_amd/csrc/retrieve_late.hip): queries [S][L][E] holds L token vectors a
  * sentence, lengths [S] int32 on the device says how many of them are live -- clamped into [0, L] on the device, never read on the host;
  * the contents of a token at or past it are not read.  sim[s][t][v] = drn_shortlist_segments_topn's score of (query row (s, t), video
