@@ -17,5 +17,5 @@ from .retrieve import (FUSE_MAX_TABLES, FusedShortlister, fuse_scores_reference,
                        fused_rerank, fused_rerank_reference, rerank_scores_reference, scores_reference, shortlist_scores)
 from .retrieve import (RANK_FUSE_MAX_LISTS, RankFusedShortlister, rank_fuse, rank_fuse_rank, rank_fuse_rank_reference,  # noqa: E402,F401
                        rank_fuse_reference)
-from .binary import (BINARY_MAX_E, BinaryShortlister, binary_dequantize, binary_quantize_reference, binary_shortlist_reference,  # noqa: E402,F401
-                     binary_signs)
+from .binary import (BINARY_MAX_E, AsymmetricBinaryView, BinaryShortlister, binary_asym_shortlist_reference, binary_dequantize,  # noqa: E402,F401
+                     binary_quantize_reference, binary_shortlist_reference, binary_signs)

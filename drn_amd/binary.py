@@ -21,16 +21,23 @@ SHORTLIST_DEEP_MAX videos a sentence under either name, plain or ragged, with al
 field bit for bit what dequantized().shortlist_deep(binary_signs(queries), n, allow=allow) gives.  It is a legal `coarse` of
 drn_amd.search_eval.evaluate_cascade(..., deep=True).
 
-What this is NOT: scoring is symmetric (float queries against sign bits are not scored), there is no rank / rerank / scores / late
-interaction on a binary table and no binary shard of a ShardedShortlister, and nothing here says anything about recall: that is what
-evaluate_cascade measures on real embeddings."""
+THE ASYMMETRIC SCORE.  score[s, r] = sum_e q[s, e] * sign(x[r, e]): the query keeps its magnitudes, which cost nothing to keep, and the
+table stays one bit a dimension.  It is the PLAIN shortlist over the +-1 table the codes stand for, so it has no arithmetic of its own:
+binary_asym_shortlist_reference is shortlist_reference / segment_shortlist_reference over binary_dequantize(codes, E, float64), and
+shortlist_asym() (drn_shortlist_bin_asym, csrc/retrieve_bin_asym.hip: the plain MFMA chain with its table operand built from the code
+bits in registers) is bit for bit dequantized().shortlist_deep(queries, n, allow=allow).  asymmetric() is a view of the same table
+whose shortlist() / shortlist_deep() score that way: the `coarse` of evaluate_cascade(..., deep=True) that compares the two scorings
+on one resident table.
+
+What this is NOT: there is no rank / rerank / scores / late interaction on a binary table and no binary shard of a
+ShardedShortlister, and nothing here says anything about recall: that is what evaluate_cascade measures on real embeddings."""
 import numpy as np
 import torch
 
 from . import ops
 from ._lib import BINARY_MAX_E, SHORTLIST_DEEP_MAX, DrnError     # BINARY_MAX_E = 4096 is a CHOICE: 16 sentences' query codes in 8 KiB of LDS
 from .retrieve import (SegmentShortlist, Shortlist, Shortlister, _allow_of, _allowed, _check_list_out, _check_packed_allow, _list_buffers,
-                       _listed, check_segment_offsets, pack_allow_reference)
+                       _listed, check_segment_offsets, pack_allow_reference, segment_shortlist_reference, shortlist_reference)
 
 BINARY_PACK_ELEMS = 1 << 26   # elements of the bool temporary one pack_allow launch of the constructor reads (64 MiB): a CHOICE, not a measurement
 
@@ -133,6 +140,24 @@ def binary_shortlist_reference(codes, E, queries, n, offsets=None, allow=None):
     m = int(order.shape[1])
     segs[:, :m] = torch.where(listed, torch.gather(rows, 1, order).to(torch.int32), segs[:, :m])
     return SegmentShortlist(ids, scores, count, segs)
+
+
+def binary_asym_shortlist_reference(codes, E, queries, n, offsets=None, allow=None):
+    """THE DEFINITION of an ASYMMETRIC binary shortlist, in float64 (usable on the CPU).  codes (rows, W) int32 sign codes over E columns,
+    queries (S, E) floats, NOT binarised: score[s, r] = sum_e queries[s, e] * (+1 where bit e of codes[r] is set, else -1).  It is
+    shortlist_reference(binary_dequantize(codes, E, torch.float64), queries.double(), n, allow) on a plain table and, with offsets (V +
+    1 non-decreasing integers from 0 to rows), segment_shortlist_reference over the same table: a Shortlist or a SegmentShortlist under
+    the total order score descending, then position ascending, then the lowest segment.  allow: a bool tensor (V,) or (S, V), exactly
+    as in those references.  A query row that holds an element that is not finite lists nothing: each of its scores is a sum with an
+    infinity or a NaN among its terms, so none is finite.  The refusals are binary_shortlist_reference's."""
+    codes, E = _check_codes("binary_asym_shortlist_reference", codes, E)
+    if not torch.is_tensor(queries) or queries.dim() != 2 or int(queries.shape[1]) != E or queries.shape[0] < 1:
+        raise DrnError("binary_asym_shortlist_reference: the queries must be a float tensor (S, %d)" % E)
+    wide = binary_dequantize(codes, E, torch.float64)
+    q = queries.double().to(codes.device)
+    if offsets is None:
+        return shortlist_reference(wide, q, n, allow)
+    return segment_shortlist_reference(wide, offsets, q, n, allow)
 
 
 class BinaryShortlister(object):
@@ -239,7 +264,23 @@ class BinaryShortlister(object):
         of a captured graph.  No host synchronisation, and the call can be captured once the (S, n) workspace is warm.  Every field
         is bit for bit dequantized().shortlist_deep(binary_signs(queries), n, allow=allow).  One entry (drn_shortlist_bin): two
         launches, three on a ragged table.  shortlist_deep is the same method under the name evaluate_cascade(deep=True) calls."""
-        what = "BinaryShortlister.shortlist"
+        return self._shortlist("BinaryShortlister.shortlist", ops.shortlist_bin, queries, n, out, allow)
+
+    shortlist_deep = shortlist
+
+    def shortlist_asym(self, queries, n, out=None, allow=None):
+        """The ASYMMETRIC shortlist: queries (S, E) on the device in self.dtype, scored AS THEY ARE against the +-1 the codes stand for
+        (score[s, r] = sum_e q[s, e] * sign(x[r, e]); binary_asym_shortlist_reference defines it), and 1 <= n <= SHORTLIST_DEEP_MAX ->
+        Shortlist, or SegmentShortlist on a ragged table, on the device.  The checks, out=, the packed allow=, the workspaces (kept
+        per (S, n) and shared with shortlist()), the result types and the -1 / 0 / -1 padding are shortlist()'s.  A query row that
+        holds an element that is not finite lists nothing.  No host synchronisation, and the call can be captured once the (S, n)
+        workspace is warm; the mask's contents may change between replays.  Every field is bit for bit
+        dequantized().shortlist_deep(queries, n, allow=allow).  One entry (drn_shortlist_bin_asym): two launches, three on a ragged
+        table."""
+        return self._shortlist("BinaryShortlister.shortlist_asym", ops.shortlist_bin_asym, queries, n, out, allow)
+
+    def _shortlist(self, what, entry, queries, n, out, allow):
+        """shortlist and shortlist_asym: the refusals, the buffers, the workspace and the ONE call of `entry` (an ops wrapper)."""
         S, n = self._check_queries(what, queries, n=n, on_table=False, cap=SHORTLIST_DEEP_MAX)
         seg = self._seg
         if out is not None:
@@ -252,10 +293,53 @@ class BinaryShortlister(object):
             out = _list_buffers(self.codes.device, S, n, rows=seg is not None)
         if seg is None:
             ws = self._workspace((S, n), lambda: ops.shortlist_ws_keys(len(self), S, n))
-            ops.shortlist_bin(self.codes, self.E, queries.contiguous(), (), n, ws, tuple(out), allow)
+            entry(self.codes, self.E, queries.contiguous(), (), n, ws, tuple(out), allow)
             return Shortlist(*out)
         ws = self._workspace((S, n), lambda: ops.shortlist_segments_ws_keys(self._nblocks(), S, n))
-        ops.shortlist_bin(self.codes, self.E, queries.contiguous(), seg, n, ws, tuple(out), allow)
+        entry(self.codes, self.E, queries.contiguous(), seg, n, ws, tuple(out), allow)
         return SegmentShortlist(*out)
+
+    def asymmetric(self):
+        """A light VIEW of this table whose shortlist() / shortlist_deep() are shortlist_asym(): the same codes, names, offsets and plan,
+        nothing copied.  It is a legal `coarse` of drn_amd.search_eval.evaluate_cascade(..., deep=True), so the two scorings can be
+        compared on one resident table."""
+        return AsymmetricBinaryView(self)
+
+
+class AsymmetricBinaryView(object):
+    """BinaryShortlister.asymmetric(): the table `base` under ASYMMETRIC scoring.  shortlist and shortlist_deep are base.shortlist_asym;
+    names, device, dtype, E, codes, offsets, plan, nbytes, len(), check, allow_of and dequantized are base's own.  Nothing is copied and
+    no workspace is kept here."""
+
+    def __init__(self, base):
+        if not isinstance(base, BinaryShortlister):
+            raise DrnError("AsymmetricBinaryView: the table must be a BinaryShortlister")
+        self.base = base
+
+    names = property(lambda self: self.base.names)
+    device = property(lambda self: self.base.device)
+    dtype = property(lambda self: self.base.dtype)
+    E = property(lambda self: self.base.E)
+    codes = property(lambda self: self.base.codes)
+    offsets = property(lambda self: self.base.offsets)
+    plan = property(lambda self: self.base.plan)
+    nbytes = property(lambda self: self.base.nbytes)
+
+    def __len__(self):
+        return len(self.base)
+
+    def check(self, store):
+        return self.base.check(store)
+
+    def allow_of(self, keep=None, drop=None):
+        return self.base.allow_of(keep=keep, drop=drop)
+
+    def dequantized(self):
+        """base.dequantized(): the oracle shortlist() answers bit for bit like, given the queries as they are."""
+        return self.base.dequantized()
+
+    def shortlist(self, queries, n, out=None, allow=None):
+        """base.shortlist_asym(queries, n, out=out, allow=allow)."""
+        return self.base.shortlist_asym(queries, n, out=out, allow=allow)
 
     shortlist_deep = shortlist

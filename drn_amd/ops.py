@@ -1676,15 +1676,8 @@ def binary_words(E):
     return -(-int(E) // 32)
 
 
-def shortlist_bin(codes, E, queries, seg, n, ws, outs, allow):
-    """The BINARY shortlist, 1 <= n <= SHORTLIST_DEEP_MAX, behind one entry and one tag (drn_shortlist_bin / shortlist_bin): codes
-    (rows, W) int32 sign codes, W = binary_words(E), 1 <= E <= BINARY_MAX_E (drn_amd.binary.binary_quantize_reference is the format);
-    queries (S, E) float32 / bfloat16, binarised by the launch; seg is () or (offsets, blk_vid, vid_blk), outs is (ids, scores, counts)
-    or (ids, scores, counts, rows) -- as in shortlist_deep, with its checks and its workspace sizes (shortlist_ws_keys /
-    shortlist_segments_ws_keys); drn_amd.binary.binary_shortlist_reference is the definition.  allow is REQUIRED: a packed mask (W,) or
-    (S, W) int32 on the device (a caller without a filter passes a row of all-ones words).  Two launches on a plain table, three on a
-    ragged one, on the current stream; nothing is read on the host."""
-    what = "shortlist_bin"
+def _shortlist_bin_entry(what, codes, E, queries, seg, n, ws, outs, allow):
+    """shortlist_bin / shortlist_bin_asym: one argument list, one list of checks, the entry drn_<what> under the tag <what>."""
     if allow is None:
         raise _lib.DrnError("%s: allow is required: a packed mask (pass a row of all-ones words to list every video)" % what)
     seg, outs = tuple(seg), tuple(outs)
@@ -1714,8 +1707,28 @@ def shortlist_bin(codes, E, queries, seg, n, ws, outs, allow):
     args += (mask, stride, rows if seg else 0, V, nblocks, E, S, n, dtype_code(queries), _p(ws), int(min(ws.numel(), 0x7fffffff)))
     args += tuple(_p(t) for t in outs) + (() if seg else (None,))
     # (per (sentence, row): E bit products and E additions, as the dot product they stand for)
-    _timed(what, 2.0 * S * rows * E, lambda: check(lib().drn_shortlist_bin(*args, _stream()), "drn_shortlist_bin"))
+    _timed(what, 2.0 * S * rows * E, lambda: check(getattr(lib(), "drn_" + what)(*args, _stream()), "drn_" + what))
     return outs
+
+
+def shortlist_bin(codes, E, queries, seg, n, ws, outs, allow):
+    """The BINARY shortlist, 1 <= n <= SHORTLIST_DEEP_MAX, behind one entry and one tag (drn_shortlist_bin / shortlist_bin): codes
+    (rows, W) int32 sign codes, W = binary_words(E), 1 <= E <= BINARY_MAX_E (drn_amd.binary.binary_quantize_reference is the format);
+    queries (S, E) float32 / bfloat16, binarised by the launch; seg is () or (offsets, blk_vid, vid_blk), outs is (ids, scores, counts)
+    or (ids, scores, counts, rows) -- as in shortlist_deep, with its checks and its workspace sizes (shortlist_ws_keys /
+    shortlist_segments_ws_keys); drn_amd.binary.binary_shortlist_reference is the definition.  allow is REQUIRED: a packed mask (W,) or
+    (S, W) int32 on the device (a caller without a filter passes a row of all-ones words).  Two launches on a plain table, three on a
+    ragged one, on the current stream; nothing is read on the host."""
+    return _shortlist_bin_entry("shortlist_bin", codes, E, queries, seg, n, ws, outs, allow)
+
+
+def shortlist_bin_asym(codes, E, queries, seg, n, ws, outs, allow):
+    """The ASYMMETRIC binary shortlist behind one entry and one tag (drn_shortlist_bin_asym / shortlist_bin_asym): the arguments, the
+    checks and the workspace sizes of shortlist_bin, but the queries keep their magnitudes: score[s, r] = sum_e q[s, e] * (+-1 of bit e
+    of codes[r]), every field bit for bit shortlist_deep over drn_amd.binary.binary_dequantize(codes, E, queries.dtype);
+    drn_amd.binary.binary_asym_shortlist_reference is the definition.  Two launches on a plain table, three on a ragged one, on the
+    current stream; nothing is read on the host."""
+    return _shortlist_bin_entry("shortlist_bin_asym", codes, E, queries, seg, n, ws, outs, allow)
 
 
 def shortlist_late_ws_keys(nblocks, S, n):

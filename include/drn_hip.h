@@ -741,6 +741,19 @@ int drn_shortlist_deep(const void* table, const uint8_t* scales, const void* que
 int drn_shortlist_bin(const int32_t* codes, const void* queries, const int32_t* offsets, const int32_t* blk_vid, const int32_t* vid_blk,
                       const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws, int ws_keys,
                       int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
+/* The ASYMMETRIC binary shortlist (drn_amd/csrc/retrieve_bin_asym.hip): FLOAT queries against the same table of sign codes.  score[s][r] =
+ * sum_e q[s][e] * (codes[r] bit e set ? +1 : -1): the queries keep their magnitudes, the table stays one bit a column.  It IS
+ * drn_shortlist_deep over the (rows, E) table of +-1 in `dtype` that the codes stand for, bit for bit in every field: phase one runs
+ * that entry's MFMA chain (the same K-steps in ascending order, 32 columns a step in bf16 and 16 in fp32) with its table operand built
+ * from the code bits in registers, a column at or past E zero on both sides.  A score that is not finite is not listed, so a query row
+ * that holds an element that is not finite lists nothing.  The argument list, the argument checks, the conventions (offsets == NULL is
+ * one row per video), the REQUIRED mask, 1 <= n <= DRN_SHORTLIST_DEEP_MAX, 1 <= E <= DRN_BINARY_MAX_E, the workspace, the order, the
+ * padding and the clamps are drn_shortlist_bin's.  Two launches on a plain table, three on a ragged one: phase one (16-byte loads of a
+ * row's words when W % 4 == 0), then the merge of drn_shortlist_deep at every n, and the segment look-up.  No atomics, no host
+ * synchronisation; the queries and the mask may change between replays of a captured graph. */
+int drn_shortlist_bin_asym(const int32_t* codes, const void* queries, const int32_t* offsets, const int32_t* blk_vid, const int32_t* vid_blk,
+                           const int32_t* allow, int allow_stride, int R, int V, int nblocks, int E, int S, int n, int dtype, void* ws,
+                           int ws_keys, int32_t* ids, float* scores, int32_t* counts, int32_t* rows, void* stream);
 /* The shortlist by LATE INTERACTION over a ragged table (drn_amd/csrc/retrieve_late.hip): queries [S][L][E] holds L token vectors a
  * sentence, lengths [S] int32 on the device says how many of them are live -- clamped into [0, L] on the device, never read on the host;
  * the contents of a token at or past it are not read.  sim[s][t][v] = drn_shortlist_segments_topn's score of (query row (s, t), video
